@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py — BASELINE.json metric on MI355X: Gauss-Newton iterations/s (+ factorise ms) on M3500, chi^2 matched.
 
-    python bench.py --gpus N --steps K --warmup W            (N > 1 is launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]     (N > 1 is launched by torch.distributed.run)
+
+A plain run sets up, warms up (W steps), times K steps, writes what they left (--dump-outputs) and prints ONE JSON line with the contract
+fields and `config`.  Everything else below -- the parity gate, the instrumented pass and `roofline`, the API-call figures, the CPU
+baseline, the lattices, the incremental demo and the side file -- runs only with --full.
 
 A "step" is one batch Gauss-Newton iteration of the hot path (relinearise -> linearise -> assemble ->
 factorise -> solve -> update) over the whole M3500 graph (3500 poses, 5453 xyt factors + the prior), with
@@ -16,7 +20,7 @@ states valid in the host objects on return -- and that number stands right besid
 `ms_per_api_call` (the same K steps as K warm API calls inside the same barrier + synchronize brackets, max over ranks);
 `speedup_vs_cpu_baseline` is computed from the API number, because the reference's figure is a whole call too.
 
-Rank 0 prints ONE JSON line with the contract fields plus
+With --full, rank 0's ONE JSON line carries the contract fields plus
   roofline     — dominant kernel (by HIP-event time) of an instrumented pass of the same K steps: every
                  kernel launch bracketed by an event pair on the solver's own stream
   cpu_baseline — the reference CPU path (oracle/_ref, unmodified AprilSAM built from source) or, if it
@@ -484,7 +488,7 @@ def short_line(out):
         for k in [k for k in list(cfg)[::-1] if "_ms_k_" in k][:len(cfg) - MAX_CONFIG_KEYS]:
             del cfg[k]
     # ---- roofline: the dominant kernel of `value`'s workload, then fractions of the lattices' kernels -------------------------------
-    for k, v in out["roofline"].items():
+    for k, v in out.get("roofline", {}).items():
         if scalar(v):
             roof[k] = sig(v)
     for tag, blk in (("l100k", l100), ("l1m", l1m)):
@@ -498,7 +502,8 @@ def short_line(out):
     line = {k: sig(out.get(k)) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
                                          "dtype", "data")}
     line["config"] = cfg
-    line["roofline"] = roof
+    if roof:                                # (a plain run has no instrumented pass)
+        line["roofline"] = roof
     if "cpu_baseline" in out:
         line["cpu_baseline"] = {k: sig(v) for k, v in out["cpu_baseline"].items() if scalar(v)}
     for k in ("factorise_ms", "value_api_call", "ms_per_api_call", "source_hash", "value_definition", "vs_baseline_definition", "extras"):
@@ -520,11 +525,25 @@ def write_extras(out):
     print("bench extras: " + json.dumps(out), file=sys.stderr, flush=True)
 
 
-def emit(out):
-    write_extras(out)
+def emit(out, full=True):
+    if full:
+        write_extras(out)
     s = json.dumps(short_line(out))
     assert len(s.encode()) < MAX_LINE_BYTES, f"bench line is {len(s.encode())} bytes"
     print(s, flush=True)
+
+
+MAX_DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: what the timed path hands its caller after its last step, as <d>/<name>.npy (float64) -- for comparing two builds
+    output for output (the inputs are the committed M3500 fixture, so they are the same in every run)"""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    assert sum(v.nbytes for v in arrays.values()) <= MAX_DUMP_BYTES
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), v)
 
 
 def aggregate_value(world, steps, max_dt):
@@ -532,37 +551,11 @@ def aggregate_value(world, steps, max_dt):
     return world * steps / max_dt
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-lattice", action="store_true")
-    ap.add_argument("--no-inc", action="store_true")
-    ap.add_argument("--lattice1m-k", type=int, default=1000, help="side of the config-5 lattice (0 = skip)")
-    ap.add_argument("--backend", default="nccl", help="nccl (= RCCL; the driver's multi-GPU runs) | gloo (functional test, host staging)")
-    ap.add_argument("--one-gpu", action="store_true", help="test mode: every rank uses cuda:0")
-    ap.add_argument("--cpu-lattice100k", action="store_true", help="(default since round 5; kept for old command lines)")
-    ap.add_argument("--no-cpu-lattice100k", action="store_true",
-                    help="do NOT time one april_graph_cholesky call of the reference on the 100k lattice on this host (about half a minute of "
-                         "CPU, single thread); the figure recorded under profiles/ is quoted instead")
-    a = ap.parse_args()
-
+def full_record(a, lib, arrays, out, rank, world, local, device, barrier, sync_all):
+    """--full: everything beyond the headline figure, added to `out`.  Every rank takes part (the API calls and config 5 are timed
+    between barriers)."""
     import torch
-    import __graft_entry__ as ge
-    rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1"))
-    local = 0 if a.one_gpu else int(os.environ.get("LOCAL_RANK", "0"))
-    if rank == 0:
-        ge.build()
-    torch.cuda.set_device(local)
-    device = torch.device("cuda", local)
-    barrier, sync_all = setup_dist(world, a.backend, device if a.backend == "nccl" else torch.device("cpu"))
     from aprilsam_amd import datasets, host
-    lib = host.SolverLib()
-    lib.dll.aprilsam_amd_set_device(local)
-    arrays = datasets.m3500_batch()
-
     # ---- parity gate on this very build: 10 iterations vs the reference golden -----------------------------
     G = np.load(os.path.join(ROOT, "tests", "golden", "m3500_batch.npz"))
     g = lib.new_graph(); g.build_from_arrays(*arrays); p = lib.new_param()
@@ -572,21 +565,14 @@ def main():
     p.destroy(); g.destroy()
     assert chi2_err < 1e-6, f"parity gate failed: chi2 relative error {chi2_err}"
 
-    # ---- timed region ------------------------------------------------------------------------------------------
+    # ---- instrumented pass: K steps of a second resident copy after the same warm-up, every kernel launch timed with HIP events on the
+    #      solver stream ------------------------------------------------------------------------------------------------------
     g = lib.new_graph(); g.build_from_arrays(*arrays); p = lib.new_param()
-    t0 = time.perf_counter()
     assert lib.dll.aprilsam_amd_resident_begin(g.ptr, p.ptr) == 0
-    first_call_ms = (time.perf_counter() - t0) * 1e3            # pack + ordering + symbolic + upload
     lib.dll.aprilsam_amd_resident_steps(g.ptr, p.ptr, a.warmup, 0)
     lib.dll.aprilsam_amd_resident_sync(g.ptr, p.ptr)
-    dt = timed_steps(lib, g, p, a.steps, sync_all, barrier)
-    ms_per_step = 1e3 * dt / a.steps
-    value = aggregate_value(world, a.steps, dt)
-
-    # ---- instrumented pass: same K steps, every kernel launch timed with HIP events on the solver stream ----
     lib.dll.aprilsam_amd_resident_steps(g.ptr, p.ptr, a.steps, 1)
     prof = kernel_profile(lib, p)
-    stats = p.stats()
     lib.dll.aprilsam_amd_resident_end(g.ptr, p.ptr)
     p.destroy(); g.destroy()
 
@@ -634,30 +620,20 @@ def main():
                 measured="HIP events around every launch, instrumented pass of the same K steps")
     factorise_ms = sum(k["ms_per_iter"] for k in prof if k["name"] in FACTOR_KERNELS)
 
-    out = {
-        "metric": "Gauss-Newton iterations/sec + factorise ms on M3500 (chi2 match <=1e-6)",
-        "value": value, "unit": "GN iterations/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+    out.update({
         "value_api_call": aggregate_value(world, a.steps, dt_api), "ms_per_api_call": 1e3 * dt_api / a.steps,
         "value_definition": "value = resident loop (inputs in HBM, bench contract); value_api_call = warm april_graph_cholesky calls through the C-ABI "
                             "(SURVEY 8(d)'s metric)",
-        "dtype": "f64", "data": "M3500 (reference data file, committed as fixture); synthetic only in `lattice100k`",
-        "config": {"workload": "M3500 batch april_graph_cholesky, 1 replica per GPU (3500 poses, 5454 factors, n=10500)",
-                   "parallelism": f"replicas x{world}" if world > 1 else "single GPU",
-                   "fronts": stats["n_fronts"], "levels": stats["n_levels"], "nnz_L": stats["nnz_L"],
-                   "sum_cj2": stats["flops_factor"], "leaf_nodes": 16},
         "factorise_ms": factorise_ms,
-        "first_call_ms_incl_symbolic": first_call_ms,
         "parity": {"chi2_max_relerr_10_iters": chi2_err, "max_abs_state_err": state_err, "bar": 1e-6},
         "roofline": roof,
         "kernels_ms_per_step": {k["name"]: round(k["ms_per_iter"], 5) for k in prof},
         "kernel_launches_per_step": {k["name"]: k["launches_per_iter"] for k in prof},
-        "source_hash": source_hash(),
         "multi_gpu": {"world": world, "backend": a.backend, "rank0_device": local,
                       "transport": ("host callbacks over gloo (test mode)" if a.backend != "nccl" else "RCCL") if world > 1 else "none (single rank)",
                       "rccl_version_torch": ".".join(str(v) for v in torch.cuda.nccl.version()) if world > 1 and a.backend == "nccl" else None,
                       "data_path_collectives": "none for `value` (independent replicas); lattice1m: ncclSend/ncclRecv of Schur slabs + ncclBroadcast of separator solutions inside the library"},
-    }
+    })
     if rank == 0 and world == 1 and not a.no_lattice:
         try:
             arr = lib.lattice_arrays(316)
@@ -779,7 +755,7 @@ def main():
         out["speedup_vs_cpu_baseline"] = out["value_api_call"] / out["cpu_baseline"]["value"]
         if "default" in out.get("api", {}):
             out["speedup_vs_cpu_baseline_cold_call"] = 1e3 / out["api"]["cold_ms_per_call"] / out["cpu_baseline"]["value"]
-        out["speedup_resident_vs_cpu_baseline"] = value / out["cpu_baseline"]["value"]
+        out["speedup_resident_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
         # BASELINE.md publishes no number for this metric; the round-5 review asked for the like-for-like ratio here: one warm
         # april_graph_cholesky call of this library against one of the unmodified reference on this host (1 thread)
         out["vs_baseline"] = out["speedup_vs_cpu_baseline"]
@@ -800,8 +776,78 @@ def main():
         except Exception as e:
             out["lattice1m"] = {"error": repr(e), "n_gpus": world}
         dog.cancel()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the states, l_points and deltas they left as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="also run everything beyond the headline figure (parity gate, roofline, API calls, "
+                                                        "CPU baseline, lattices, incremental demo, side file); the --no-* options below apply to it")
+    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-lattice", action="store_true")
+    ap.add_argument("--no-inc", action="store_true")
+    ap.add_argument("--lattice1m-k", type=int, default=1000, help="side of the config-5 lattice (0 = skip)")
+    ap.add_argument("--backend", default="nccl", help="nccl (= RCCL; the driver's multi-GPU runs) | gloo (functional test, host staging)")
+    ap.add_argument("--one-gpu", action="store_true", help="test mode: every rank uses cuda:0")
+    ap.add_argument("--cpu-lattice100k", action="store_true", help="(default since round 5; kept for old command lines)")
+    ap.add_argument("--no-cpu-lattice100k", action="store_true",
+                    help="do NOT time one april_graph_cholesky call of the reference on the 100k lattice on this host (about half a minute of "
+                         "CPU, single thread); the figure recorded under profiles/ is quoted instead")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+
+    import torch
+    import __graft_entry__ as ge
+    rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1"))
+    local = 0 if a.one_gpu else int(os.environ.get("LOCAL_RANK", "0"))
     if rank == 0:
-        emit(out)
+        ge.build()
+    torch.cuda.set_device(local)
+    device = torch.device("cuda", local)
+    barrier, sync_all = setup_dist(world, a.backend, device if a.backend == "nccl" else torch.device("cpu"))
+    from aprilsam_amd import datasets, host
+    lib = host.SolverLib()
+    lib.dll.aprilsam_amd_set_device(local)
+    arrays = datasets.m3500_batch()
+
+    # ---- timed region ------------------------------------------------------------------------------------------
+    g = lib.new_graph(); g.build_from_arrays(*arrays); p = lib.new_param()
+    t0 = time.perf_counter()
+    assert lib.dll.aprilsam_amd_resident_begin(g.ptr, p.ptr) == 0
+    first_call_ms = (time.perf_counter() - t0) * 1e3            # pack + ordering + symbolic + upload
+    lib.dll.aprilsam_amd_resident_steps(g.ptr, p.ptr, a.warmup, 0)
+    lib.dll.aprilsam_amd_resident_sync(g.ptr, p.ptr)
+    dt = timed_steps(lib, g, p, a.steps, sync_all, barrier)
+    ms_per_step = 1e3 * dt / a.steps
+    value = aggregate_value(world, a.steps, dt)
+
+    stats = p.stats()
+    # what the K steps hand the caller in the node objects: state, l_point (where the last step was linearised), delta_X (its dx)
+    assert lib.dll.aprilsam_amd_resident_end(g.ptr, p.ptr) == 0
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"states": g.states(), "l_points": g.l_points(), "deltas": g.deltas()})
+    p.destroy(); g.destroy()
+
+    out = {
+        "metric": "Gauss-Newton iterations/sec + factorise ms on M3500 (chi2 match <=1e-6)",
+        "value": value, "unit": "GN iterations/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f64", "data": "M3500 (reference data file, committed as fixture); synthetic only in `lattice100k`",
+        "config": {"workload": "M3500 batch april_graph_cholesky, 1 replica per GPU (3500 poses, 5454 factors, n=10500)",
+                   "parallelism": f"replicas x{world}" if world > 1 else "single GPU",
+                   "fronts": stats["n_fronts"], "levels": stats["n_levels"], "nnz_L": stats["nnz_L"],
+                   "sum_cj2": stats["flops_factor"], "leaf_nodes": 16},
+        "first_call_ms_incl_symbolic": first_call_ms,
+        "source_hash": source_hash(),
+    }
+    if a.full:
+        full_record(a, lib, arrays, out, rank, world, local, device, barrier, sync_all)
+    if rank == 0:
+        emit(out, full=a.full)
     if world > 1:
         import torch.distributed as dist
         try:

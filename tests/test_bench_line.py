@@ -4,10 +4,11 @@ import glob
 import json
 import os
 
+import numpy as np
 import pytest
 
 import bench
-from tests.support.bench_line import check_line
+from tests.support.bench_line import CONTRACT, check_line
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RECORDS = sorted(glob.glob(os.path.join(ROOT, "profiles", "r0[5-9]_bench.json")) + glob.glob(os.path.join(ROOT, "profiles", "*_bench_extras*.json")))
@@ -33,3 +34,26 @@ def test_short_line_survives_failed_extras_and_long_error_strings():
     full["m3500_incremental"] = {"error": "z" * 100}
     out = check_line(json.dumps(bench.short_line(full)), cpu_baseline="cpu_baseline" in full)
     assert out["config"]["lattice1m_error"].startswith("watchdog") and out["config"]["lattice1m_n_gpus"] == 8
+
+
+def test_line_of_a_plain_run_has_the_contract_fields_and_no_full_blocks():
+    """a run without --full records only the timed steps and the plan's shape: no roofline, no CPU baseline, no side file"""
+    full = json.load(open(RECORDS[0]))
+    plain = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "dtype",
+                                  "data", "config", "source_hash")}
+    plain["vs_baseline"] = None
+    s = json.dumps(bench.short_line(plain))
+    out = json.loads(s)
+    assert "\n" not in s and len(s.encode()) < bench.MAX_LINE_BYTES
+    for k in CONTRACT:
+        assert k in out, k
+    assert out["ms_per_step"] == bench.sig(full["ms_per_step"]) and out["metric"] == full["metric"]
+    assert not any(k in out for k in ("roofline", "cpu_baseline", "factorise_ms", "value_api_call", "extras"))
+
+
+def test_dump_outputs_writes_float64_arrays(tmp_path):
+    a = np.arange(12, dtype=np.float32).reshape(4, 3)
+    bench.dump_outputs(str(tmp_path / "d"), {"states": a, "deltas": -a})
+    for name, want in (("states", a), ("deltas", -a)):
+        got = np.load(tmp_path / "d" / f"{name}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, want)

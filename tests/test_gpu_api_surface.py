@@ -494,7 +494,7 @@ def test_bench_two_ranks_on_one_gpu_prints_one_valid_line(built):
     import json
     port = 29500 + os.getpid() % 400
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--one-gpu",
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--one-gpu", "--full",
            "--backend", "gloo", "--lattice1m-k", "316", "--no-cpu-baseline", "--no-inc"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -514,3 +514,23 @@ def test_bench_two_ranks_on_one_gpu_prints_one_valid_line(built):
     assert l1["n_gpus"] == 2 and "shards x2" in l1["parallelism"]
     assert max(l1["chi2_relerr_vs_reference"]) < 1e-9
     assert ex["multi_gpu"]["world"] == 2 and ex["multi_gpu"]["transport"].startswith("host callbacks")
+
+
+def test_bench_plain_run_prints_the_headline_and_dumps_what_the_steps_left(built, tmp_path):
+    """bench.py without --full: the contract fields of the timed steps only, and --dump-outputs writes the node objects they left --
+    after 6 warm-up + 4 timed steps, the states of the reference's 10 batch iterations (golden)"""
+    import json
+    from tests.conftest import golden
+    d = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "6", "--dump-outputs", str(d)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads(r.stdout.splitlines()[-1])
+    assert out["steps"] == 4 and out["warmup"] == 6 and out["n_gpus"] == 1
+    assert out["unit"] == "GN iterations/s" and out["higher_is_better"] is True and out["dtype"] == "f64"
+    assert out["ms_per_step"] > 0 and out["value"] == pytest.approx(1e3 / out["ms_per_step"], rel=1e-4)
+    assert not any(k in out for k in ("roofline", "cpu_baseline", "value_api_call", "extras"))
+    arrs = {k: np.load(d / f"{k}.npy") for k in ("states", "l_points", "deltas")}
+    for a in arrs.values():
+        assert a.dtype == np.float64 and a.shape == (3500, 3) and np.all(np.isfinite(a))
+    assert np.max(np.abs(arrs["states"] - golden("m3500_batch.npz")["final_states"])) < 1e-6

@@ -83,9 +83,14 @@ def test_interchange_with_the_live_reference(lib, reflib, tmp_path):
     ours.destroy(); back.destroy()
 
 
-@pytest.mark.skipif(not os.path.exists(REFDATA), reason="reference tree not mounted")
-def test_reader_loads_the_reference_data_file(lib):
-    g = lib.load_graph(REFDATA)
+def test_reader_loads_the_reference_data_file(lib, tmp_path):
+    """the reference's data/M3500.graph, byte for byte: rebuilt from the committed fixture by the writer and pinned by its sha256"""
+    g = _m3500_loaded_graph(lib)
+    path = str(tmp_path / "M3500.graph")
+    assert g.save(path)
+    g.destroy()
+    assert hashlib.sha256(open(path, "rb").read()).hexdigest() == REF_M3500_GRAPH_SHA256
+    g = lib.load_graph(path)
     st, fa, fb, z, W = datasets.m3500_arrays()
     a = g.arrays()
     assert np.array_equal(a[0], st) and np.array_equal(a[1], fa) and np.array_equal(a[2], fb) and np.array_equal(a[3], z) and np.array_equal(a[4], W)

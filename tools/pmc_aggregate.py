@@ -48,7 +48,7 @@ for c in ("FETCH_SIZE", "WRITE_SIZE"):
     if r and c in r:
         hbm[c] = {k: {"dispatches": v["dispatches"], "total_kb": v["total"], "kb_per_dispatch": v["per_dispatch"]} for k, v in r[c].items()}
 if hbm:
-    json.dump({"source_hash": SRC_HASH, "command": "APRILSAM_AMD_USE_GRAPH=0 rocprofv3 --pmc <COUNTER> --output-format csv -- python bench.py --steps 10 --warmup 2 --no-lattice "
+    json.dump({"source_hash": SRC_HASH, "command": "APRILSAM_AMD_USE_GRAPH=0 rocprofv3 --pmc <COUNTER> --output-format csv -- python bench.py --steps 10 --warmup 2 --full --no-lattice "
                           "--no-inc --no-cpu-baseline (one pass per counter, hipGraph replay off)",
                "unit": "KB as reported by rocprofv3; MI355X_MICROARCH.md: FETCH_SIZE under-reports wide coalesced reads by 2x on gfx950 - "
                        "values are RAW, bench.py applies the x2 to the read side", "counters": hbm},

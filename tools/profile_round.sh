@@ -9,8 +9,8 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp
-BENCH="python $ROOT/bench.py --steps 200 --warmup 10 --no-lattice --no-inc --no-cpu-baseline"
-SHORT="python $ROOT/bench.py --steps 10 --warmup 2 --no-lattice --no-inc --no-cpu-baseline"
+BENCH="python $ROOT/bench.py --steps 200 --warmup 10 --full --no-lattice --no-inc --no-cpu-baseline"
+SHORT="python $ROOT/bench.py --steps 10 --warmup 2 --full --no-lattice --no-inc --no-cpu-baseline"
 LAT="python $ROOT/tools/lattice_big.py 316 2"
 rocprofv3 -L > $OUT/counters_available.txt 2>&1
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $BENCH > $OUT/stats.log 2>&1
