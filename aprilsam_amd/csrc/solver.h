@@ -92,5 +92,7 @@ void unbind_param(const april_graph_cholesky_param_t *param);
 void warm_up() noexcept;          // once per process, from april_graph_cholesky_param_init: see solver.hip.cpp
 int api_set_option(const char *name, double v);
 int api_get_option(const char *name, double *v);
+int marginals(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *qa, const int *qb, double *cov, bool joint);     // solver_marginals.inc.h
+long long selinv_runs(const april_graph_cholesky_param_t *param);
 
 }  // namespace asam

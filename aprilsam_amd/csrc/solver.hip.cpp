@@ -27,6 +27,7 @@
 #include "../../include/aprilsam_amd.h"
 #include "errors.h"
 #include "kernels.hip.h"
+#include "selinv.hip.h"
 #include "plan.h"
 #include "refmodel.h"
 #include "solver.h"
@@ -238,6 +239,7 @@ struct PatchList {
 #include "solver_calls.inc.h"
 #include "solver_resident.inc.h"
 #include "solver_shard.inc.h"
+#include "solver_marginals.inc.h"
 
 // ------------------------------------------------------------------------------------------------------
 // Runtime warm-up, once per process, from april_graph_cholesky_param_init (the API's set-up call; aprilsam.c:45-64 has nothing to set up).
@@ -442,3 +444,13 @@ int api_get_option(const char *name, double *v) {
 }
 
 }  // namespace asam
+
+// The marginals entry points are defined here, in the HIP translation unit, and not in capi.cpp: the sanitizer build of the host
+// sources (tools/sanitize_host.sh) links capi.cpp without this unit.
+extern "C" int aprilsam_amd_marginals(april_graph_t *graph, april_graph_cholesky_param_t *param, int n, const int *nodes, double *cov) {
+    return asam::marginals(graph, param, n, nodes, nullptr, cov, false);
+}
+extern "C" int aprilsam_amd_marginals_joint(april_graph_t *graph, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, double *cov) {
+    return asam::marginals(graph, param, n, a, b, cov, true);
+}
+extern "C" long long aprilsam_amd_debug_selinv_runs(const april_graph_cholesky_param_t *param) { return asam::selinv_runs(param); }

@@ -146,6 +146,7 @@ static void batch_impl(april_graph_t *g, april_graph_cholesky_param_t *param) {
         param->nreordering = N;
         param->factor_num = gp.Fg;      // (graph factors; F counts packed entries, pack_factors)
         c.have_fact = true; c.batch_nodes = N; c.batch_factors = F; c.model.valid = model_ready;
+        record_factor(c, hybrid ? FACT_EXTENDED : FACT_PLAN, gp);
         if (!hybrid && !(reused && c.inc.ready && c.inc.pristine)) inc_prepare(c);      // (an extended plan keeps its base + tail bookkeeping; a warm call on an untouched plan its tables: rebuilding them was 40 % of the call's time behind the stream sync)
         c.inc_F = F; c.inc_N = N;
         record_unary_points(gp, 0, F, gp.h_state.p);         // the linearisation point of this call
@@ -365,6 +366,7 @@ static void inc_impl(april_graph_t *g, april_graph_cholesky_param_t *param) {
         c.inc.upd_ok = false;                        // (... nor to update)
         return;
     }
+    record_factor(c, reused ? FACT_EXTENDED : FACT_PLAN, gp);
     // bookkeeping exactly as the reference: which poses solve_node visits / updates, start_over (refmodel.cpp)
     april_graph_node_t **ns = (april_graph_node_t **)g->nodes->data;
     for (int i = (partial && reused) ? std::min(N_before, N) : 0; i < N; i++) ns[i]->UID = i;      // aprilsam.c:474 (the new nodes; every node where the walk is full anyway)

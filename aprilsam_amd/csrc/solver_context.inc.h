@@ -60,6 +60,9 @@ struct IncState {
     std::vector<char> st_mid, st_mode; std::vector<int> st_owner, st_mask, st_wout, st_slot; std::vector<UpdRec> st_upd, st_rec;
 };
 
+// marginal covariances (solver_marginals.inc.h): per level, the ranges of its work entries in the selected inversion's table
+struct SelLevel { int gat_off = 0, n_gat = 0, diag_off = 0, n_diag = 0, tri_off = 0, n_tri = 0, x_off = 0, n_x = 0, sus_off = 0, n_sus = 0, sss_off = 0, n_sss = 0; };
+
 struct Context {
     Plan plan;
     bool have_plan = false;
@@ -164,7 +167,19 @@ struct Context {
         retired.push_back(r); g = nullptr;
     }
     double lambda_val = -1; int lambda_N = -1;     // what d_lambda currently holds (uniform batch value), -1: unknown
+    // marginal covariances (solver_marginals.inc.h): what the last successful solver call left in d_pool (FACT_*), at which value of
+    // epoch_steps; the Sigma pool (front pool layout) and the step it was computed for; launch tables built per plan
+    int fact_kind = 0; long long fact_epoch = -1; bool fact_asym = false;
+    DBuf<double> d_sigma, d_sel_scr; DBuf<SelFront> d_sel_fd; DBuf<int> d_sel_i32, d_sel_q; DBuf<int4> d_sel_ent; HBuf<double> h_cov;
+    long long fact_serial = 0;                     // factorisations recorded so far (only grows)
+    std::vector<SelLevel> sel_levels; int sel_tab_kind = 0, sel_N = 0;
+    long long sel_serial = -1, sel_tab_serial = -1, sel_runs = 0, sel_pool = 1; double sel_flops = 0;
+    void release_sel() {
+        d_sigma.release(); d_sel_scr.release(); d_sel_fd.release(); d_sel_i32.release(); d_sel_q.release(); d_sel_ent.release(); h_cov.release();
+        sel_levels.clear(); sel_serial = -1; sel_tab_serial = -1;
+    }
     void release() {
+        release_sel();
         d_i32.release(); d_fd.release(); d_dest.release(); d_child.release(); d_lambda.release(); d_tab.release(); d_swap.release(); d_pos.release();
         d_pool.release(); d_H.release(); d_x.release(); d_diag.release(); d_bad.release(); h_bad.release(); patches.release();
         h_done.release(); h_kstamp.release(); d_prof.release(); d_upd.release(); d_wbuf.release(); d_flags.release(); d_flevel.release(); d_epoch.release(); d_marks.release(); d_perm.release(); d_solve_tab.release(); d_dinv.release(); d_bsb_far.release(); d_bsb_flags.release(); d_guard.release(); d_guard_cnt.release(); n_guard = 0;
@@ -260,6 +275,9 @@ template <class Fn> static int guarded_rc(const april_graph_cholesky_param_t *pa
 static const int FIRST_EPOCH = 1 << 20;
 struct Context;
 static void rewind_epoch(Context &c, hipStream_t s, long long phases);
+// marginal covariances (solver_marginals.inc.h): what a successful solver call left in the front pool
+enum { FACT_NONE = 0, FACT_PLAN = 1, FACT_EXTENDED = 2 };      // no factor / the factor of c.plan / tail fronts appended by the incremental path
+static void record_factor(Context &c, int kind, const GraphPack &gp);
 // slack reserved at plan upload so that the incremental path can append without reallocating device buffers
 constexpr int INC_NODES = 4096, INC_FACT = 16384, INC_I32 = 4 << 20, INC_DEST = 1 << 20, INC_CHILD = 1 << 18, INC_TAB = 1 << 20;
 #define TAIL_POSES (g_opt.tail_poses)         // own poses per tail front of the incremental path (inc_fast_step), option tail_poses (>= 8)
@@ -445,6 +463,7 @@ static void upload_plan(Context &c, hipStream_t s, const ShardLayout *lay = null
     const double u0 = uprof ? now_ms() : 0;
     c.retire(c.gexec); c.retire(c.gexec_api); c.api_key_runs = 0;
     c.lambda_N = -1;
+    c.release_sel();                          // (Sigma and its tables describe the plan being replaced)
     // ---- descriptors + index arrays ----------------------------------------------------------------------------
     std::vector<FrontDesc> &fd = c.inc.fd; fd.assign(P.nF, FrontDesc());
     std::vector<ChildRec> ch(std::max<size_t>(1, P.ch_idx.size()));
@@ -675,6 +694,7 @@ static DevPlan persist_plan(const Context &c) { DevPlan d = c.dp; d.flevel = c.d
 static void rewind_epoch(Context &c, hipStream_t s, long long phases) {
     c.epoch_steps += phases;
     if (c.epoch_steps < (1ll << 30) || !c.d_epoch.p) return;
+    c.fact_kind = FACT_NONE;                                // (marginals: the counter the factor was stamped with starts over)
     HIPCHECK(hipStreamSynchronize(s));                      // nothing in flight reads a flag
     HIPCHECK(hipMemsetAsync(c.d_flags.p, 0, c.d_flags.cap * 4, s));
     HIPCHECK(hipMemsetAsync(c.d_marks.p, 0, c.d_marks.cap * 4, s));

@@ -125,6 +125,7 @@ static int resident_end_impl(april_graph_t *g, april_graph_cholesky_param_t *par
     memcpy(param->ordering, c.plan.perm.data(), sizeof(int) * (size_t)N);
     param->nreordering = N; param->factor_num = gp.Fg;
     c.have_fact = true; c.batch_nodes = N; c.batch_factors = F; c.model.valid = false;
+    record_factor(c, c.inc.t_first.empty() ? FACT_PLAN : FACT_EXTENDED, gp);
     inc_prepare(c); c.inc_F = F; c.inc_N = N;
     record_unary_points(gp, 0, F, gp.h_lp.p);                // (unary factors were last linearised at the last step's l_points)
     return 0;

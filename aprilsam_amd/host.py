@@ -34,6 +34,14 @@ def _np_i(a):
     return a.ctypes.data_as(_ip)
 
 
+class MarginalsError(RuntimeError):
+    """a negative return of aprilsam_amd_marginals / _joint: .code is the return value"""
+
+    def __init__(self, code, msg=None):
+        super().__init__(f"marginals failed: {code} {msg or ''}".strip())
+        self.code = code
+
+
 class SolverLib:
     """A loaded shared library exporting the reference API names."""
 
@@ -95,6 +103,11 @@ class SolverLib:
             d.aprilsam_amd_plan_query.restype = C.c_longlong
             d.aprilsam_amd_plan_query.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.POINTER(C.c_longlong))]
             d.aprilsam_amd_free.argtypes = [C.c_void_p]
+            if hasattr(d, "aprilsam_amd_marginals"):          # (defined in the HIP translation unit: absent from the sanitizer build of the host sources)
+                d.aprilsam_amd_marginals.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.c_int, _ip, _dp]
+                d.aprilsam_amd_marginals_joint.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.c_int, _ip, _ip, _dp]
+                d.aprilsam_amd_debug_selinv_runs.argtypes = [C.POINTER(abi.CholeskyParam)]
+                d.aprilsam_amd_debug_selinv_runs.restype = C.c_longlong
             d.aprilsam_amd_graph_save_ex.argtypes = [C.POINTER(abi.Graph), C.c_char_p, C.c_ulonglong]
             d.aprilsam_amd_graph_load.restype = C.POINTER(abi.Graph)
             d.aprilsam_amd_graph_load.argtypes = [C.c_char_p]
@@ -365,6 +378,33 @@ class Graph:
     def cholesky_inc_solver(self, param):
         """april_graph_cholesky_inc_solver (aprilsam.c:578-597); neither library reads the idxs argument"""
         self.lib.dll.april_graph_cholesky_inc_solver(self.ptr, param.ptr, None)
+
+    def marginals(self, param, nodes=None):
+        """[n, 3, 3] marginal covariances (x, y, theta) of `nodes` (all nodes: None) from the factor of the last solver call on
+        `param` (include/aprilsam_amd.h: aprilsam_amd_marginals).  Raises MarginalsError(rc) on a negative return."""
+        if nodes is None:
+            n = self.n_nodes
+            out = np.empty((n, 3, 3))
+            rc = self.lib.dll.aprilsam_amd_marginals(self.ptr, param.ptr, 0, None, _np_d(out))
+        else:
+            idx = np.ascontiguousarray(nodes, dtype=np.int32).ravel()
+            out = np.empty((len(idx), 3, 3))
+            rc = self.lib.dll.aprilsam_amd_marginals(self.ptr, param.ptr, len(idx), _np_i(idx), _np_d(out))
+        if rc < 0:
+            raise MarginalsError(rc, self.lib.last_error())
+        return out
+
+    def marginals_joint(self, param, a, b):
+        """[n, 6, 6] joint covariances of the pairs (a[i], b[i]), a's unknowns first; pairs off the pattern of the factor come back
+        NaN (include/aprilsam_amd.h: aprilsam_amd_marginals_joint).  Raises MarginalsError(rc) on a negative return."""
+        a = np.ascontiguousarray(a, dtype=np.int32).ravel(); b = np.ascontiguousarray(b, dtype=np.int32).ravel()
+        if a.shape != b.shape:
+            raise ValueError("a and b must have the same length")
+        out = np.empty((len(a), 6, 6))
+        rc = self.lib.dll.aprilsam_amd_marginals_joint(self.ptr, param.ptr, len(a), _np_i(a), _np_i(b), _np_d(out))
+        if rc < 0:
+            raise MarginalsError(rc, self.lib.last_error())
+        return out
 
     def batch_resident(self, param, iters):
         chi2 = np.zeros(iters + 1); ms = np.zeros(iters)

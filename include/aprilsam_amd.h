@@ -403,6 +403,33 @@ int aprilsam_amd_kernel_profile(const april_graph_cholesky_param_t *param, doubl
  * launch is booked on its first level.  Returns the number of levels (fills at most cap_levels). */
 int aprilsam_amd_level_profile(const april_graph_cholesky_param_t *param, double *out6, int cap_levels);
 
+/* ---- marginal covariances from the retained factor ---------------------------------------------------
+ * Marginal covariances of the system the LAST successful solver call on `param` factorised: the inverse of
+ * (sum J^T W J + diag(lambda)) at that step's linearisation points (the nodes' l_point after the call), read from the retained
+ * factor by selected inversion on the GPU.  Available after april_graph_cholesky, aprilsam_amd_batch_resident,
+ * aprilsam_amd_resident_end and april_graph_cholesky_inc (whichever way the step went: fast path with tail fronts, low-rank updates,
+ * re-plan, batch fall-back).  lambda sits where the step put it: param->tikhanov on every pose after a batch call (an extended plan
+ * included); after an incremental step on the positions that carry it in the factorised system (DevPlan::lambda): the poses present at
+ * the last batch step.  Sigma is recomputed in full after every solver call.
+ * nodes == NULL: all nodes (n ignored; the graph must hold exactly the factorised nodes).  cov: 9 doubles per node, row-major
+ * (x, y, theta: the unknowns of delta_X).  Returns 0, or < 0:
+ *   -1   no retained factor (never solved, the last solver call failed or was not positive definite, a resident run in progress)
+ *   -12  sharded param; the factorised graph holds a factor with an asymmetric information matrix (the reference-order path
+ *        factorises one triangle of an unsymmetric system: no covariance is defined)
+ *   -13  a node id out of range of the factorised system (nodes added since the last solve), or a bad argument
+ *   -14  no HIP device
+ * It sets aprilsam_amd_last_error like every entry point, but -- unlike the solver entry points -- a failed marginals call leaves
+ * the param's plan and factor in place: it only reads them, and the next solver call is unaffected.  Sigma is computed once per
+ * factorisation and kept beside the factor (a second pool of stats.bytes_fronts bytes, allocated on the first call, freed with the
+ * plan; option mem_cap_mb applies): a second call with no solver call in between only extracts.  Two calls give the same bits. */
+int aprilsam_amd_marginals(april_graph_t *graph, april_graph_cholesky_param_t *param, int n, const int *nodes, double *cov);
+/* Joint covariance [[S_aa S_ab]; [S_ba S_bb]] (36 doubles per pair, row-major, a's unknowns first) for pairs on the factor's
+ * pattern -- every pair joined by a factor is.  Returns the number of pairs NOT on the pattern (their 36 values are NaN), or the
+ * codes above. */
+int aprilsam_amd_marginals_joint(april_graph_t *graph, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, double *cov);
+/* debug: number of selected inversions run on this param so far (-1: no context) */
+long long aprilsam_amd_debug_selinv_runs(const april_graph_cholesky_param_t *param);
+
 /* ---- multi-GPU: nested-dissection subtree sharding, one process per GPU -------
  * The reference has no counterpart (it is sequential); a C host drives a sharded solve through the same graph / param
  * objects it hands to april_graph_cholesky (aprilsam.h:268-281):
