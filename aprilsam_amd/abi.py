@@ -34,6 +34,26 @@ class Factor(C.Structure):
                 ("destroy", C.c_void_p), ("u", FactorCommon), ("stype", C.c_void_p)]
 
 
+class FactorMax(C.Structure):
+    """u.max of a max-mixture factor (aprilsam.h:134-138; include/aprilsam_amd.h: APRILSAM_AMD_FACTOR_MAX_TYPE): it aliases u.common"""
+    _fields_ = [("factors", C.POINTER(C.POINTER(Factor))), ("logw", C.POINTER(C.c_double)), ("nfactors", C.c_int)]
+
+
+def max_view(factor):
+    """the u.max view of a Factor (a ctypes structure or a pointer to one)"""
+    f = factor.contents if hasattr(factor, "contents") else factor
+    return FactorMax.from_address(C.addressof(f) + Factor.u.offset)
+
+
+FACTOR_MAX_TYPE = 3
+_DESTROY = C.CFUNCTYPE(None, C.c_void_p)
+
+
+def destroy_factor(fptr):
+    """call a factor's own destroy() (a factor that never went into a graph)"""
+    _DESTROY(fptr.contents.destroy)(C.cast(fptr, C.c_void_p))
+
+
 class Node(C.Structure):
     _fields_ = [("UID", C.c_int), ("type", C.c_int), ("length", C.c_int),
                 ("state", C.POINTER(C.c_double)), ("init", C.POINTER(C.c_double)),

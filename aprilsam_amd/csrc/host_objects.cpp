@@ -6,8 +6,10 @@
 // because reference-compiled host code calls them directly (examples/aprilsam_demo.c:183 nb->relinearize,
 // :166 exist_factor->copy, april_graph.c:335-346 ->destroy).  The vtable entries are a courtesy to such
 // callers; the solver entry points never call them — factors of type 1/2 are evaluated by the HIP
-// kernels (csrc/kernels.hip.h).
+// kernels (csrc/kernels.hip.h).  Max-mixture factors (type 3) are built here too: their selection rule
+// (max_select) is the one the incremental path applies on the host and k_select_mixture restates on the device.
 #include <cmath>
+#include <cstdio>
 #include <string>
 #include <utility>
 #include <vector>
@@ -16,6 +18,7 @@
 
 #include "../../include/aprilsam_amd.h"
 #include "solver.h"
+#include "errors.h"
 
 namespace {
 
@@ -163,9 +166,125 @@ april_graph_node_t *node_copy(april_graph_node_t *n) {
     return c;
 }
 
+// ---- max-mixture factor -------------------------------------------------------------------
+// u.max { factors, logw, nfactors } as the reference's union lays it out; the components are library xyt factors on the same (a, b)
+april_graph_factor_eval_t *max_eval_at(april_graph_factor_t *f, april_graph_t *g, april_graph_factor_eval_t *e, bool at_state) {
+    april_graph_node_t **ns = (april_graph_node_t **)g->nodes->data;
+    const double *pa = at_state ? ns[f->nodes[0]]->state : ns[f->nodes[0]]->l_point;
+    const double *pb = at_state ? ns[f->nodes[1]]->state : ns[f->nodes[1]]->l_point;
+    april_graph_factor_t *c = f->u.max.factors[asam::max_select(f, pa, pb)];
+    return xyt_eval_at(c, g, e, at_state);
+}
+april_graph_factor_eval_t *max_eval(april_graph_factor_t *f, april_graph_t *g, april_graph_factor_eval_t *e) { return max_eval_at(f, g, e, false); }
+april_graph_factor_eval_t *max_state_eval(april_graph_factor_t *f, april_graph_t *g, april_graph_factor_eval_t *e) { return max_eval_at(f, g, e, true); }
+void max_destroy(april_graph_factor_t *f) {
+    for (int i = 0; i < f->u.max.nfactors; i++) f->u.max.factors[i]->destroy(f->u.max.factors[i]);
+    free(f->u.max.factors); free(f->u.max.logw); free(f->nodes);
+    attr_free(f->attr);
+    free(f);
+}
+april_graph_factor_t *max_make(april_graph_factor_t **components, const double *logw, int n) {
+    april_graph_factor_t *f = (april_graph_factor_t *)calloc(1, sizeof(april_graph_factor_t));
+    f->type = APRILSAM_AMD_FACTOR_MAX_TYPE;
+    f->nnodes = 2;
+    f->nodes = (int *)calloc(2, sizeof(int));
+    f->nodes[0] = components[0]->nodes[0]; f->nodes[1] = components[0]->nodes[1];
+    f->length = 3;
+    f->u.max.factors = (april_graph_factor_t **)malloc(sizeof(april_graph_factor_t *) * (size_t)n);
+    f->u.max.logw = (double *)malloc(sizeof(double) * (size_t)n);
+    memcpy(f->u.max.factors, components, sizeof(april_graph_factor_t *) * (size_t)n);
+    memcpy(f->u.max.logw, logw, sizeof(double) * (size_t)n);
+    f->u.max.nfactors = n;
+    return f;
+}
+april_graph_factor_t *max_copy(april_graph_factor_t *f) {
+    const int n = f->u.max.nfactors;
+    std::vector<april_graph_factor_t *> cs((size_t)n);
+    for (int i = 0; i < n; i++) cs[i] = f->u.max.factors[i]->copy(f->u.max.factors[i]);
+    april_graph_factor_t *c = max_make(cs.data(), f->u.max.logw, n);
+    c->copy = f->copy; c->eval = f->eval; c->state_eval = f->state_eval; c->destroy = f->destroy;
+    c->attr = attr_clone(f->attr);
+    return c;
+}
+
 }  // namespace
 
+namespace asam {
+
+bool is_native_max(const april_graph_factor_t *f) { return f->type == APRILSAM_AMD_FACTOR_MAX_TYPE && f->eval == max_eval; }
+
+double max_det3(const double *w) {
+    return w[0] * (w[4] * w[8] - w[5] * w[7]) - w[1] * (w[3] * w[8] - w[5] * w[6]) + w[2] * (w[3] * w[7] - w[4] * w[6]);
+}
+// c_i = -2 logw_i - ln det W_i: the part of a component's score that does not depend on the point
+double max_const(const april_graph_factor_t *f, int i) {
+    return -2.0 * f->u.max.logw[i] - log(max_det3(f->u.max.factors[i]->u.common.W->data));
+}
+
+bool max_check(const april_graph_factor_t *f, char *why, int cap) {
+    const int n = f->u.max.nfactors;
+    if (n < 1 || n > MAX_MIX_K || !f->u.max.factors || !f->u.max.logw) { snprintf(why, cap, "%d components (1 to %d are supported)", n, MAX_MIX_K); return false; }
+    for (int i = 0; i < n; i++) {
+        const april_graph_factor_t *c = f->u.max.factors[i];
+        if (!c || c->type != APRIL_GRAPH_FACTOR_XYT_TYPE || c->nnodes != 2 || c->eval != xyt_eval || !c->u.common.z || !c->u.common.W) {
+            snprintf(why, cap, "component %d is not an xyt factor of this library (april_graph_factor_xyt_create)", i); return false;
+        }
+        if (c->nodes[0] != f->nodes[0] || c->nodes[1] != f->nodes[1]) {
+            snprintf(why, cap, "component %d connects (%d, %d), the factor (%d, %d)", i, c->nodes[0], c->nodes[1], f->nodes[0], f->nodes[1]); return false;
+        }
+        const double *w = c->u.common.W->data;
+        if (w[1] != w[3] || w[2] != w[6] || w[5] != w[7]) { snprintf(why, cap, "component %d: W is not symmetric", i); return false; }
+        if (!(max_det3(w) > 0)) { snprintf(why, cap, "component %d: det W = %g is not positive", i, max_det3(w)); return false; }
+        if (!std::isfinite(f->u.max.logw[i])) { snprintf(why, cap, "component %d: logw = %g is not finite", i, f->u.max.logw[i]); return false; }
+    }
+    return true;
+}
+
+// the selection rule of DESIGN.md section 12 at poses pa, pb: the score r^T W r (eval_finish's association) + c_i, lowest index on a tie or NaN
+int max_select(const april_graph_factor_t *f, const double *pa, const double *pb) {
+    const double ca = cos(pa[2]), sa = sin(pa[2]);
+    const double dx = pb[0] - pa[0], dy = pb[1] - pa[1];
+    const double zh0 = ca * dx + sa * dy, zh1 = -sa * dx + ca * dy, zh2 = pb[2] - pa[2];
+    int best = 0; double sbest = 0;
+    for (int i = 0; i < f->u.max.nfactors; i++) {
+        const april_graph_factor_t *c = f->u.max.factors[i];
+        const double *z = c->u.common.z, *w = c->u.common.W->data;
+        const double r[3] = { z[0] - zh0, z[1] - zh1, mod2pi_h(z[2] - zh2) };
+        const double X0 = w[0] * r[0] + w[1] * r[1] + w[2] * r[2];
+        const double X1 = w[3] * r[0] + w[4] * r[1] + w[5] * r[2];
+        const double X2 = w[6] * r[0] + w[7] * r[1] + w[8] * r[2];
+        const double s = (r[0] * X0 + r[1] * X1 + r[2] * X2) + max_const(f, i);
+        if (i == 0) sbest = s;
+        else if (s < sbest) { best = i; sbest = s; }
+    }
+    return best;
+}
+
+}  // namespace asam
+
 extern "C" {
+
+april_graph_factor_t *aprilsam_amd_factor_max_create(april_graph_factor_t **components, const double *logw, int n) {
+    if (!components || !logw || n < 1 || n > asam::MAX_MIX_K) {
+        asam::set_last_error(asam::ERR_UNSUPPORTED, "aprilsam_amd_factor_max_create: " + std::to_string(n) + " components (1 to " + std::to_string(asam::MAX_MIX_K) +
+                             " are supported) or a null argument");
+        return nullptr;
+    }
+    for (int i = 0; i < n; i++)
+        if (!components[i] || components[i]->nnodes != 2 || !components[i]->nodes) {
+            asam::set_last_error(asam::ERR_UNSUPPORTED, "aprilsam_amd_factor_max_create: component " + std::to_string(i) + " is not a binary factor");
+            return nullptr;
+        }
+    april_graph_factor_t *f = max_make(components, logw, n);
+    char why[256];
+    if (!asam::max_check(f, why, sizeof why)) {     // (the caller keeps its components)
+        asam::set_last_error(asam::ERR_UNSUPPORTED, std::string("aprilsam_amd_factor_max_create: ") + why);
+        free(f->u.max.factors); free(f->u.max.logw); free(f->nodes); free(f);
+        return nullptr;
+    }
+    f->copy = max_copy; f->eval = max_eval; f->state_eval = max_state_eval; f->destroy = max_destroy;
+    return f;
+}
 
 april_graph_t *april_graph_create(void) {
     april_graph_t *g = (april_graph_t *)calloc(1, sizeof(april_graph_t));

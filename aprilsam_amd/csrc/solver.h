@@ -94,5 +94,12 @@ int api_set_option(const char *name, double v);
 int api_get_option(const char *name, double *v);
 int marginals(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *qa, const int *qb, double *cov, bool joint);     // solver_marginals.inc.h
 long long selinv_runs(const april_graph_cholesky_param_t *param);
+int max_selected(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *factors, int *out);   // solver_pack.inc.h
+// max-mixture factors (host_objects.cpp)
+constexpr int MAX_MIX_K = 8;
+bool is_native_max(const april_graph_factor_t *f);                 // type 3 with this library's eval
+bool max_check(const april_graph_factor_t *f, char *why, int cap);  // component count, types, endpoints, symmetric W with det > 0, finite logw
+double max_const(const april_graph_factor_t *f, int i);           // -2 logw_i - ln det W_i
+int max_select(const april_graph_factor_t *f, const double *pa, const double *pb);
 
 }  // namespace asam

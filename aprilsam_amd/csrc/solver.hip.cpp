@@ -27,6 +27,7 @@
 #include "../../include/aprilsam_amd.h"
 #include "errors.h"
 #include "kernels.hip.h"
+#include "maxmix.hip.h"
 #include "selinv.hip.h"
 #include "plan.h"
 #include "refmodel.h"
@@ -452,5 +453,8 @@ extern "C" int aprilsam_amd_marginals(april_graph_t *graph, april_graph_cholesky
 }
 extern "C" int aprilsam_amd_marginals_joint(april_graph_t *graph, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, double *cov) {
     return asam::marginals(graph, param, n, a, b, cov, true);
+}
+extern "C" int aprilsam_amd_max_selected(april_graph_t *graph, april_graph_cholesky_param_t *param, int n, const int *factors, int *out) {
+    return asam::max_selected(graph, param, n, factors, out);
 }
 extern "C" long long aprilsam_amd_debug_selinv_runs(const april_graph_cholesky_param_t *param) { return asam::selinv_runs(param); }

@@ -63,6 +63,7 @@ static void batch_impl(april_graph_t *g, april_graph_cholesky_param_t *param) {
             // z / W of already-packed factors edited in place by the caller (pack_factors recorded the range) only reach the
             // device through upload_factors: the patch list of inc_fast_step carries the NEW factors alone
             if (F > gp.F_cap || gp.dirty_hi > gp.dirty_lo) upload_factors(gp);
+            upload_mixture(gp);                         // (max factors appended: their components, for the step's k_select_mixture)
             c.h_bad.need(4);
             hybrid = inc_fast_step(c, gp, N, F, c.inc_F, c.inc_N, nullptr, lam);
             reused = hybrid;
@@ -298,9 +299,11 @@ static void inc_impl(april_graph_t *g, april_graph_cholesky_param_t *param) {
         for (const RefModel::Visit &v : visits) inv.push_back(v.node);
         patch_states = pack_states_some(gp, g, inv); lazy_states = true;
     } else patch_states = pack_states_diff(gp, g);
+    select_new_max(gp, g, c.inc_F);                    // new max factors: selected at their l_points as the mirror holds them, into h_z / h_W
     const double tp1 = now_ms() - (tp0b - tp0a);      // (profile: "pack" = factors + states, "model" = the bookkeeping in between)
     const double tp2 = tp1 + (tp0b - tp0a);
     if (F > gp.F_cap || !g_opt.inc_fast || !gp.host_idx.empty()) upload_factors(gp);     // (growing the device arrays re-uploads everything)
+    upload_mixture(gp);
     if (!gp.host_idx.empty()) {       // new foreign factors are linearised now, at the host objects' current l_points
         eval_host_factors(gp, g, gp.host_evaluated);     // (aprilsam.c:508-542); older ones keep their evaluation
         upload_host_index(gp);
@@ -553,3 +556,35 @@ static double chi2_impl(april_graph_t *g) {
     return chi2;
 }
 
+
+// aprilsam_amd_max_selected: which component each listed factor's most recent linearisation used -- k_select_mixture's
+// record (d_sel) for the factors on the device, the host's selection (select_new_max) or -1 for the others.  A bad index is refused before
+// anything is read, and (like every query) leaves the param's plan alone.
+int max_selected(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *factors, int *out) {
+    const int Fg = g ? zsize(g->factors) : 0;
+    if (!g || n < 0 || (n > 0 && (!factors || !out))) { set_last_error(ERR_BAD_GRAPH, "aprilsam_amd_max_selected: bad argument"); return ERR_BAD_GRAPH; }
+    for (int i = 0; i < n; i++)
+        if (factors[i] < 0 || factors[i] >= Fg) {
+            set_last_error(ERR_BAD_GRAPH, "aprilsam_amd_max_selected: factor " + std::to_string(factors[i]) + " out of range (" + std::to_string(Fg) + " factors)");
+            return ERR_BAD_GRAPH;
+        }
+    return guarded_rc(param, g, [&]() -> int {
+        SlotLock lk(param, g);
+        auto it = g_packs.find(g);
+        if (it == g_packs.end() || it->second->slot != t_slot) { for (int i = 0; i < n; i++) out[i] = -1; return 0; }
+        GraphPack &gp = *it->second;
+        std::vector<int> sel(gp.mx_sel);
+        if (gp.mx_on_device > 0) {             // (through the pinned staging buffer; the stream is idle before it is written)
+            HIPCHECK(hipStreamSynchronize(gp.stream));
+            gp.mx_stage.need((size_t)gp.mx_on_device);
+            HIPCHECK(hipMemcpyAsync(gp.mx_stage.p, gp.d_sel.p, (size_t)4 * gp.mx_on_device, hipMemcpyDeviceToHost, gp.stream));
+            HIPCHECK(hipStreamSynchronize(gp.stream));
+            memcpy(sel.data(), gp.mx_stage.p, (size_t)4 * gp.mx_on_device);
+        }
+        for (int i = 0; i < n; i++) {
+            const int gi = factors[i], m = gi < (int)gp.mx_of.size() && gi < gp.Fg ? gp.mx_of[gi] : -1;
+            out[i] = m >= 0 ? sel[m] : -1;
+        }
+        return 0;
+    });
+}

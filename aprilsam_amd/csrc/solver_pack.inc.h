@@ -64,6 +64,17 @@ struct GraphPack {
     // factors of foreign types, evaluated on the host through factor->eval: indices, 33 doubles each
     // (Haa, Hab, Hbb, ga, gb), how many of them hold a current evaluation
     std::vector<int> host_idx; HBuf<double> h_hostH; DBuf<double> d_hostH; DBuf<int> d_host_idx; int host_evaluated = 0;
+    // max-mixture factors: per max factor m its packed entry mx_f[m] and components [mx_k[m], mx_k[m + 1]); per
+    // component z (3), W (9), c = -2 logw - ln det W and logw as given (content check); mx_sel: the selection made on the host (incremental
+    // steps; -1: none yet) -- d_sel, written by k_select_mixture, holds the selection of each factor's most recent linearisation.  mx_of: per
+    // graph factor its m or -1.  mx_gen changes whenever the table's size or device addresses do: captured graphs are keyed by it
+    std::vector<int> mx_f, mx_k{ 0 }, mx_sel, mx_of; std::vector<double> mx_z, mx_W, mx_c, mx_logw;
+    DBuf<int> d_mx_f, d_mx_k, d_sel; DBuf<double> d_mx_z, d_mx_W, d_mx_c; HBuf<double> mx_stage;
+    int mx_on_device = 0; bool mx_dirty = false; long long mx_gen = 0;
+    int n_max() const { return (int)mx_f.size(); }
+    void mx_clear() {
+        if (!mx_f.empty() || mx_on_device) mx_gen++;      // (a pack that never held max factors keeps its captured graphs)
+        mx_f.clear(); mx_k.assign(1, 0); mx_sel.clear(); mx_of.clear(); mx_z.clear(); mx_W.clear(); mx_c.clear(); mx_logw.clear(); mx_on_device = 0; mx_dirty = false; }
     hipStream_t stream = nullptr;
     HBuf<double> h_scalar;
     // incremental steps: the pinned mirrors h_state / h_lp and the device arrays d_state / d_lp hold the same values (mirror_sync),
@@ -75,6 +86,7 @@ struct GraphPack {
         h_fa.release(); h_fb.release(); h_z.release(); h_W.release(); h_state.release(); h_lp.release(); h_dx.release();
         d_fa.release(); d_fb.release(); d_z.release(); d_W.release(); d_state.release(); d_lp.release(); d_lp_last.release(); d_dx.release();
         d_chi2f.release(); d_scalar.release(); h_scalar.release(); h_hostH.release(); d_hostH.release(); d_host_idx.release(); d_upt.release();
+        d_mx_f.release(); d_mx_k.release(); d_sel.release(); d_mx_z.release(); d_mx_W.release(); d_mx_c.release(); mx_stage.release(); mx_clear();
         if (stream) { forget_stream(stream); park_stream(slot, stream); }
         stream = nullptr;
     }
@@ -146,14 +158,18 @@ static void pack_factors(GraphPack &gp, const april_graph_t *g, bool validate_ol
     // (incremental calls only ever look at the factors added since the previous call, aprilsam.c:508-511: first and last packed pointer
     // as a sanity check instead of all of them -- the comparison of 5 000 pointers was a microsecond of every step)
     if (valid && trust) valid = from == 0 || (validate_old ? memcmp(gp.fptr.data(), fs, sizeof(void *) * from) == 0 : (gp.fptr[0] == fs[0] && gp.fptr[from - 1] == fs[from - 1]));
-    auto restart = [&]() { gp.topo_version++; from = 0; gp.F = 0; gp.F_on_device = 0; gp.host_idx.clear(); gp.host_evaluated = 0; gp.is_host.clear(); gp.p2g.clear(); gp.vslot.clear(); gp.g2p.assign(1, 0); gp.asym.clear(); gp.n_asym = 0; };
+    auto restart = [&]() { gp.topo_version++; from = 0; gp.F = 0; gp.F_on_device = 0; gp.host_idx.clear(); gp.host_evaluated = 0; gp.is_host.clear(); gp.p2g.clear(); gp.vslot.clear(); gp.g2p.assign(1, 0); gp.asym.clear(); gp.n_asym = 0; gp.mx_clear(); };
     if (!valid) restart();
     // one graph factor -> its packed entries (a, b, host flag, node slots of a host pair, what the pair carries)
     struct Ent { int a, b; bool host; unsigned short slots; unsigned char carry; };
-    Ent ents[64]; int ne = 0;
+    Ent ents[64]; int ne = 0; bool is_max = false;
     auto classify = [&](const april_graph_factor_t *f, int i) {
-        ne = 0;
-        if (f->type == APRIL_GRAPH_FACTOR_XYT_TYPE && f->nnodes == 2) ents[ne++] = Ent{ f->nodes[0], f->nodes[1], false, 0, 3 };
+        ne = 0; is_max = false;
+        if (is_native_max(f)) {        // (before anything reads u.common: u.max aliases it)
+            char why[192];
+            if (f->nnodes != 2 || !max_check(f, why, sizeof why)) fail(ERR_UNSUPPORTED, "factor %d: max factor: %s", i, f->nnodes != 2 ? "not binary" : why);
+            ents[ne++] = Ent{ f->nodes[0], f->nodes[1], false, 0, 3 }; is_max = true;
+        } else if (f->type == APRIL_GRAPH_FACTOR_XYT_TYPE && f->nnodes == 2) ents[ne++] = Ent{ f->nodes[0], f->nodes[1], false, 0, 3 };
         else if (f->type == APRIL_GRAPH_FACTOR_XYTPOS_TYPE && f->nnodes == 1) ents[ne++] = Ent{ f->nodes[0], -1, false, 0, 3 };
         else if ((f->nnodes == 1 || f->nnodes == 2) && f->eval)       // any other type: the factor's own eval(), on the host
             ents[ne++] = Ent{ f->nodes[0], f->nnodes == 2 ? f->nodes[1] : -1, true, (unsigned short)(f->nnodes == 2 ? 1 : 0xff), 3 };
@@ -188,9 +204,25 @@ static void pack_factors(GraphPack &gp, const april_graph_t *g, bool validate_ol
             if (gp.g2p[i + 1] - p0 != ne) { changed = true; break; }
             for (int e = 0; e < ne && !changed; e++)
                 changed = ents[e].a != gp.h_fa.p[p0 + e] || ents[e].b != gp.h_fb.p[p0 + e] || ents[e].host != (bool)gp.is_host[p0 + e];
+            if (!changed) changed = is_max != (gp.mx_of[i] >= 0) || (is_max && gp.mx_k[gp.mx_of[i] + 1] - gp.mx_k[gp.mx_of[i]] != f->u.max.nfactors);
             if (changed) break;
             gp.fptr[i] = f;
             if (ents[0].host) continue;
+            if (is_max) {              // the components against the table: an edited one is copied and the table uploaded again
+                const int m = gp.mx_of[i];
+                bool edit = false;
+                for (int k = gp.mx_k[m], j = 0; k < gp.mx_k[m + 1]; k++, j++) {
+                    const april_graph_factor_t *cf = f->u.max.factors[j];
+                    double *zp = gp.mx_z.data() + (size_t)3 * k, *Wp = gp.mx_W.data() + (size_t)9 * k;
+                    if (memcmp(zp, cf->u.common.z, 24) != 0 || memcmp(Wp, cf->u.common.W->data, 72) != 0 || memcmp(&gp.mx_logw[k], &f->u.max.logw[j], 8) != 0) {
+                        memcpy(zp, cf->u.common.z, 24); memcpy(Wp, cf->u.common.W->data, 72);
+                        gp.mx_logw[k] = f->u.max.logw[j]; gp.mx_c[k] = max_const(f, j);
+                        edit = true;
+                    }
+                }
+                if (edit) { gp.mx_dirty = true; lo = std::min(lo, p0); hi = std::max(hi, p0 + 1); }
+                continue;
+            }
             double *zp = gp.h_z.p + (size_t)3 * p0, *Wp = gp.h_W.p + (size_t)9 * p0;
             if (memcmp(zp, f->u.common.z, 24) != 0 || memcmp(Wp, f->u.common.W->data, 72) != 0) {
                 memcpy(zp, f->u.common.z, 24); memcpy(Wp, f->u.common.W->data, 72);
@@ -205,7 +237,7 @@ static void pack_factors(GraphPack &gp, const april_graph_t *g, bool validate_ol
             gp.content_version++;
         }
     }
-    gp.fptr.resize(Fg); gp.g2p.resize((size_t)Fg + 1);
+    gp.fptr.resize(Fg); gp.g2p.resize((size_t)Fg + 1); gp.mx_of.resize(Fg, -1);
     int F = gp.g2p[from];
     {   // the pinned mirrors are sized ONCE for everything this call appends (a pinned reallocation costs a quarter of a millisecond)
         size_t total = (size_t)F;
@@ -230,6 +262,20 @@ static void pack_factors(GraphPack &gp, const april_graph_t *g, bool validate_ol
                 memset(gp.h_z.p + (size_t)3 * F, 0, 24); memset(gp.h_W.p + (size_t)9 * F, 0, 72);
                 gp.note_asym(F, gp.h_W.p + (size_t)9 * F, false);
                 gp.host_idx.push_back(F);
+            } else if (is_max) {       // the slot holds component 0 until a selection writes it (k_select_mixture, select_new_max)
+                const april_graph_factor_t *c0 = f->u.max.factors[0];
+                memcpy(gp.h_z.p + (size_t)3 * F, c0->u.common.z, 24);
+                memcpy(gp.h_W.p + (size_t)9 * F, c0->u.common.W->data, 72);
+                gp.note_asym(F, gp.h_W.p + (size_t)9 * F, true);
+                gp.mx_of[i] = gp.n_max(); gp.mx_f.push_back(F); gp.mx_sel.push_back(-1);
+                for (int j = 0; j < f->u.max.nfactors; j++) {
+                    const april_graph_factor_t *cf = f->u.max.factors[j];
+                    gp.mx_z.insert(gp.mx_z.end(), cf->u.common.z, cf->u.common.z + 3);
+                    gp.mx_W.insert(gp.mx_W.end(), cf->u.common.W->data, cf->u.common.W->data + 9);
+                    gp.mx_c.push_back(max_const(f, j)); gp.mx_logw.push_back(f->u.max.logw[j]);
+                }
+                gp.mx_k.push_back((int)gp.mx_c.size());
+                gp.mx_gen++;
             } else {
                 memcpy(gp.h_z.p + (size_t)3 * F, f->u.common.z, 24);
                 memcpy(gp.h_W.p + (size_t)9 * F, f->u.common.W->data, 72);
@@ -239,6 +285,77 @@ static void pack_factors(GraphPack &gp, const april_graph_t *g, bool validate_ol
         gp.g2p[i + 1] = F;
     }
     gp.F = F; gp.Fg = Fg;
+}
+// the component table of the max factors -> device: what was appended since the last upload, everything after an edit or a move.  d_sel
+// receives the host's selections of the appended factors only: the device's own of the older ones stay (kept across a move)
+static void upload_mixture(GraphPack &gp) {
+    const int M = gp.n_max(), C = gp.mx_k.back();
+    if (M == 0 || (gp.mx_on_device == M && !gp.mx_dirty)) return;
+    hipStream_t s = gp.stream;
+    // (through the pinned staging buffer mx_stage, as every other upload of the pack goes from pinned memory: the stream is idle before
+    // it is written -- this runs only when max factors were added or edited)
+    HIPCHECK(hipStreamSynchronize(s));
+    // (each buffer against its own capacity: they grow by half at different moments)
+    if ((size_t)M > gp.d_sel.cap || (size_t)M > gp.d_mx_f.cap || (size_t)M + 1 > gp.d_mx_k.cap || (size_t)C > gp.d_mx_c.cap || (size_t)3 * C > gp.d_mx_z.cap ||
+        (size_t)9 * C > gp.d_mx_W.cap) {
+        if (gp.mx_on_device > 0) {
+            gp.mx_stage.need((size_t)gp.mx_on_device);
+            HIPCHECK(hipMemcpyAsync(gp.mx_stage.p, gp.d_sel.p, (size_t)4 * gp.mx_on_device, hipMemcpyDeviceToHost, s));
+            HIPCHECK(hipStreamSynchronize(s));
+            memcpy(gp.mx_sel.data(), gp.mx_stage.p, (size_t)4 * gp.mx_on_device);
+        }
+        gp.d_mx_f.need(M); gp.d_sel.need(M); gp.d_mx_k.need((size_t)M + 1);
+        gp.d_mx_z.need((size_t)3 * C); gp.d_mx_W.need((size_t)9 * C); gp.d_mx_c.need(C);
+        gp.mx_on_device = 0; gp.mx_dirty = true; gp.mx_gen++;
+    }
+    const int m0 = gp.mx_dirty ? 0 : gp.mx_on_device, k0 = gp.mx_k[m0], s0 = std::min(gp.mx_on_device, M);
+    // staging layout (8-byte words): z | W | c | f, k, sel (ints, packed by two)
+    const size_t nz = (size_t)3 * (C - k0), nW = (size_t)9 * (C - k0), nc = (size_t)(C - k0);
+    const size_t ni = (size_t)(M - m0) + (size_t)(M + 1 - m0) + (size_t)(M - s0);
+    gp.mx_stage.need(nz + nW + nc + (ni + 1) / 2);
+    double *st = gp.mx_stage.p;
+    memcpy(st, gp.mx_z.data() + (size_t)3 * k0, 8 * nz);
+    memcpy(st + nz, gp.mx_W.data() + (size_t)9 * k0, 8 * nW);
+    memcpy(st + nz + nW, gp.mx_c.data() + k0, 8 * nc);
+    int *si = (int *)(st + nz + nW + nc);
+    memcpy(si, gp.mx_f.data() + m0, (size_t)4 * (M - m0));
+    memcpy(si + (M - m0), gp.mx_k.data() + m0, (size_t)4 * (M + 1 - m0));
+    memcpy(si + (M - m0) + (M + 1 - m0), gp.mx_sel.data() + s0, (size_t)4 * (M - s0));
+    if (nc) {
+        HIPCHECK(hipMemcpyAsync(gp.d_mx_z.p + (size_t)3 * k0, st, 8 * nz, hipMemcpyHostToDevice, s));
+        HIPCHECK(hipMemcpyAsync(gp.d_mx_W.p + (size_t)9 * k0, st + nz, 8 * nW, hipMemcpyHostToDevice, s));
+        HIPCHECK(hipMemcpyAsync(gp.d_mx_c.p + k0, st + nz + nW, 8 * nc, hipMemcpyHostToDevice, s));
+    }
+    HIPCHECK(hipMemcpyAsync(gp.d_mx_f.p + m0, si, (size_t)4 * (M - m0), hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(gp.d_mx_k.p + m0, si + (M - m0), (size_t)4 * (M + 1 - m0), hipMemcpyHostToDevice, s));
+    if (M > s0) HIPCHECK(hipMemcpyAsync(gp.d_sel.p + s0, si + (M - m0) + (M + 1 - m0), (size_t)4 * (M - s0), hipMemcpyHostToDevice, s));
+    gp.mx_on_device = M; gp.mx_dirty = false;
+}
+// incremental steps: the max factors packed at or after entry f_from are selected on the host at the l_point mirror (max_select, the rule
+// k_select_mixture applies) and their slots of h_z / h_W take the winner -- the fast path uploads and linearises them as plain xyt factors
+static void select_new_max(GraphPack &gp, const april_graph_t *g, int f_from) {
+    april_graph_factor_t **fs = (april_graph_factor_t **)g->factors->data;
+    for (int m = gp.n_max() - 1; m >= 0 && gp.mx_f[m] >= f_from; m--) {
+        const int p = gp.mx_f[m];
+        const april_graph_factor_t *f = fs[gp.p2g[p]];
+        const int k = max_select(f, gp.h_lp.p + (size_t)3 * gp.h_fa.p[p], gp.h_lp.p + (size_t)3 * gp.h_fb.p[p]);
+        gp.mx_sel[m] = k;
+        memcpy(gp.h_z.p + (size_t)3 * p, &gp.mx_z[(size_t)3 * (gp.mx_k[m] + k)], 24);
+        memcpy(gp.h_W.p + (size_t)9 * p, &gp.mx_W[(size_t)9 * (gp.mx_k[m] + k)], 72);
+    }
+}
+// the launches every linearisation / chi^2 of a pack with max factors is bracketed with (none for a pack without)
+static void enqueue_select(GraphPack &gp, hipStream_t s) {
+    const int M = gp.n_max();
+    if (M == 0) return;
+    hipLaunchKernelGGL(k_select_mixture, dim3((M + TPB - 1) / TPB), dim3(TPB), 0, s, M, gp.d_mx_f.p, gp.d_mx_k.p, gp.d_mx_z.p, gp.d_mx_W.p, gp.d_mx_c.p,
+                       gp.d_fa.p, gp.d_fb.p, gp.d_lp.p, gp.d_z.p, gp.d_W.p, gp.d_sel.p);
+}
+static void enqueue_chi2_mixture(GraphPack &gp, hipStream_t s) {
+    const int M = gp.n_max();
+    if (M == 0) return;
+    hipLaunchKernelGGL(k_chi2_mixture, dim3((M + TPB - 1) / TPB), dim3(TPB), 0, s, M, gp.d_mx_f.p, gp.d_mx_k.p, gp.d_mx_z.p, gp.d_mx_W.p, gp.d_mx_c.p,
+                       gp.d_fa.p, gp.d_fb.p, gp.d_state.p, gp.d_chi2f.p);
 }
 static void upload_factors(GraphPack &gp) {
     const int F = gp.F;
@@ -264,6 +381,7 @@ static void upload_factors(GraphPack &gp) {
     gp.dirty_lo = gp.dirty_hi = 0;
     gp.F_on_device = F;
     gp.d_scalar.need(8); gp.h_scalar.need(8);
+    upload_mixture(gp);
 }
 // evaluate the host factors [from, end) through their vtable (aprilsam.c:156 calls factor->eval the same way) and form
 // (J_a^T W) J_a, (J_a^T W) J_b, (J_b^T W) J_b, (J^T W) r in the reference's association (aprilsam.c:162-187)

@@ -108,6 +108,11 @@ class SolverLib:
                 d.aprilsam_amd_marginals_joint.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.c_int, _ip, _ip, _dp]
                 d.aprilsam_amd_debug_selinv_runs.argtypes = [C.POINTER(abi.CholeskyParam)]
                 d.aprilsam_amd_debug_selinv_runs.restype = C.c_longlong
+            if hasattr(d, "aprilsam_amd_factor_max_create"):
+                d.aprilsam_amd_factor_max_create.restype = C.POINTER(abi.Factor)
+                d.aprilsam_amd_factor_max_create.argtypes = [C.POINTER(C.POINTER(abi.Factor)), _dp, C.c_int]
+            if hasattr(d, "aprilsam_amd_max_selected"):      # (defined in the HIP translation unit)
+                d.aprilsam_amd_max_selected.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.c_int, _ip, _ip]
             d.aprilsam_amd_graph_save_ex.argtypes = [C.POINTER(abi.Graph), C.c_char_p, C.c_ulonglong]
             d.aprilsam_amd_graph_load.restype = C.POINTER(abi.Graph)
             d.aprilsam_amd_graph_load.argtypes = [C.c_char_p]
@@ -252,6 +257,43 @@ class Graph:
         m = self._matd(W)
         f = self.lib.dll.april_graph_factor_xyt_create(int(a), int(b), zz, None, C.byref(m))
         self.lib._add_factor(self.ptr, f)
+
+    def make_factor_max(self, a, b, zs, Ws, logw):
+        """a max-mixture factor on (a, b) (include/aprilsam_amd.h: aprilsam_amd_factor_max_create), NOT added to the graph: one xyt
+        component per row of zs [K, 3] / Ws [K, 9], log weights logw [K].  Raises ValueError (message of the library) when refused."""
+        zs = np.asarray(zs, float).reshape(-1, 3); Ws = np.asarray(Ws, float).reshape(-1, 9)
+        lw = np.ascontiguousarray(logw, float).ravel()
+        K = len(zs)
+        if len(Ws) != K or len(lw) != K:
+            raise ValueError("zs, Ws and logw must have one row per component")
+        d = self.lib.dll
+        comps = (C.POINTER(abi.Factor) * max(K, 1))()
+        for i in range(K):
+            zz = (C.c_double * 3)(*zs[i])
+            m = self._matd(Ws[i])
+            comps[i] = d.april_graph_factor_xyt_create(int(a), int(b), zz, None, C.byref(m))
+        f = d.aprilsam_amd_factor_max_create(comps, _np_d(lw), K)
+        if not f:
+            for i in range(K):          # (a refused call leaves the components with the caller)
+                abi.destroy_factor(comps[i])
+            code, msg = self.lib.last_error()
+            raise ValueError(f"aprilsam_amd_factor_max_create refused its arguments ({code}): {msg}")
+        return f
+
+    def add_factor_max(self, a, b, zs, Ws, logw):
+        """append a max-mixture factor (make_factor_max); returns its factor index"""
+        self.lib._add_factor(self.ptr, self.make_factor_max(a, b, zs, Ws, logw))
+        return self.n_factors - 1
+
+    def max_selected(self, param, factors=None):
+        """int array: the component each listed factor's most recent linearisation used, -1 for a non-max factor or one not yet
+        linearised (include/aprilsam_amd.h: aprilsam_amd_max_selected); all factors when `factors` is None"""
+        idx = np.arange(self.n_factors, dtype=np.int32) if factors is None else np.ascontiguousarray(factors, dtype=np.int32).ravel()
+        out = np.full(len(idx), -1, np.int32)
+        rc = self.lib.dll.aprilsam_amd_max_selected(self.ptr, param.ptr if param is not None else None, len(idx), _np_i(idx), _np_i(out))
+        if rc != 0:
+            raise RuntimeError(f"aprilsam_amd_max_selected failed rc={rc}: {self.lib.last_error()}")
+        return out
 
     def add_factor_xytpos(self, a, z, W):
         zz = (C.c_double * 3)(*z)

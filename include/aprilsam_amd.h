@@ -64,6 +64,7 @@ typedef struct april_graph_node   april_graph_node_t;
 
 /* aprilsam.h:98-146 — 104 bytes. The device path recognises type 1 (xyt) and 2 (xytpos) and reads
  * nodes[], u.common.z and u.common.W directly; function pointers are never called on the device.
+ * This library's own max-mixture factors (type 3, u.max, PART 4) are native too.
  * Any other type (1 or 2 nodes) is evaluated on the HOST through ->eval(), as aprilsam.c:156 does. */
 struct april_graph_factor {
     int   type;
@@ -429,6 +430,25 @@ int aprilsam_amd_marginals(april_graph_t *graph, april_graph_cholesky_param_t *p
 int aprilsam_amd_marginals_joint(april_graph_t *graph, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, double *cov);
 /* debug: number of selected inversions run on this param so far (-1: no context) */
 long long aprilsam_amd_debug_selinv_runs(const april_graph_cholesky_param_t *param);
+
+/* ---- max-mixture factors (Olson & Agarwal, RSS 2012) ---------------------------------------------------
+ * A max factor on the ordered pair (a, b) holds K = 1..8 components, each an xyt factor made by april_graph_factor_xyt_create on
+ * the same (a, b) with a symmetric W of det W > 0, and a log weight per component.  At a point p component i scores
+ *     s_i = r_i(p)^T W_i r_i(p) - 2 logw_i - ln det W_i           (r_i: the xyt residual, mod2pi on theta)
+ * and the selected component is  best = 0; for i in 1..K-1: if (s_i < s_best) best = i  (ties and NaN: the lower index).
+ * Wherever the solver linearises the factor it selects at the factor's linearisation point (l_point of a and b), on the GPU, and
+ * linearises the selected component exactly as an xyt factor; an incremental step selects a new factor when it first linearises
+ * it.  april_graph_chi2 counts 0.5 r_s^T W_s r_s with s selected at the states.  With K = 1 and logw = 0 the factor is its single
+ * component, bit for bit.  The layout is the reference's u.max { factors, logw, nfactors }; eval / state_eval return the selected
+ * component's evaluation at l_point / state, copy is deep, destroy frees the components.
+ * A factor is native only if type == APRILSAM_AMD_FACTOR_MAX_TYPE AND its eval is this library's: a foreign factor that uses tag 3
+ * keeps the host-evaluated path.  Sharded runs refuse max factors (-12); .graph files cannot hold them (save returns an error). */
+#define APRILSAM_AMD_FACTOR_MAX_TYPE 3
+/* takes ownership of components[0..n); copies logw; NULL (+ aprilsam_amd_last_error, -12) on a bad argument, owning nothing then */
+april_graph_factor_t *aprilsam_amd_factor_max_create(april_graph_factor_t **components, const double *logw, int n);
+/* for each listed graph factor: index of the component its most recent linearisation used, -1 for a non-max factor or one not yet
+ * linearised; returns 0 or a negative error code (-13 for an index out of range or a bad argument) */
+int aprilsam_amd_max_selected(april_graph_t *graph, april_graph_cholesky_param_t *param, int n, const int *factors, int *out);
 
 /* ---- multi-GPU: nested-dissection subtree sharding, one process per GPU -------
  * The reference has no counterpart (it is sequential); a C host drives a sharded solve through the same graph / param
