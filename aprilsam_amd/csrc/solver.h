@@ -94,6 +94,9 @@ int api_set_option(const char *name, double v);
 int api_get_option(const char *name, double *v);
 int marginals(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *qa, const int *qb, double *cov, bool joint);     // solver_marginals.inc.h
 long long selinv_runs(const april_graph_cholesky_param_t *param);
+int marginals_joint_any(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, double *cov);      // solver_gating.inc.h
+int gate_xyt(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, const double *z, const double *W, double *d2, double *S);
+long long path_solve_bytes(const april_graph_cholesky_param_t *param);
 int max_selected(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *factors, int *out);   // solver_pack.inc.h
 // max-mixture factors (host_objects.cpp)
 constexpr int MAX_MIX_K = 8;

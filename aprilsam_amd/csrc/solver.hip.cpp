@@ -29,6 +29,7 @@
 #include "kernels.hip.h"
 #include "maxmix.hip.h"
 #include "selinv.hip.h"
+#include "pathsolve.hip.h"
 #include "plan.h"
 #include "refmodel.h"
 #include "solver.h"
@@ -241,6 +242,7 @@ struct PatchList {
 #include "solver_resident.inc.h"
 #include "solver_shard.inc.h"
 #include "solver_marginals.inc.h"
+#include "solver_gating.inc.h"
 
 // ------------------------------------------------------------------------------------------------------
 // Runtime warm-up, once per process, from april_graph_cholesky_param_init (the API's set-up call; aprilsam.c:45-64 has nothing to set up).
@@ -458,3 +460,11 @@ extern "C" int aprilsam_amd_max_selected(april_graph_t *graph, april_graph_chole
     return asam::max_selected(graph, param, n, factors, out);
 }
 extern "C" long long aprilsam_amd_debug_selinv_runs(const april_graph_cholesky_param_t *param) { return asam::selinv_runs(param); }
+extern "C" int aprilsam_amd_marginals_joint_any(april_graph_t *graph, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, double *cov) {
+    return asam::marginals_joint_any(graph, param, n, a, b, cov);
+}
+extern "C" int aprilsam_amd_gate_xyt(april_graph_t *graph, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, const double *z,
+                                     const double *W, double *d2, double *S) {
+    return asam::gate_xyt(graph, param, n, a, b, z, W, d2, S);
+}
+extern "C" long long aprilsam_amd_debug_path_solve_bytes(const april_graph_cholesky_param_t *param) { return asam::path_solve_bytes(param); }

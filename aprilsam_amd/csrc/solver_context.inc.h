@@ -63,6 +63,21 @@ struct IncState {
 // marginal covariances (solver_marginals.inc.h): per level, the ranges of its work entries in the selected inversion's table
 struct SelLevel { int gat_off = 0, n_gat = 0, diag_off = 0, n_diag = 0, tri_off = 0, n_tri = 0, x_off = 0, n_x = 0, sus_off = 0, n_sus = 0, sss_off = 0, n_sss = 0; };
 
+// joint covariances of any pair and gating (solver_gating.inc.h): the fronts of the retained factor's structure (host), the scratch maps of
+// one call, and the device buffers of the path solves
+struct PathState {
+    long long serial = -1;                 // fact_serial the host tables describe
+    int N = 0;
+    std::vector<SelFront> fr; std::vector<int> depth, i32, rec, node_j;      // rec: front -> record, node_j: node -> column group (-1 between calls)
+    DBuf<PsFront> d_fr; DBuf<int4> d_ent; DBuf<int> d_cmap; DBuf<long long> d_at; DBuf<PsPath> d_path; DBuf<PsPair> d_pair;
+    DBuf<double> d_buf, d_cov, d_in; HBuf<double> h_out;
+    long long peak_doubles = 0;            // the largest work buffer a chunk has used
+    void release() {
+        d_fr.release(); d_ent.release(); d_cmap.release(); d_at.release(); d_path.release(); d_pair.release(); d_buf.release(); d_cov.release(); d_in.release(); h_out.release();
+        fr.clear(); depth.clear(); i32.clear(); rec.clear(); node_j.clear(); serial = -1;
+    }
+};
+
 struct Context {
     Plan plan;
     bool have_plan = false;
@@ -175,9 +190,11 @@ struct Context {
     long long fact_serial = 0;                     // factorisations recorded so far (only grows)
     std::vector<SelLevel> sel_levels; int sel_tab_kind = 0, sel_N = 0;
     long long sel_serial = -1, sel_tab_serial = -1, sel_runs = 0, sel_pool = 1; double sel_flops = 0;
+    PathState ps;
     void release_sel() {
         d_sigma.release(); d_sel_scr.release(); d_sel_fd.release(); d_sel_i32.release(); d_sel_q.release(); d_sel_ent.release(); h_cov.release();
         sel_levels.clear(); sel_serial = -1; sel_tab_serial = -1;
+        ps.release();
     }
     void release() {
         release_sel();

@@ -1,0 +1,279 @@
+// solver_gating.inc.h -- part of solver.hip.cpp (ONE translation unit); included from there, inside namespace asam.
+// Contents: aprilsam_amd_marginals_joint_any / aprilsam_amd_gate_xyt: joint covariances of any pose pairs from the retained factor
+// by triangular solves along assembly-tree paths (pathsolve.hip.h), and the Mahalanobis gating of candidate xyt measurements.
+// DESIGN.md section 13.
+// ------------------------------------------------------------------------------------------------------
+// The fronts of the factor's structure (sel_fronts, solver_marginals.inc.h: the plan or the incremental path's extended structure),
+// kept against the factorisation counter.
+static void ps_fronts(Context &c) {
+    PathState &S = c.ps;
+    if (S.serial == c.fact_serial) return;
+    S.serial = -1;
+    long long pool_end; double flops;
+    S.N = sel_fronts(c, S.fr, S.depth, S.i32, pool_end, flops);
+    S.rec.assign(S.fr.size(), -1);
+    S.serial = c.fact_serial;
+}
+
+// doubles of work buffer node q's three columns take: 3 (s + u) summed over its path
+static long long ps_path_doubles(const PathState &S, int q) {
+    long long d = 0;
+    for (int t = S.i32[S.N + S.i32[q]]; t >= 0; t = S.fr[t].parent) d += 3ll * (S.fr[t].s + S.fr[t].u);
+    return d;
+}
+
+// One chunk: the columns of `nodes` solved along their paths, then the joint blocks of the pairs (ja, jb) (indices into nodes) into
+// output slots out0, out0 + 1, ...: device S.d_cov and pinned S.h_out.
+static void ps_chunk(Context &c, hipStream_t s, const std::vector<int> &nodes, const std::vector<int2> &pj, int out0) {
+    PathState &S = c.ps;
+    const std::vector<SelFront> &fr = S.fr;
+    const int N = S.N, nn = (int)nodes.size();
+    std::vector<int> pbeg((size_t)nn + 1, 0), pfr;              // the fronts on each node's path, its own front first
+    for (int j = 0; j < nn; j++) {
+        for (int t = S.i32[N + S.i32[nodes[j]]]; t >= 0; t = fr[t].parent) pfr.push_back(t);
+        pbeg[j + 1] = (int)pfr.size();
+    }
+    // records: the fronts the columns pass through, deepest level first (a parent's record comes after its children's)
+    std::vector<int> touched;
+    for (int t : pfr) if (S.rec[t] < 0) { S.rec[t] = 0; touched.push_back(t); }
+    std::sort(touched.begin(), touched.end(), [&](int x, int y) { return S.depth[x] != S.depth[y] ? S.depth[x] > S.depth[y] : x < y; });
+    const int nr = (int)touched.size();
+    for (int r = 0; r < nr; r++) S.rec[touched[r]] = r;
+    // the nodes through each record, in node-list order: slot[e] = index of path entry e's node among its front's nodes
+    std::vector<int> m((size_t)nr, 0), slot(pfr.size());
+    for (size_t e = 0; e < pfr.size(); e++) slot[e] = m[S.rec[pfr[e]]]++;
+    std::vector<PsFront> rec((size_t)nr);
+    std::vector<int> cbeg((size_t)nr + 1, 0);
+    long long used = 0;
+    for (int r = 0; r < nr; r++) {
+        const SelFront &F = fr[touched[r]];
+        PsFront &R = rec[r];
+        R.off = F.off; R.buf = used; R.s = F.s; R.u = F.u; R.R = F.R; R.ncol = 3 * m[r];
+        R.parent = F.parent >= 0 ? S.rec[F.parent] : -1; R.rel_begin = F.rel_begin; R.cmap = cbeg[r]; R.pad = 0;
+        if (F.parent >= 0 && R.parent < 0) fail(ERR_INTERNAL, "aprilsam_amd_marginals_joint_any: a path leaves the tree");
+        cbeg[r + 1] = cbeg[r] + R.ncol;
+        used += (long long)(F.s + F.u) * R.ncol;
+    }
+    std::vector<int> cmap((size_t)std::max(cbeg[nr], 1), -1);
+    std::vector<long long> at((size_t)3 * nn);
+    std::vector<PsPath> path(pfr.size());
+    for (int j = 0; j < nn; j++) {
+        for (int e = pbeg[j]; e < pbeg[j + 1]; e++) {
+            const PsFront &R = rec[S.rec[pfr[e]]];
+            const int ld = R.s + R.u;
+            path[e] = PsPath{ R.buf + 3ll * slot[e] * ld, ld, R.s };
+            if (e + 1 < pbeg[j + 1])
+                for (int k = 0; k < 3; k++) cmap[R.cmap + 3 * slot[e] + k] = 3 * slot[e + 1] + k;
+        }
+        const int e0 = pbeg[j], p = S.i32[nodes[j]];
+        const SelFront &F = fr[pfr[e0]];
+        const PsFront &R = rec[S.rec[pfr[e0]]];
+        const int ld = R.s + R.u, l = 3 * (p - F.first);
+        if (l < 0 || l + 3 > F.s) fail(ERR_INTERNAL, "aprilsam_amd_marginals_joint_any: node %d is not among its front's own rows", nodes[j]);
+        for (int k = 0; k < 3; k++) at[3 * j + k] = R.buf + (3ll * slot[e0] + k) * ld + l + k;
+    }
+    std::vector<PsPair> pairs(pj.size());
+    for (size_t i = 0; i < pj.size(); i++) {
+        const int ja = pj[i].x, jb = pj[i].y, na = pbeg[ja + 1] - pbeg[ja], nb = pbeg[jb + 1] - pbeg[jb];
+        int nc = 0;
+        while (nc < std::min(na, nb) && pfr[pbeg[ja + 1] - 1 - nc] == pfr[pbeg[jb + 1] - 1 - nc]) nc++;
+        pairs[i] = PsPair{ pbeg[ja], na, pbeg[jb], nb, nc, out0 + (int)i };
+    }
+    // work entries, level by level
+    struct Lev { int tr_off, n_tr, gm_off, n_gm; };
+    std::vector<Lev> lev;
+    std::vector<int4> ent;
+    for (int r0 = 0; r0 < nr; ) {
+        int r1 = r0;
+        while (r1 < nr && S.depth[touched[r1]] == S.depth[touched[r0]]) r1++;
+        Lev L;
+        L.tr_off = (int)ent.size();
+        for (int r = r0; r < r1; r++) for (int y = 0; y * SEL_T < rec[r].ncol; y++) ent.push_back(int4{ r, y, 0, 0 });
+        L.n_tr = (int)ent.size() - L.tr_off;
+        L.gm_off = (int)ent.size();
+        for (int r = r0; r < r1; r++)
+            if (rec[r].parent >= 0)
+                for (int y = 0; y * SEL_T < rec[r].ncol; y++) for (int i = 0; i * SEL_T < rec[r].u; i++) ent.push_back(int4{ r, i, y, 0 });
+        L.n_gm = (int)ent.size() - L.gm_off;
+        lev.push_back(L);
+        r0 = r1;
+    }
+    for (int t : touched) S.rec[t] = -1;
+    if (ent.empty()) ent.push_back(int4{ 0, 0, 0, 0 });
+    S.d_fr.need(std::max<size_t>(1, rec.size())); S.d_ent.need(ent.size()); S.d_cmap.need(cmap.size()); S.d_at.need(at.size());
+    S.d_path.need(path.size()); S.d_pair.need(pairs.size()); S.d_buf.need((size_t)std::max(used, 1ll));
+    S.peak_doubles = std::max(S.peak_doubles, used);
+    HIPCHECK(hipMemcpyAsync(S.d_fr.p, rec.data(), rec.size() * sizeof(PsFront), hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(S.d_ent.p, ent.data(), ent.size() * sizeof(int4), hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(S.d_cmap.p, cmap.data(), cmap.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(S.d_at.p, at.data(), at.size() * 8, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(S.d_path.p, path.data(), path.size() * sizeof(PsPath), hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(S.d_pair.p, pairs.data(), pairs.size() * sizeof(PsPair), hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemsetAsync(S.d_buf.p, 0, (size_t)used * 8, s));
+    const PsFront *dfr = S.d_fr.p; const int4 *de = S.d_ent.p; const double *pool = c.d_pool.p; double *buf = S.d_buf.p;
+    hipLaunchKernelGGL(k_path_init, dim3((unsigned)((at.size() + 255) / 256)), dim3(256), 0, s, (int)at.size(), (const long long *)S.d_at.p, buf);
+    auto waves = [](int n) { return dim3((unsigned)((n + 3) / 4)); };
+    for (const Lev &L : lev) {
+        if (L.n_tr) hipLaunchKernelGGL(k_path_trsm, waves(L.n_tr), dim3(256), 0, s, dfr, de + L.tr_off, L.n_tr, pool, buf);
+        if (L.n_gm) hipLaunchKernelGGL(k_path_gemm, waves(L.n_gm), dim3(256), 0, s, dfr, de + L.gm_off, L.n_gm, pool, (const int *)c.d_i32.p,
+                                       (const int *)S.d_cmap.p, buf);
+    }
+    hipLaunchKernelGGL(k_path_gram, dim3((unsigned)pairs.size()), dim3(256), 0, s, (const PsPair *)S.d_pair.p, (const PsPath *)S.d_path.p,
+                       (const double *)buf, S.d_cov.p, S.h_out.p);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(s));                      // (the host tables go out of scope; the next chunk reuses the buffers)
+}
+
+// the doubles of work buffer one chunk may take: 1 GB, or option mem_cap_mb (the limit on any single device buffer)
+static long long ps_budget() {
+    const long long dflt = 1ll << 27;
+    return g_opt.mem_cap_mb > 0 ? std::min(dflt, ((long long)g_opt.mem_cap_mb << 20) / 8) : dflt;
+}
+
+// joint blocks of the n pairs (qa, qb) into S.d_cov / S.h_out (36 per pair); gate != null: then the gate of candidate i, in = 18
+// doubles each (k_gate_xyt), its d2 and S behind the blocks in S.h_out.
+static void ps_run(Context &c, hipStream_t s, int n, const int *qa, const int *qb, const double *gate_in) {
+    ps_fronts(c);
+    PathState &S = c.ps;
+    S.d_cov.need((size_t)36 * n);
+    S.h_out.need((size_t)(gate_in ? 46 : 36) * n);
+    const long long budget = ps_budget();
+    if ((int)S.node_j.size() != S.N) S.node_j.assign((size_t)S.N, -1);
+    std::vector<int> nodes; std::vector<int2> pj;
+    long long used = 0;
+    int first = 0;
+    auto flush = [&](int end) {
+        if (!pj.empty()) ps_chunk(c, s, nodes, pj, first);
+        for (int q : nodes) S.node_j[q] = -1;
+        nodes.clear(); pj.clear(); used = 0; first = end;
+    };
+    try {
+    for (int i = 0; i < n; i++) {
+        long long add = 0;
+        if (S.node_j[qa[i]] < 0) add += ps_path_doubles(S, qa[i]);
+        if (qb[i] != qa[i] && S.node_j[qb[i]] < 0) add += ps_path_doubles(S, qb[i]);
+        if (!pj.empty() && used + add > budget) flush(i);
+        for (int q : { qa[i], qb[i] })
+            if (S.node_j[q] < 0) { S.node_j[q] = (int)nodes.size(); nodes.push_back(q); used += ps_path_doubles(S, q); }
+        pj.push_back(int2{ S.node_j[qa[i]], S.node_j[qb[i]] });
+    }
+    flush(n);
+    } catch (...) {                                         // (the maps are rebuilt by the next call)
+        S.node_j.clear(); S.serial = -1;
+        throw;
+    }
+    if (gate_in) {
+        S.d_in.need((size_t)18 * n);
+        HIPCHECK(hipMemcpyAsync(S.d_in.p, gate_in, (size_t)8 * 18 * n, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_gate_xyt, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, (const double *)S.d_in.p, (const double *)S.d_cov.p,
+                           S.h_out.p + (size_t)36 * n);
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipStreamSynchronize(s));
+    }
+}
+
+static int gate_refuse(int code, const char *msg) {
+    set_last_error(code, msg); fprintf(stderr, "aprilsam_amd: ERROR %d: %s\n", code, msg); fflush(stderr); return code;
+}
+
+// the checks aprilsam_amd_marginals makes (solver_marginals.inc.h), in the same order; 0 and the context, or the code
+static int ps_context(april_graph_cholesky_param_t *param, const char *who, Context *&out) {
+    char msg[256];
+    if (g_shard.find(param) != g_shard.end()) { snprintf(msg, sizeof msg, "%s: sharded params are not supported", who); return gate_refuse(ERR_UNSUPPORTED, msg); }
+    auto it = g_ctx.find(param);
+    if (it == g_ctx.end() || !it->second->have_fact || it->second->st.not_spd || it->second->fact_kind == FACT_NONE || it->second->fact_epoch != it->second->epoch_steps) {
+        snprintf(msg, sizeof msg, "%s: no retained factor (no successful solver call since the param was created or last failed)", who);
+        return gate_refuse(-1, msg);
+    }
+    if (it->second->fact_asym) {
+        snprintf(msg, sizeof msg, "%s: the factorised graph holds factors with an asymmetric information matrix", who);
+        return gate_refuse(ERR_UNSUPPORTED, msg);
+    }
+    out = &*it->second;
+    return 0;
+}
+
+static int joint_any_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *qa, const int *qb, double *cov) {
+    (void)g;
+    const char *who = "aprilsam_amd_marginals_joint_any";
+    if (!param || !cov || !qa || !qb || n < 0) return gate_refuse(ERR_BAD_GRAPH, "aprilsam_amd_marginals_joint_any: null argument or negative count");
+    ensure_device();
+    SlotLock lk(param, g);
+    Context *cp = nullptr;
+    if (int rc = ps_context(param, who, cp)) return rc;
+    Context &c = *cp;
+    const int N = c.fact_kind == FACT_EXTENDED ? c.inc_N : c.plan.N;
+    for (int i = 0; i < n; i++)
+        if (qa[i] < 0 || qa[i] >= N || qb[i] < 0 || qb[i] >= N)
+            return gate_refuse(ERR_BAD_GRAPH, "aprilsam_amd_marginals_joint_any: node id out of range of the factorised system (nodes added since the last solver call?)");
+    if (n == 0) return 0;
+    hipStream_t s = take_stream(t_slot);
+    struct Park { int slot; hipStream_t s; ~Park() { park_stream(slot, s); } } park{ t_slot, s };
+    ps_run(c, s, n, qa, qb, nullptr);
+    memcpy(cov, c.ps.h_out.p, (size_t)8 * 36 * n);
+    return 0;
+}
+
+static int gate_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *qa, const int *qb, const double *z, const double *W,
+                     double *d2, double *Sout) {
+    const char *who = "aprilsam_amd_gate_xyt";
+    if (!g || !param || !qa || !qb || !z || !W || !d2 || n < 0) return gate_refuse(ERR_BAD_GRAPH, "aprilsam_amd_gate_xyt: null argument or negative count");
+    ensure_device();
+    SlotLock lk(param, g);
+    Context *cp = nullptr;
+    if (int rc = ps_context(param, who, cp)) return rc;
+    Context &c = *cp;
+    const int N = c.fact_kind == FACT_EXTENDED ? c.inc_N : c.plan.N, Ng = zsize(g->nodes);
+    for (int i = 0; i < n; i++) {
+        if (qa[i] < 0 || qa[i] >= N || qb[i] < 0 || qb[i] >= N || qa[i] >= Ng || qb[i] >= Ng)
+            return gate_refuse(ERR_BAD_GRAPH, "aprilsam_amd_gate_xyt: node id out of range of the factorised system (nodes added since the last solver call?)");
+        if (qa[i] == qb[i]) return gate_refuse(ERR_BAD_GRAPH, "aprilsam_amd_gate_xyt: a candidate joins a node to itself");
+        for (int k = 0; k < 3; k++) if (!std::isfinite(z[3 * i + k])) return gate_refuse(ERR_BAD_GRAPH, "aprilsam_amd_gate_xyt: a non-finite measurement");
+        for (int k = 0; k < 9; k++) if (!std::isfinite(W[9 * i + k])) return gate_refuse(ERR_BAD_GRAPH, "aprilsam_amd_gate_xyt: a non-finite information matrix");
+    }
+    for (int i = 0; i < n; i++) {                           // symmetric (mirror entries equal) and positive definite: a Cholesky factorisation
+        const double *w = W + 9 * i;
+        bool ok = w[1] == w[3] && w[2] == w[6] && w[5] == w[7];
+        const double l00 = w[0] > 0 ? sqrt(w[0]) : 0;
+        ok = ok && l00 > 0;
+        const double l10 = ok ? w[3] / l00 : 0, l20 = ok ? w[6] / l00 : 0, p1 = w[4] - l10 * l10;
+        ok = ok && p1 > 0;
+        const double l11 = ok ? sqrt(p1) : 0, l21 = ok ? (w[7] - l20 * l10) / l11 : 0, p2 = w[8] - l20 * l20 - l21 * l21;
+        ok = ok && p2 > 0;
+        if (!ok) return gate_refuse(ERR_UNSUPPORTED, "aprilsam_amd_gate_xyt: an information matrix that is not symmetric positive definite");
+    }
+    if (n == 0) return 0;
+    std::vector<double> in((size_t)18 * n);
+    april_graph_node_t **ns = (april_graph_node_t **)g->nodes->data;
+    for (int i = 0; i < n; i++) {
+        double *q = in.data() + (size_t)18 * i;
+        for (int k = 0; k < 3; k++) { q[k] = ns[qa[i]]->state[k]; q[3 + k] = ns[qb[i]]->state[k]; q[6 + k] = z[3 * i + k]; }
+        for (int k = 0; k < 9; k++) q[9 + k] = W[9 * i + k];
+    }
+    hipStream_t s = take_stream(t_slot);
+    struct Park { int slot; hipStream_t s; ~Park() { park_stream(slot, s); } } park{ t_slot, s };
+    ps_run(c, s, n, qa, qb, in.data());
+    const double *o = c.ps.h_out.p + (size_t)36 * n;
+    memcpy(d2, o, (size_t)8 * n);
+    if (Sout) memcpy(Sout, o + n, (size_t)8 * 9 * n);
+    return 0;
+}
+
+// As marginals: a failed call only reads the param's plan and factor, records the error and leaves both in place.
+template <class F> static int ps_guard(F f) {
+    try { return f(); }
+    catch (const SolverError &e) { set_last_error(e.code, e.msg); fprintf(stderr, "aprilsam_amd: ERROR %d: %s\n", e.code, e.msg.c_str()); fflush(stderr); (void)hipGetLastError(); return e.code; }
+    catch (const std::bad_alloc &) { set_last_error(ERR_OOM, "host memory exhausted (std::bad_alloc)"); return ERR_OOM; }
+    catch (const std::exception &e) { set_last_error(ERR_INTERNAL, e.what()); return ERR_INTERNAL; }
+}
+int marginals_joint_any(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, double *cov) {
+    return ps_guard([&] { return joint_any_impl(g, param, n, a, b, cov); });
+}
+int gate_xyt(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, const double *z, const double *W, double *d2, double *S) {
+    return ps_guard([&] { return gate_impl(g, param, n, a, b, z, W, d2, S); });
+}
+long long path_solve_bytes(const april_graph_cholesky_param_t *param) {
+    SlotLock lk(param, nullptr);
+    auto it = g_ctx.find(param);
+    return it == g_ctx.end() ? -1 : 8 * it->second->ps.peak_doubles;
+}

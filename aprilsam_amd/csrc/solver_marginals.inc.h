@@ -6,16 +6,19 @@
 // plan with the incremental path's appended tail fronts and regenerated descriptors (FACT_EXTENDED: Context::inc -- descriptors,
 // current parents, block maps and tail rows in the device arena d_i32, exactly what the factorisation read).  Fronts are grouped by
 // their depth below the root: a front's parent is always one group earlier.
-static void build_sel_tables(Context &c, hipStream_t s) {
+// The fronts of that structure (SelFront, without the scratch offsets), their depth below the root, the end of the pool they occupy, the
+// estimated flops of the inversion, and i32 = pos | pos_front (node -> elimination position, position -> owning front) of its N nodes.
+// Shared with the path solves of solver_gating.inc.h.  Returns N.
+static int sel_fronts(Context &c, std::vector<SelFront> &fr, std::vector<int> &depth, std::vector<int> &i32, long long &pool_end, double &flops) {
     const Plan &P = c.plan; const IncState &I = c.inc;
     const bool ext = c.fact_kind == FACT_EXTENDED;
     const int nF0 = P.nF, nFr = ext ? I.nF0 + (int)I.t_first.size() : P.nF, N = ext ? c.inc_N : P.N;
     if (ext && (I.nF0 != P.nF || I.Nb != P.N || (int)I.fd.size() < nFr || (int)I.parent.size() < nFr || (int)I.E.size() < nFr || (int)I.rel_begin.size() < nFr))
         fail(ERR_INTERNAL, "aprilsam_amd_marginals: incremental bookkeeping does not match the plan");
-    c.sel_flops = 0;
-    std::vector<SelFront> fr((size_t)nFr);
-    std::vector<int> depth((size_t)nFr, 0);
-    long long pool_end = 1;
+    flops = 0;
+    fr.assign((size_t)nFr, SelFront());
+    depth.assign((size_t)nFr, 0);
+    pool_end = 1;
     for (int t = nFr - 1; t >= 0; t--) {
         SelFront &F = fr[t];
         int nsb, nub, nub_real, parent;
@@ -34,15 +37,22 @@ static void build_sel_tables(Context &c, hipStream_t s) {
         F.s = 3 * nsb; F.u = 3 * nub_real; F.R = 3 * (nsb + nub + 1); F.parent = parent; F.nsb = nsb;
         depth[t] = parent < 0 ? 0 : depth[parent] + 1;
         pool_end = std::max(pool_end, F.off + (long long)F.R * 3 * (nsb + nub));
-        c.sel_flops += 2.0 * F.u * F.u * F.s + (double)F.u * F.s * F.s + (double)F.s * F.s * F.s / 3.0;
+        flops += 2.0 * F.u * F.u * F.s + (double)F.u * F.s * F.s + (double)F.s * F.s * F.s / 3.0;
     }
-    const int nLev = nFr ? *std::max_element(depth.begin(), depth.end()) + 1 : 0;
-    std::vector<std::vector<int>> lev((size_t)nLev);
-    for (int t = 0; t < nFr; t++) lev[depth[t]].push_back(t);
-    std::vector<int> i32((size_t)2 * N);                    // pos | pos_front
+    i32.assign((size_t)2 * N, 0);                           // pos | pos_front
     for (int i = 0; i < N; i++) i32[i] = i < P.N ? P.pos[i] : i;                 // (a tail pose's position is its id)
     for (int t = 0; t < nF0; t++) for (int q = P.f_first[t]; q < P.f_first[t] + P.f_nsb[t]; q++) i32[N + q] = t;
     for (int q = P.N; q < N; q++) i32[N + q] = I.tf_of[q - P.N];
+    return N;
+}
+
+// the selected inversion's work entries, level by level (root first), and its scratch
+static void build_sel_tables(Context &c, hipStream_t s) {
+    std::vector<SelFront> fr; std::vector<int> depth, i32; long long pool_end;
+    const int N = sel_fronts(c, fr, depth, i32, pool_end, c.sel_flops), nFr = (int)fr.size();
+    const int nLev = nFr ? *std::max_element(depth.begin(), depth.end()) + 1 : 0;
+    std::vector<std::vector<int>> lev((size_t)nLev);
+    for (int t = 0; t < nFr; t++) lev[depth[t]].push_back(t);
     std::vector<int4> ent;
     c.sel_levels.assign(nLev, SelLevel());
     long long scr_max = 16;

@@ -108,6 +108,11 @@ class SolverLib:
                 d.aprilsam_amd_marginals_joint.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.c_int, _ip, _ip, _dp]
                 d.aprilsam_amd_debug_selinv_runs.argtypes = [C.POINTER(abi.CholeskyParam)]
                 d.aprilsam_amd_debug_selinv_runs.restype = C.c_longlong
+            if hasattr(d, "aprilsam_amd_marginals_joint_any"):    # (defined in the HIP translation unit)
+                d.aprilsam_amd_marginals_joint_any.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.c_int, _ip, _ip, _dp]
+                d.aprilsam_amd_gate_xyt.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.c_int, _ip, _ip, _dp, _dp, _dp, _dp]
+                d.aprilsam_amd_debug_path_solve_bytes.argtypes = [C.POINTER(abi.CholeskyParam)]
+                d.aprilsam_amd_debug_path_solve_bytes.restype = C.c_longlong
             if hasattr(d, "aprilsam_amd_factor_max_create"):
                 d.aprilsam_amd_factor_max_create.restype = C.POINTER(abi.Factor)
                 d.aprilsam_amd_factor_max_create.argtypes = [C.POINTER(C.POINTER(abi.Factor)), _dp, C.c_int]
@@ -447,6 +452,35 @@ class Graph:
         if rc < 0:
             raise MarginalsError(rc, self.lib.last_error())
         return out
+
+    def marginals_joint_any(self, param, a, b):
+        """[n, 6, 6] joint covariances of the pairs (a[i], b[i]), a's unknowns first, for ANY pairs (a == b allowed), by triangular
+        solves along the factor's assembly-tree paths (include/aprilsam_amd.h: aprilsam_amd_marginals_joint_any).  Raises
+        MarginalsError(rc) on a negative return."""
+        a = np.ascontiguousarray(a, dtype=np.int32).ravel(); b = np.ascontiguousarray(b, dtype=np.int32).ravel()
+        if a.shape != b.shape:
+            raise ValueError("a and b must have the same length")
+        out = np.empty((len(a), 6, 6))
+        rc = self.lib.dll.aprilsam_amd_marginals_joint_any(self.ptr, param.ptr, len(a), _np_i(a), _np_i(b), _np_d(out))
+        if rc < 0:
+            raise MarginalsError(rc, self.lib.last_error())
+        return out
+
+    def gate_xyt(self, param, a, b, z, W):
+        """Mahalanobis gating of candidate xyt measurements z[i] (3) with information W[i] (3 x 3) between a[i] and b[i]: returns
+        d2 [n] = r' S^-1 r and the innovation covariance S [n, 3, 3] (include/aprilsam_amd.h: aprilsam_amd_gate_xyt).  The residual is
+        taken at the nodes' states, the covariance at the last solver call's linearisation points.  Raises MarginalsError(rc) on a
+        negative return."""
+        a = np.ascontiguousarray(a, dtype=np.int32).ravel(); b = np.ascontiguousarray(b, dtype=np.int32).ravel()
+        n = len(a)
+        z = np.ascontiguousarray(z, dtype=float).reshape(n, 3); W = np.ascontiguousarray(W, dtype=float).reshape(n, 9)
+        if b.shape != a.shape:
+            raise ValueError("a and b must have the same length")
+        d2 = np.empty(n); S = np.empty((n, 3, 3))
+        rc = self.lib.dll.aprilsam_amd_gate_xyt(self.ptr, param.ptr, n, _np_i(a), _np_i(b), _np_d(z), _np_d(W), _np_d(d2), _np_d(S))
+        if rc < 0:
+            raise MarginalsError(rc, self.lib.last_error())
+        return d2, S
 
     def batch_resident(self, param, iters):
         chi2 = np.zeros(iters + 1); ms = np.zeros(iters)

@@ -431,6 +431,31 @@ int aprilsam_amd_marginals_joint(april_graph_t *graph, april_graph_cholesky_para
 /* debug: number of selected inversions run on this param so far (-1: no context) */
 long long aprilsam_amd_debug_selinv_runs(const april_graph_cholesky_param_t *param);
 
+/* ---- joint covariances of any pose pair, and gating of candidate measurements ---------------------------
+ * Joint covariance [[S_aa S_ab]; [S_ba S_bb]] of ANY pairs (36 doubles per pair, row-major, a's unknowns first; a == b allowed), of the
+ * same system as aprilsam_amd_marginals: the inverse of the system the last successful solver call on `param` factorised (lambda where
+ * the step put it, evaluated at the nodes' l_point), read from the retained factor.  Every value is finite, whatever the pattern of L:
+ * S_ab = (L^-1 E_a)' (L^-1 E_b) by triangular solves along the assembly-tree paths of the two poses on the GPU (no selected inversion
+ * runs, no Sigma pool is allocated; the work buffer is chunked to at most 1 GB, or to option mem_cap_mb).  Returns 0, or the codes of
+ * aprilsam_amd_marginals (-1 no retained factor or a resident run in progress; -12 sharded param or asymmetric W in the factorised graph;
+ * -13 a node id out of range or a null argument; -14 no HIP device).  A failed call writes nothing and changes nothing.  Two calls give
+ * the same bits.  aprilsam_amd_marginals_joint keeps its NaN for pairs off the pattern. */
+int aprilsam_amd_marginals_joint_any(april_graph_t *graph, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, double *cov);
+/* Mahalanobis gating of n candidate xyt measurements: z[3i..] (x, y, theta of b in a's frame) with information W[9i..] (row-major)
+ * between nodes a[i] and b[i].  Per candidate, on the GPU right after the path solves:
+ *     r, J_a, J_b   residual and Jacobians exactly as an xyt factor computes them (theta wrapped), at the nodes' CURRENT state
+ *                   (what graph holds now: after a solver call, the updated states)
+ *     S  = [J_a J_b] Sigma_ab [J_a J_b]' + W^-1     Sigma_ab: aprilsam_amd_marginals_joint_any's block, i.e. at the l_points of the
+ *                                                  last solver call
+ *     d2 = r' S^-1 r      (compare with a chi^2 quantile of 3 degrees of freedom: 16.27 at 0.999)
+ * d2: n doubles; S: 9 n doubles (row-major) or NULL.  Returns 0, or the codes above, and: -12 a W that is not symmetric (mirror entries
+ * bitwise equal) positive definite; -13 a == b, a non-finite z or W, a node id out of range of the factorised system or of graph, a null
+ * argument.  Nothing is written on a refusal. */
+int aprilsam_amd_gate_xyt(april_graph_t *graph, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, const double *z,
+                          const double *W, double *d2, double *S);
+/* debug: the largest path-solve work buffer this param has used, in bytes (-1: no context) */
+long long aprilsam_amd_debug_path_solve_bytes(const april_graph_cholesky_param_t *param);
+
 /* ---- max-mixture factors (Olson & Agarwal, RSS 2012) ---------------------------------------------------
  * A max factor on the ordered pair (a, b) holds K = 1..8 components, each an xyt factor made by april_graph_factor_xyt_create on
  * the same (a, b) with a symmetric W of det W > 0, and a log weight per component.  At a point p component i scores
