@@ -87,6 +87,24 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+
+class LmOpts(C.Structure):
+    """aprilsam_amd_lm_opts_t (include/aprilsam_amd.h)"""
+    _fields_ = [("max_iters", C.c_int), ("check_every", C.c_int), ("lambda0", C.c_double), ("lambda_max", C.c_double),
+                ("eta", C.c_double), ("ftol", C.c_double), ("xtol", C.c_double)]
+
+
+class LmReport(C.Structure):
+    """aprilsam_amd_lm_report_t"""
+    _fields_ = [("status", C.c_int), ("iterations", C.c_int), ("accepted", C.c_int), ("rejected_not_spd", C.c_int),
+                ("F_initial", C.c_double), ("F_final", C.c_double), ("chi2_final", C.c_double), ("lambda_final", C.c_double)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+LM_CONVERGED_F, LM_CONVERGED_X, LM_STALLED, LM_MAX_ITERS = 1, 2, 3, 4
+
 # measured LP64 layout of the reference (SURVEY.md §8(b)); checked by tests/test_abi.py
 EXPECTED_SIZES = {"ZArray": 24, "Graph": 32, "Factor": 104, "Node": 112, "CholeskyParam": 128}
 EXPECTED_OFFSETS = {

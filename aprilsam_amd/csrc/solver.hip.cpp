@@ -28,6 +28,7 @@
 #include "errors.h"
 #include "kernels.hip.h"
 #include "maxmix.hip.h"
+#include "lm.hip.h"
 #include "selinv.hip.h"
 #include "pathsolve.hip.h"
 #include "plan.h"
@@ -243,6 +244,7 @@ struct PatchList {
 #include "solver_shard.inc.h"
 #include "solver_marginals.inc.h"
 #include "solver_gating.inc.h"
+#include "solver_lm.inc.h"
 
 // ------------------------------------------------------------------------------------------------------
 // Runtime warm-up, once per process, from april_graph_cholesky_param_init (the API's set-up call; aprilsam.c:45-64 has nothing to set up).
@@ -468,3 +470,8 @@ extern "C" int aprilsam_amd_gate_xyt(april_graph_t *graph, april_graph_cholesky_
     return asam::gate_xyt(graph, param, n, a, b, z, W, d2, S);
 }
 extern "C" long long aprilsam_amd_debug_path_solve_bytes(const april_graph_cholesky_param_t *param) { return asam::path_solve_bytes(param); }
+extern "C" void aprilsam_amd_lm_opts_init(aprilsam_amd_lm_opts_t *opts) { asam::lm_opts_init(opts); }
+extern "C" int aprilsam_amd_optimize_lm(april_graph_t *graph, april_graph_cholesky_param_t *param, const aprilsam_amd_lm_opts_t *opts,
+                                        aprilsam_amd_lm_report_t *report, double *trace) {
+    return asam::optimize_lm(graph, param, opts, report, trace);
+}

@@ -152,6 +152,10 @@ struct Context {
     // writes new states / dx / pivot flag back to pinned mirrors -- one graph launch + one stream sync per call
     hipGraphExec_t gexec_api = nullptr;
     const void *api_key[8] = {};
+    // Levenberg-Marquardt (solver_lm.inc.h): one iteration captured as its own graph, keyed like gexec plus the LM buffers it reads
+    hipGraphExec_t gexec_lm = nullptr;
+    const void *lm_key[8] = {};
+    DBuf<double> d_lm_trial, d_lm_hacc, d_lm_terms, d_lm_trace; DBuf<LmScalars> d_lm; HBuf<LmScalars> h_lm;
     int api_key_runs = 0;                          // calls seen with this key: the first one runs without a graph (below)
     // captured graphs that are no longer current: hipGraphExecDestroy takes 0.24 ms on this stack, so they are destroyed while the
     // GPU works on a step (reap_retired), not on the way to the next plan
@@ -201,7 +205,8 @@ struct Context {
         d_i32.release(); d_fd.release(); d_dest.release(); d_child.release(); d_lambda.release(); d_tab.release(); d_swap.release(); d_pos.release();
         d_pool.release(); d_H.release(); d_x.release(); d_diag.release(); d_bad.release(); h_bad.release(); patches.release();
         h_done.release(); h_kstamp.release(); d_prof.release(); d_upd.release(); d_wbuf.release(); d_flags.release(); d_flevel.release(); d_epoch.release(); d_marks.release(); d_perm.release(); d_solve_tab.release(); d_dinv.release(); d_bsb_far.release(); d_bsb_flags.release(); d_guard.release(); d_guard_cnt.release(); n_guard = 0;
-        retire(gexec); retire(gexec_api); reap_retired(true);
+        d_lm_trial.release(); d_lm_hacc.release(); d_lm_terms.release(); d_lm_trace.release(); d_lm.release(); h_lm.release();
+        retire(gexec); retire(gexec_api); retire(gexec_lm); reap_retired(true);
         if (have_events) for (auto &e : ev) (void)hipEventDestroy(e);
         have_events = false;
         for (auto &e : k_ev) (void)hipEventDestroy(e);
@@ -479,7 +484,7 @@ static void upload_plan(Context &c, hipStream_t s, const ShardLayout *lay = null
     const Plan &P = c.plan;
     const bool uprof = getenv("APRILSAM_AMD_PLAN_PROFILE") != nullptr;
     const double u0 = uprof ? now_ms() : 0;
-    c.retire(c.gexec); c.retire(c.gexec_api); c.api_key_runs = 0;
+    c.retire(c.gexec); c.retire(c.gexec_api); c.retire(c.gexec_lm); c.api_key_runs = 0;
     c.lambda_N = -1;
     c.release_sel();                          // (Sigma and its tables describe the plan being replaced)
     // ---- descriptors + index arrays ----------------------------------------------------------------------------
@@ -796,7 +801,9 @@ static void enqueue_factor_level(Context &c, const LevelPlan &L, hipStream_t s, 
 // enqueue: linearise -> per level {assemble+factor} -> back substitution -> state update
 // ev != null: record stage events (0 start, 1 after linearise, 2 after factor, 3 after solve+update)
 // ktime: bracket EVERY kernel launch with its own HIP event pair on this stream (c.k_ev / c.k_ids)
-static void enqueue_numeric(Context &c, GraphPack &gp, hipStream_t s, hipEvent_t *ev, bool unary_at_lp = false, bool ktime = false, bool io_host = false, bool relin = false) {
+// st_dest (LM iterations, solver_lm.inc.h): where the state update writes x (+) h instead of d_state -- the trial buffer
+static void enqueue_numeric(Context &c, GraphPack &gp, hipStream_t s, hipEvent_t *ev, bool unary_at_lp = false, bool ktime = false, bool io_host = false, bool relin = false,
+                            double *st_dest = nullptr) {
     const Plan &P = c.plan;
     const int F = P.F, N = P.N;
     size_t nev = 0;
@@ -838,7 +845,7 @@ static void enqueue_numeric(Context &c, GraphPack &gp, hipStream_t s, hipEvent_t
     if (ev) HIPCHECK(hipEventRecord(ev[2], s));
     // the state update of a front's own poses rides on its back substitution (no kernel of its own); the last launch also
     // mirrors the pivot flag for the API call
-    UpdArgs upd{ c.d_perm.p, gp.d_lp.p, gp.d_state.p, gp.d_dx.p, io_host ? gp.h_lp.p : nullptr, io_host ? gp.h_dx.p : nullptr, nullptr, relin ? gp.d_lp.p : nullptr };
+    UpdArgs upd{ c.d_perm.p, gp.d_lp.p, st_dest ? st_dest : gp.d_state.p, gp.d_dx.p, io_host ? gp.h_lp.p : nullptr, io_host ? gp.h_dx.p : nullptr, nullptr, relin ? gp.d_lp.p : nullptr };
     if (l0 < P.nLevels) {
         UpdArgs u = upd; if (l0 == 0) u.bad_out = io_host ? c.h_bad.p : nullptr;
         tic(K_BACKSOLVE);

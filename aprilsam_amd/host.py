@@ -42,6 +42,14 @@ class MarginalsError(RuntimeError):
         self.code = code
 
 
+class LMError(RuntimeError):
+    """a negative return of aprilsam_amd_optimize_lm: .code is the return value"""
+
+    def __init__(self, code, msg=None):
+        super().__init__(f"optimize_lm failed: {code} {msg or ''}".strip())
+        self.code = code
+
+
 class SolverLib:
     """A loaded shared library exporting the reference API names."""
 
@@ -113,6 +121,11 @@ class SolverLib:
                 d.aprilsam_amd_gate_xyt.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.c_int, _ip, _ip, _dp, _dp, _dp, _dp]
                 d.aprilsam_amd_debug_path_solve_bytes.argtypes = [C.POINTER(abi.CholeskyParam)]
                 d.aprilsam_amd_debug_path_solve_bytes.restype = C.c_longlong
+            if hasattr(d, "aprilsam_amd_optimize_lm"):          # (defined in the HIP translation unit)
+                d.aprilsam_amd_lm_opts_init.argtypes = [C.POINTER(abi.LmOpts)]
+                d.aprilsam_amd_lm_opts_init.restype = None
+                d.aprilsam_amd_optimize_lm.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.POINTER(abi.LmOpts),
+                                                       C.POINTER(abi.LmReport), _dp]
             if hasattr(d, "aprilsam_amd_factor_max_create"):
                 d.aprilsam_amd_factor_max_create.restype = C.POINTER(abi.Factor)
                 d.aprilsam_amd_factor_max_create.argtypes = [C.POINTER(C.POINTER(abi.Factor)), _dp, C.c_int]
@@ -481,6 +494,28 @@ class Graph:
         if rc < 0:
             raise MarginalsError(rc, self.lib.last_error())
         return d2, S
+
+    def optimize_lm(self, param, trace=False, **opts):
+        """Levenberg-Marquardt on the GPU until a stop test holds (include/aprilsam_amd.h: aprilsam_amd_optimize_lm).
+        opts: fields of aprilsam_amd_lm_opts_t (max_iters, check_every, lambda0, lambda_max, eta, ftol, xtol), defaults for the rest.
+        Returns the report's fields as a dict, plus "trace": an (iterations, 4) array (F at the trial point, rho, lambda used,
+        accepted) when trace is true.  Raises LMError(rc) on a negative return."""
+        o = abi.LmOpts()
+        self.lib.dll.aprilsam_amd_lm_opts_init(C.byref(o))
+        for k, v in opts.items():
+            if k not in dict(abi.LmOpts._fields_):
+                raise TypeError(f"unknown LM option {k}")
+            setattr(o, k, v)
+        rep = abi.LmReport()
+        tr = np.full((max(int(o.max_iters), 1), 4), np.nan) if trace else None
+        rc = self.lib.dll.aprilsam_amd_optimize_lm(self.ptr, param.ptr if param is not None else None, C.byref(o), C.byref(rep),
+                                                   _np_d(tr) if trace else None)
+        if rc < 0:
+            raise LMError(rc, self.lib.last_error())
+        out = rep.asdict()
+        if trace:
+            out["trace"] = tr[:rep.iterations].copy()
+        return out
 
     def batch_resident(self, param, iters):
         chi2 = np.zeros(iters + 1); ms = np.zeros(iters)

@@ -456,6 +456,59 @@ int aprilsam_amd_gate_xyt(april_graph_t *graph, april_graph_cholesky_param_t *pa
 /* debug: the largest path-solve work buffer this param has used, in bytes (-1: no context) */
 long long aprilsam_amd_debug_path_solve_bytes(const april_graph_cholesky_param_t *param);
 
+/* ---- Levenberg-Marquardt optimisation -------------------------------------------------------------------
+ * The reference has no counterpart: april_graph_cholesky is one Gauss-Newton step with the fixed damping param->tikhanov, and the
+ * drop-in entry points keep exactly that.  aprilsam_amd_optimize_lm runs a whole damped optimisation on the GPU, every iteration one
+ * captured graph; the accept / reject decision is made on the device and the host only polls a small status block.
+ *   Objective  F(x) = sum_f r_f' W_f r_f over all factors, NO 0.5 factor: the cost the normal equations (sum J'WJ + D) h = sum J'W r
+ *              minimise (april_graph_chi2 halves xyt terms and would not match the model).  A max factor contributes
+ *              min_k (r_k' W_k r_k + c_k), c_k = -2 log w_k - ln det W_k: the score its selection minimises.
+ *   Damping    D = lambda on every pose, written into the device's damping array by the device.  param->tikhanov is the reference's
+ *              fixed Tikhonov term of the plain step; the LM run ignores it (it would bound the damping from below).
+ *   Iteration  at the current point x (state = l_point = x, so xytpos priors linearise at the same point):
+ *              1. select the max-factor components at x;  2. linearise, assemble, factor, back-substitute (the existing kernels); the
+ *              update goes to a trial buffer, x_t = x (+) h, theta wrapped;  3. F(x_t);  4. the model decrease
+ *              pred = sum_f [r_f' W_f r_f - (r_f - d_f)' W_f (r_f - d_f)] = sum_f d_f' W_f (2 r_f - d_f), d_f = J_a h_a + J_b h_b, at x
+ *              with the selected slot's z and W (it equals h'B + lambda |h|^2);  5. rho = (F(x) - F(x_t)) / pred.
+ *   Rejection  a pivot that was not positive, a NaN in h or a non-finite F(x_t) rejects the step (rejected_not_spd counts the first).
+ *   Decision   (Nielsen) rho > eta: x <- x_t, lambda <- lambda * max(1/3, 1 - (2 rho - 1)^3), nu <- 2; otherwise lambda <- lambda * nu,
+ *              nu <- 2 nu.  pred <= 0 on a step that was not rejected: converged (status CONVERGED_F).  After an accepted step the
+ *              ftol test, then the xtol test; lambda > lambda_max: STALLED; max_iters iterations: MAX_ITERS.
+ *   Determinism  once a stop condition holds, every later iteration of the same chunk of check_every iterations is a no-op (a device
+ *              latch): results and trace are bitwise the same for every check_every, and two runs give identical bits.
+ * What the call leaves: state = l_point = x*, the last accepted iterate (x0 if none); delta_X = the last accepted h (untouched if none);
+ * param->tikhanov untouched; the param's plan kept; the retained factor DROPPED (it was made at another point with another lambda):
+ * aprilsam_amd_marginals* / aprilsam_amd_gate_xyt return -1 and the next april_graph_cholesky_inc behaves as on a fresh param.  For
+ * covariances at the optimum call april_graph_cholesky once, then aprilsam_amd_marginals.
+ * Returns 0 (reason in report->status), or: -1 empty graph; -4 the graph holds host-evaluated (foreign) factors; -12 sharded param, or
+ * a factor with an asymmetric information matrix; -13 bad options or a null argument; -14 no HIP device.  On a refusal nothing is
+ * written and the graph is untouched; aprilsam_amd_last_error says why.  A failure during the run fails the call as on every solver
+ * entry point (see the error codes above): -9 when a multi-level launch of an iteration gave up waiting for a dependency flag (never
+ * taken for a rejected step), -10 / -11 for HIP errors / memory; the graph is untouched and the param's plan and captured graphs are
+ * dropped. */
+typedef struct {
+    int    max_iters;     /* >= 1, default 50: LM iterations (accepted + rejected) */
+    int    check_every;   /* >= 1, default 1: the host reads the status after this many iterations; results never depend on it */
+    double lambda0;       /* > 0, default 1e-4: initial damping */
+    double lambda_max;    /* default 1e16: damping above this ends the run, status STALLED */
+    double eta;           /* default 0, in [0, 1): a step is accepted when rho > eta */
+    double ftol;          /* default 1e-10: an accepted step with F - F_new <= ftol * |F| ends the run, CONVERGED_F */
+    double xtol;          /* default 1e-10: an accepted step with ||h||_2 <= xtol * (||x||_2 + xtol) ends the run, CONVERGED_X */
+} aprilsam_amd_lm_opts_t;
+void aprilsam_amd_lm_opts_init(aprilsam_amd_lm_opts_t *opts);
+
+enum { APRILSAM_AMD_LM_CONVERGED_F = 1, APRILSAM_AMD_LM_CONVERGED_X = 2, APRILSAM_AMD_LM_STALLED = 3, APRILSAM_AMD_LM_MAX_ITERS = 4 };
+typedef struct {
+    int    status, iterations, accepted, rejected_not_spd;
+    double F_initial, F_final;     /* the LM objective above */
+    double chi2_final;             /* april_graph_chi2 of the returned states */
+    double lambda_final;
+} aprilsam_amd_lm_report_t;
+
+/* trace: NULL, or 4 * opts->max_iters doubles, one row per iteration: F at the trial point, rho, the lambda used, accepted (0/1) */
+int aprilsam_amd_optimize_lm(april_graph_t *graph, april_graph_cholesky_param_t *param, const aprilsam_amd_lm_opts_t *opts,
+                             aprilsam_amd_lm_report_t *report, double *trace);
+
 /* ---- max-mixture factors (Olson & Agarwal, RSS 2012) ---------------------------------------------------
  * A max factor on the ordered pair (a, b) holds K = 1..8 components, each an xyt factor made by april_graph_factor_xyt_create on
  * the same (a, b) with a symmetric W of det W > 0, and a log weight per component.  At a point p component i scores
