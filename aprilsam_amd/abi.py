@@ -104,6 +104,8 @@ class LmReport(C.Structure):
 
 
 LM_CONVERGED_F, LM_CONVERGED_X, LM_STALLED, LM_MAX_ITERS = 1, 2, 3, 4
+# robust loss kinds of xyt / xytpos factors (include/aprilsam_amd.h: aprilsam_amd_factor_set_robust)
+ROBUST_NONE, ROBUST_HUBER, ROBUST_CAUCHY, ROBUST_DCS = 0, 1, 2, 3
 
 # measured LP64 layout of the reference; checked by tests/test_abi.py
 EXPECTED_SIZES = {"ZArray": 24, "Graph": 32, "Factor": 104, "Node": 112, "CholeskyParam": 128}

@@ -140,6 +140,14 @@ int aprilsam_amd_graph_save_ex(april_graph_t *g, const char *path, unsigned long
             fprintf(stderr, "aprilsam_amd_graph_save: factor %d has type %d, only xyt / xytpos factors have a file encoding\n", i, fs[i]->type);
             return 0;
         }
+    for (int i = 0; i < g->factors->size; i++) {
+        int kind = APRILSAM_AMD_ROBUST_NONE; double c = 0;
+        aprilsam_amd_factor_get_robust(fs[i], &kind, &c);
+        if (kind != APRILSAM_AMD_ROBUST_NONE) {       // (the format has no encoding of the loss: a reloaded file would be another problem)
+            fprintf(stderr, "aprilsam_amd_graph_save: factor %d carries a robust loss, which has no file encoding\n", i);
+            return 0;
+        }
+    }
     Writer w{ MAGIC0 + magic_offset };
     auto graph_body = [&](Sink &o) {
         for (int i = 0; i < g->nodes->size; i++) {

@@ -7,7 +7,8 @@
 // :166 exist_factor->copy, april_graph.c:335-346 ->destroy).  The vtable entries are a courtesy to such
 // callers; the solver entry points never call them — factors of type 1/2 are evaluated by the HIP
 // kernels (csrc/kernels.hip.h).  Max-mixture factors (type 3) are built here too: their selection rule
-// (max_select) is the one the incremental path applies on the host and k_select_mixture restates on the device.
+// (max_select) is the one the incremental path applies on the host and k_select_mixture restates on the device.  Robust losses on xyt /
+// xytpos factors are kept here as well: a tagged block hung off u.common.impl, applied by eval_finish.
 #include <cmath>
 #include <cstdio>
 #include <string>
@@ -19,6 +20,7 @@
 #include "../../include/aprilsam_amd.h"
 #include "solver.h"
 #include "errors.h"
+#include "robust.h"
 
 namespace {
 
@@ -63,6 +65,23 @@ april_graph_factor_eval_t *eval_alloc(int njac) {
     e->W = matd33(nullptr);
     return e;
 }
+// ---- robust loss ----------------------------------------------------------------------
+// The reference leaves u.common.impl unused (NULL) for its xyt / xytpos factors.  A library factor with a loss points it at this block;
+// the tag tells it apart from anything a foreign library might keep there, and only factors whose eval is this library's are looked at.
+constexpr unsigned long long ROBUST_TAG = 0x726f627573745f6cULL;       // "robust_l"
+struct RobustBlock { unsigned long long tag = ROBUST_TAG; int kind = 0; double c = 0; };
+april_graph_factor_eval_t *xyt_eval(april_graph_factor_t *f, april_graph_t *g, april_graph_factor_eval_t *e);
+april_graph_factor_eval_t *xytpos_eval(april_graph_factor_t *f, april_graph_t *g, april_graph_factor_eval_t *e);
+bool is_library_common(const april_graph_factor_t *f) {
+    return (f->type == APRIL_GRAPH_FACTOR_XYT_TYPE && f->nnodes == 2 && f->eval == xyt_eval) ||
+           (f->type == APRIL_GRAPH_FACTOR_XYTPOS_TYPE && f->nnodes == 1 && f->eval == xytpos_eval);
+}
+RobustBlock *own_robust(const april_graph_factor_t *f) {
+    if (!is_library_common(f)) return nullptr;
+    void *p = f->u.common.impl;
+    return (p && *(const unsigned long long *)p == ROBUST_TAG) ? (RobustBlock *)p : nullptr;
+}
+
 void eval_finish(april_graph_factor_t *f, april_graph_factor_eval_t *e) {
     e->length = 3;
     memcpy(e->W->data, f->u.common.W->data, 72);
@@ -71,6 +90,11 @@ void eval_finish(april_graph_factor_t *f, april_graph_factor_eval_t *e) {
     double X1 = w[3] * r[0] + w[4] * r[1] + w[5] * r[2];
     double X2 = w[6] * r[0] + w[7] * r[1] + w[8] * r[2];
     e->chi2 = r[0] * X0 + r[1] * X1 + r[2] * X2;
+    if (const RobustBlock *rb = own_robust(f)) {      // IRLS: the plain r and J with W_eff = w(s) W, chi2 = rho(s)
+        const double s = e->chi2, wt = asam::robust_weight(rb->kind, rb->c, s);
+        for (int i = 0; i < 9; i++) e->W->data[i] = wt * e->W->data[i];
+        e->chi2 = asam::robust_rho(rb->kind, rb->c, s);
+    }
 }
 
 // ---- xyt factor ------------------------------------------------------------------------------------------
@@ -120,13 +144,18 @@ const char *attr_get(const void *p, const char *key) {
 }
 
 void factor_destroy(april_graph_factor_t *f) {
+    delete own_robust(f);
     free(f->nodes); free(f->u.common.z); free(f->u.common.ztruth); free(f->u.common.W);
     attr_free(f->attr);
     free(f);
 }
+void robust_clone(const april_graph_factor_t *f, april_graph_factor_t *c) {
+    if (const RobustBlock *rb = own_robust(f)) c->u.common.impl = new RobustBlock(*rb);
+}
 april_graph_factor_t *xyt_copy(april_graph_factor_t *f) {
     april_graph_factor_t *c = april_graph_factor_xyt_create(f->nodes[0], f->nodes[1], f->u.common.z, f->u.common.ztruth, f->u.common.W);
     c->attr = attr_clone(f->attr);            // the reference's copy keeps the attributes (the demo reads "type" from the copy)
+    robust_clone(f, c);
     return c;
 }
 
@@ -145,6 +174,7 @@ april_graph_factor_eval_t *xytpos_eval(april_graph_factor_t *f, april_graph_t *g
 april_graph_factor_t *xytpos_copy(april_graph_factor_t *f) {
     april_graph_factor_t *c = april_graph_factor_xytpos_create(f->nodes[0], f->u.common.z, f->u.common.ztruth, f->u.common.W);
     c->attr = attr_clone(f->attr);
+    robust_clone(f, c);
     return c;
 }
 
@@ -229,6 +259,7 @@ bool max_check(const april_graph_factor_t *f, char *why, int cap) {
         if (!c || c->type != APRIL_GRAPH_FACTOR_XYT_TYPE || c->nnodes != 2 || c->eval != xyt_eval || !c->u.common.z || !c->u.common.W) {
             snprintf(why, cap, "component %d is not an xyt factor of this library (april_graph_factor_xyt_create)", i); return false;
         }
+        if (own_robust(c)) { snprintf(why, cap, "component %d carries a robust loss (DESIGN.md section 15: not supported on max factors)", i); return false; }
         if (c->nodes[0] != f->nodes[0] || c->nodes[1] != f->nodes[1]) {
             snprintf(why, cap, "component %d connects (%d, %d), the factor (%d, %d)", i, c->nodes[0], c->nodes[1], f->nodes[0], f->nodes[1]); return false;
         }
@@ -260,9 +291,71 @@ int max_select(const april_graph_factor_t *f, const double *pa, const double *pb
     return best;
 }
 
+// s = r^T W r of an xyt (pb given) or xytpos factor with measurement z at pa / pb, in eval_finish's association
+double robust_host_s(const double *z, const double *w, const double *pa, const double *pb) {
+    double r[3];
+    if (pb) {
+        const double ca = cos(pa[2]), sa = sin(pa[2]);
+        const double dx = pb[0] - pa[0], dy = pb[1] - pa[1];
+        const double zh0 = ca * dx + sa * dy, zh1 = -sa * dx + ca * dy, zh2 = pb[2] - pa[2];
+        r[0] = z[0] - zh0; r[1] = z[1] - zh1; r[2] = mod2pi_h(z[2] - zh2);
+    } else {
+        r[0] = z[0] - pa[0]; r[1] = z[1] - pa[1]; r[2] = mod2pi_h(z[2] - pa[2]);
+    }
+    const double X0 = w[0] * r[0] + w[1] * r[1] + w[2] * r[2];
+    const double X1 = w[3] * r[0] + w[4] * r[1] + w[5] * r[2];
+    const double X2 = w[6] * r[0] + w[7] * r[1] + w[8] * r[2];
+    return r[0] * X0 + r[1] * X1 + r[2] * X2;
+}
+
+bool robust_of(const april_graph_factor_t *f, int *kind, double *c) {
+    const RobustBlock *rb = own_robust(f);
+    if (!rb) return false;
+    *kind = rb->kind; *c = rb->c;
+    return true;
+}
+
 }  // namespace asam
 
 extern "C" {
+
+int aprilsam_amd_factor_set_robust(april_graph_factor_t *f, int kind, double c) {
+    const char *who = "aprilsam_amd_factor_set_robust: ";
+    if (!f) { asam::set_last_error(asam::ERR_BAD_GRAPH, std::string(who) + "null factor"); return asam::ERR_BAD_GRAPH; }
+    if (!is_library_common(f) || !f->u.common.W || !f->u.common.z) {
+        asam::set_last_error(asam::ERR_UNSUPPORTED, std::string(who) + "not an xyt / xytpos factor of this library (max factors and foreign factors carry no loss)");
+        return asam::ERR_UNSUPPORTED;
+    }
+    if (f->u.common.impl && !own_robust(f)) {
+        asam::set_last_error(asam::ERR_UNSUPPORTED, std::string(who) + "u.common.impl is in use by another library");
+        return asam::ERR_UNSUPPORTED;
+    }
+    if (kind < APRILSAM_AMD_ROBUST_NONE || kind > APRILSAM_AMD_ROBUST_DCS) {
+        asam::set_last_error(asam::ERR_BAD_GRAPH, std::string(who) + "kind " + std::to_string(kind) + " out of range (0 to 3)");
+        return asam::ERR_BAD_GRAPH;
+    }
+    if (kind == APRILSAM_AMD_ROBUST_NONE) { delete own_robust(f); f->u.common.impl = nullptr; return 0; }
+    if (!std::isfinite(c) || !(c > 0)) {
+        asam::set_last_error(asam::ERR_BAD_GRAPH, std::string(who) + "c = " + std::to_string(c) + " must be finite and > 0");
+        return asam::ERR_BAD_GRAPH;
+    }
+    if (!asam::robust_spd(f->u.common.W->data)) {
+        asam::set_last_error(asam::ERR_UNSUPPORTED, std::string(who) + "W is not symmetric positive definite");
+        return asam::ERR_UNSUPPORTED;
+    }
+    RobustBlock *rb = own_robust(f);
+    if (!rb) { rb = new RobustBlock(); f->u.common.impl = rb; }
+    rb->kind = kind; rb->c = c;
+    return 0;
+}
+
+int aprilsam_amd_factor_get_robust(const april_graph_factor_t *f, int *kind, double *c) {
+    int k = APRILSAM_AMD_ROBUST_NONE; double cv = 0;
+    if (f) (void)asam::robust_of(f, &k, &cv);
+    if (kind) *kind = k;
+    if (c) *c = cv;
+    return 0;
+}
 
 april_graph_factor_t *aprilsam_amd_factor_max_create(april_graph_factor_t **components, const double *logw, int n) {
     if (!components || !logw || n < 1 || n > asam::MAX_MIX_K) {

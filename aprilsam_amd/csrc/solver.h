@@ -106,5 +106,9 @@ bool is_native_max(const april_graph_factor_t *f);                 // type 3 wit
 bool max_check(const april_graph_factor_t *f, char *why, int cap);  // component count, types, endpoints, symmetric W with det > 0, finite logw
 double max_const(const april_graph_factor_t *f, int i);           // -2 logw_i - ln det W_i
 int max_select(const april_graph_factor_t *f, const double *pa, const double *pb);
+// robust losses (host_objects.cpp): true for a library xyt / xytpos factor that carries one, with its kind and c
+bool robust_of(const april_graph_factor_t *f, int *kind, double *c);
+double robust_host_s(const double *z, const double *w, const double *pa, const double *pb);      // r^T W r at pa (/ pb: xyt), eval_finish's association
+int robust_weights(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *factors, double *w);   // solver_calls.inc.h
 
 }  // namespace asam

@@ -28,6 +28,7 @@
 #include "errors.h"
 #include "kernels.hip.h"
 #include "maxmix.hip.h"
+#include "robust.hip.h"
 #include "lm.hip.h"
 #include "selinv.hip.h"
 #include "pathsolve.hip.h"
@@ -460,6 +461,9 @@ extern "C" int aprilsam_amd_marginals_joint(april_graph_t *graph, april_graph_ch
 }
 extern "C" int aprilsam_amd_max_selected(april_graph_t *graph, april_graph_cholesky_param_t *param, int n, const int *factors, int *out) {
     return asam::max_selected(graph, param, n, factors, out);
+}
+extern "C" int aprilsam_amd_robust_weights(april_graph_t *graph, april_graph_cholesky_param_t *param, int n, const int *factors, double *w) {
+    return asam::robust_weights(graph, param, n, factors, w);
 }
 extern "C" long long aprilsam_amd_debug_selinv_runs(const april_graph_cholesky_param_t *param) { return asam::selinv_runs(param); }
 extern "C" int aprilsam_amd_marginals_joint_any(april_graph_t *graph, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, double *cov) {

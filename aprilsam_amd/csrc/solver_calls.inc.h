@@ -64,6 +64,7 @@ static void batch_impl(april_graph_t *g, april_graph_cholesky_param_t *param) {
             // device through upload_factors: the patch list of inc_fast_step carries the NEW factors alone
             if (F > gp.F_cap || gp.dirty_hi > gp.dirty_lo) upload_factors(gp);
             upload_mixture(gp);                         // (max factors appended: their components, for the step's k_select_mixture)
+            upload_robust(gp);                          // (robust factors appended or edited: their table, for the step's k_robust_weight)
             c.h_bad.need(4);
             hybrid = inc_fast_step(c, gp, N, F, c.inc_F, c.inc_N, nullptr, lam);
             reused = hybrid;
@@ -300,10 +301,12 @@ static void inc_impl(april_graph_t *g, april_graph_cholesky_param_t *param) {
         patch_states = pack_states_some(gp, g, inv); lazy_states = true;
     } else patch_states = pack_states_diff(gp, g);
     select_new_max(gp, g, c.inc_F);                    // new max factors: selected at their l_points as the mirror holds them, into h_z / h_W
+    select_new_robust(gp, c.inc_F);                    // new robust factors: weighted at the points the mirror holds, into h_W
     const double tp1 = now_ms() - (tp0b - tp0a);      // (profile: "pack" = factors + states, "model" = the bookkeeping in between)
     const double tp2 = tp1 + (tp0b - tp0a);
     if (F > gp.F_cap || !g_opt.inc_fast || !gp.host_idx.empty()) upload_factors(gp);     // (growing the device arrays re-uploads everything)
     upload_mixture(gp);
+    upload_robust(gp);
     if (!gp.host_idx.empty()) {       // new foreign factors are linearised now, at the host objects' current l_points
         eval_host_factors(gp, g, gp.host_evaluated);     // (aprilsam.c:508-542); older ones keep their evaluation
         upload_host_index(gp);
@@ -584,6 +587,37 @@ int max_selected(april_graph_t *g, april_graph_cholesky_param_t *param, int n, c
         for (int i = 0; i < n; i++) {
             const int gi = factors[i], m = gi < (int)gp.mx_of.size() && gi < gp.Fg ? gp.mx_of[gi] : -1;
             out[i] = m >= 0 ? sel[m] : -1;
+        }
+        return 0;
+    });
+}
+
+// aprilsam_amd_robust_weights: the weight each listed factor's most recent linearisation used -- k_robust_weight's
+// record (d_rb_w) for the factors on the device, the host's weight (select_new_robust) or -1 for the others.  The rule of max_selected.
+int robust_weights(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *factors, double *out) {
+    const int Fg = g ? zsize(g->factors) : 0;
+    if (!g || n < 0 || (n > 0 && (!factors || !out))) { set_last_error(ERR_BAD_GRAPH, "aprilsam_amd_robust_weights: bad argument"); return ERR_BAD_GRAPH; }
+    for (int i = 0; i < n; i++)
+        if (factors[i] < 0 || factors[i] >= Fg) {
+            set_last_error(ERR_BAD_GRAPH, "aprilsam_amd_robust_weights: factor " + std::to_string(factors[i]) + " out of range (" + std::to_string(Fg) + " factors)");
+            return ERR_BAD_GRAPH;
+        }
+    return guarded_rc(param, g, [&]() -> int {
+        SlotLock lk(param, g);
+        auto it = g_packs.find(g);
+        if (it == g_packs.end() || it->second->slot != t_slot) { for (int i = 0; i < n; i++) out[i] = -1; return 0; }
+        GraphPack &gp = *it->second;
+        std::vector<double> w(gp.rb_w);
+        if (gp.rb_on_device > 0) {             // (through the pinned staging buffer; the stream is idle before it is written)
+            HIPCHECK(hipStreamSynchronize(gp.stream));
+            gp.rb_stage.need((size_t)gp.rb_on_device);
+            HIPCHECK(hipMemcpyAsync(gp.rb_stage.p, gp.d_rb_w.p, (size_t)8 * gp.rb_on_device, hipMemcpyDeviceToHost, gp.stream));
+            HIPCHECK(hipStreamSynchronize(gp.stream));
+            memcpy(w.data(), gp.rb_stage.p, (size_t)8 * gp.rb_on_device);
+        }
+        for (int i = 0; i < n; i++) {
+            const int gi = factors[i], q = gi < (int)gp.rb_of.size() && gi < gp.Fg ? gp.rb_of[gi] : -1;
+            out[i] = q >= 0 ? w[q] : -1.0;
         }
         return 0;
     });

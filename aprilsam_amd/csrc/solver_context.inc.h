@@ -148,13 +148,14 @@ struct Context {
     const void *gexec_key = nullptr;      // GraphPack the graph was captured against
     long long gexec_serial = 0;
     long long gexec_mx = -1;              // GraphPack::mx_gen it was captured with (max-mixture table)
+    long long gexec_rb = -1;              // GraphPack::rb_gen it was captured with (robust table)
     // the same phase as the API call runs it: first kernel reads the caller's states from the pinned mirror, last kernel
     // writes new states / dx / pivot flag back to pinned mirrors -- one graph launch + one stream sync per call
     hipGraphExec_t gexec_api = nullptr;
-    const void *api_key[8] = {};
+    const void *api_key[9] = {};
     // Levenberg-Marquardt (solver_lm.inc.h): one iteration captured as its own graph, keyed like gexec plus the LM buffers it reads
     hipGraphExec_t gexec_lm = nullptr;
-    const void *lm_key[8] = {};
+    const void *lm_key[9] = {};
     DBuf<double> d_lm_trial, d_lm_hacc, d_lm_terms, d_lm_trace; DBuf<LmScalars> d_lm; HBuf<LmScalars> h_lm;
     int api_key_runs = 0;                          // calls seen with this key: the first one runs without a graph (below)
     // captured graphs that are no longer current: hipGraphExecDestroy takes 0.24 ms on this stack, so they are destroyed while the
@@ -822,6 +823,7 @@ static void enqueue_numeric(Context &c, GraphPack &gp, hipStream_t s, hipEvent_t
     enqueue_poison(c, s, nullptr, P.nF);
     tic(K_LINEARIZE);
     enqueue_select(gp, s);                           // max-mixture factors: the component selected at l_point goes into the factor's slot
+    enqueue_robust(gp, s, unary_at_lp ? gp.d_upt.p : (const double *)nullptr);      // robust factors: W_eff = w(s) W0 into the factor's slot
     {   // (a variant of the kernel without the asymmetric-W orientation branch, for graphs that have no such factor, was measured in round 6: no
         // difference -- 0.79 ms on the 1 M lattice either way)
         auto launch = [&](auto kern) {
@@ -886,7 +888,8 @@ static void run_numeric(Context &c, GraphPack &gp, bool timing, bool unary_at_lp
     if (timing && !c.have_events) { for (auto &e : c.ev) HIPCHECK(hipEventCreate(&e)); c.have_events = true; }
     if (io_host) {
         if (g_opt.use_graph && !timing && gp.host_idx.empty()) {
-            const void *key[8] = { gp.d_state.p, gp.h_state.p, gp.h_lp.p, gp.h_dx.p, c.h_bad.p, (const void *)(size_t)gp.N, (const void *)(size_t)gp.serial, (const void *)(size_t)gp.mx_gen };
+            const void *key[9] = { gp.d_state.p, gp.h_state.p, gp.h_lp.p, gp.h_dx.p, c.h_bad.p, (const void *)(size_t)gp.N, (const void *)(size_t)gp.serial, (const void *)(size_t)gp.mx_gen,
+                                   (const void *)(size_t)gp.rb_gen };
             // A graph is worth its capture, instantiation and destruction (0.3 ms together) only if the configuration comes back:
             // the first call with a new key -- every fall-back of an incremental run, every cold call -- enqueues its kernels directly.
             if (memcmp(key, c.api_key, sizeof(key)) != 0) { c.retire(c.gexec_api); memcpy(c.api_key, key, sizeof(key)); c.api_key_runs = 0; }
@@ -907,7 +910,7 @@ static void run_numeric(Context &c, GraphPack &gp, bool timing, bool unary_at_lp
         return;
     }
     if (g_opt.use_graph && !timing && !unary_at_lp && gp.host_idx.empty()) {   // (host-evaluated factors: staging buffers may move)
-        if (!c.gexec || c.gexec_key != (const void *)gp.d_state.p || c.gexec_serial != gp.serial || c.gexec_mx != gp.mx_gen) {
+        if (!c.gexec || c.gexec_key != (const void *)gp.d_state.p || c.gexec_serial != gp.serial || c.gexec_mx != gp.mx_gen || c.gexec_rb != gp.rb_gen) {
             c.retire(c.gexec);
             hipGraph_t graph = nullptr;
             HIPCHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
@@ -915,7 +918,7 @@ static void run_numeric(Context &c, GraphPack &gp, bool timing, bool unary_at_lp
             HIPCHECK(hipStreamEndCapture(s, &graph));
             HIPCHECK(hipGraphInstantiate(&c.gexec, graph, nullptr, nullptr, 0));
             HIPCHECK(hipGraphDestroy(graph));
-            c.gexec_key = (const void *)gp.d_state.p; c.gexec_serial = gp.serial; c.gexec_mx = gp.mx_gen;
+            c.gexec_key = (const void *)gp.d_state.p; c.gexec_serial = gp.serial; c.gexec_mx = gp.mx_gen; c.gexec_rb = gp.rb_gen;
         }
         c.graph_stream = s;
         HIPCHECK(hipGraphLaunch(c.gexec, s));
@@ -929,6 +932,7 @@ static double device_chi2(GraphPack &gp) {     // chi^2 at d_state; synchronises
     if (gp.F == 0) return 0;
     hipLaunchKernelGGL(k_chi2, dim3((gp.F + TPB - 1) / TPB), dim3(TPB), 0, s, gp.F, gp.d_fa.p, gp.d_fb.p, gp.d_z.p, gp.d_W.p, gp.d_state.p, gp.d_chi2f.p);
     enqueue_chi2_mixture(gp, s);       // (max factors: their terms selected at the states, in place -- the sums below keep their order)
+    enqueue_chi2_robust(gp, s);        // (robust factors: rho(s) in place of s)
     if (gp.F > REDUCE_SPLIT) {         // (the parts live behind the F_cap per-factor terms: upload_factors)
         double *parts = gp.d_chi2f.p + gp.F_cap;
         hipLaunchKernelGGL(k_reduce_parts, dim3(REDUCE_PARTS), dim3(TPB), 0, s, gp.F, gp.d_chi2f.p, parts);

@@ -32,12 +32,15 @@ static void lm_reduce(hipStream_t s, int n, const double *in, double *parts, dou
 }
 // F at st -> *out
 static void lm_enqueue_cost(Context &c, GraphPack &gp, hipStream_t s, const double *st, double *out) {
-    const int F = gp.F, M = gp.n_max(), T = std::max(F, 2 * gp.N);
+    const int F = gp.F, M = gp.n_max(), R = gp.n_robust(), T = std::max(F, 2 * gp.N);
     double *terms = c.d_lm_terms.p;
     hipLaunchKernelGGL(k_lm_cost, dim3((F + TPB - 1) / TPB), dim3(TPB), 0, s, F, gp.d_fa.p, gp.d_fb.p, gp.d_z.p, gp.d_W.p, st, terms);
     if (M > 0)
         hipLaunchKernelGGL(k_lm_cost_mixture, dim3((M + TPB - 1) / TPB), dim3(TPB), 0, s, M, gp.d_mx_f.p, gp.d_mx_k.p, gp.d_mx_z.p, gp.d_mx_W.p,
                            gp.d_mx_c.p, gp.d_fa.p, gp.d_fb.p, st, terms);
+    if (R > 0)           // (robust factors: rho(r^T W0 r) in place of the weighted slot's term)
+        hipLaunchKernelGGL(k_lm_cost_robust, dim3((R + TPB - 1) / TPB), dim3(TPB), 0, s, R, gp.d_rb_f.p, gp.d_rb_kind.p, gp.d_rb_c.p, gp.d_rb_W0.p,
+                           gp.d_fa.p, gp.d_fb.p, gp.d_z.p, st, terms);
     lm_reduce(s, F, terms, terms + T, out);
 }
 static void lm_enqueue_commit(Context &c, GraphPack &gp, hipStream_t s) {
@@ -65,8 +68,8 @@ static void lm_enqueue_iteration(Context &c, GraphPack &gp, hipStream_t s) {
 static void lm_run_iteration(Context &c, GraphPack &gp, hipStream_t s) {
     rewind_epoch(c, s, 1);
     if (!g_opt.use_graph) { lm_enqueue_iteration(c, gp, s); return; }
-    const void *key[8] = { gp.d_state.p, (const void *)(size_t)gp.serial, (const void *)(size_t)gp.mx_gen, (const void *)(size_t)gp.N,
-                           c.d_lm_trial.p, c.d_lm_terms.p, c.d_lm_trace.p, c.d_lm.p };
+    const void *key[9] = { gp.d_state.p, (const void *)(size_t)gp.serial, (const void *)(size_t)gp.mx_gen, (const void *)(size_t)gp.N,
+                           c.d_lm_trial.p, c.d_lm_terms.p, c.d_lm_trace.p, c.d_lm.p, (const void *)(size_t)gp.rb_gen };
     if (!c.gexec_lm || memcmp(key, c.lm_key, sizeof(key)) != 0) {
         c.retire(c.gexec_lm);
         hipGraph_t graph = nullptr;

@@ -75,6 +75,17 @@ struct GraphPack {
     void mx_clear() {
         if (!mx_f.empty() || mx_on_device) mx_gen++;      // (a pack that never held max factors keeps its captured graphs)
         mx_f.clear(); mx_k.assign(1, 0); mx_sel.clear(); mx_of.clear(); mx_z.clear(); mx_W.clear(); mx_c.clear(); mx_logw.clear(); mx_on_device = 0; mx_dirty = false; }
+    // robust factors: per robust factor q its packed entry rb_f[q], kind rb_kind[q], scale rb_c[q] and unweighted
+    // information matrix rb_W0[9q] (the slot of h_W / d_W holds W_eff = w W0 once a linearisation weighted it); rb_w: the host's weight
+    // (incremental steps; -1: none yet) -- d_rb_w, written by k_robust_weight, holds the weight of each factor's most recent linearisation.
+    // rb_of: per graph factor its q or -1.  rb_gen changes whenever the table's size or device addresses do: captured graphs are keyed by it
+    std::vector<int> rb_f, rb_kind, rb_of; std::vector<double> rb_c, rb_W0, rb_w;
+    DBuf<int> d_rb_f, d_rb_kind; DBuf<double> d_rb_c, d_rb_W0, d_rb_w; HBuf<double> rb_stage;
+    int rb_on_device = 0; bool rb_dirty = false; long long rb_gen = 0;
+    int n_robust() const { return (int)rb_f.size(); }
+    void rb_clear() {
+        if (!rb_f.empty() || rb_on_device) rb_gen++;      // (a pack that never held robust factors keeps its captured graphs)
+        rb_f.clear(); rb_kind.clear(); rb_of.clear(); rb_c.clear(); rb_W0.clear(); rb_w.clear(); rb_on_device = 0; rb_dirty = false; }
     hipStream_t stream = nullptr;
     HBuf<double> h_scalar;
     // incremental steps: the pinned mirrors h_state / h_lp and the device arrays d_state / d_lp hold the same values (mirror_sync),
@@ -87,6 +98,7 @@ struct GraphPack {
         d_fa.release(); d_fb.release(); d_z.release(); d_W.release(); d_state.release(); d_lp.release(); d_lp_last.release(); d_dx.release();
         d_chi2f.release(); d_scalar.release(); h_scalar.release(); h_hostH.release(); d_hostH.release(); d_host_idx.release(); d_upt.release();
         d_mx_f.release(); d_mx_k.release(); d_sel.release(); d_mx_z.release(); d_mx_W.release(); d_mx_c.release(); mx_stage.release(); mx_clear();
+        d_rb_f.release(); d_rb_kind.release(); d_rb_c.release(); d_rb_W0.release(); d_rb_w.release(); rb_stage.release(); rb_clear();
         if (stream) { forget_stream(stream); park_stream(slot, stream); }
         stream = nullptr;
     }
@@ -158,19 +170,19 @@ static void pack_factors(GraphPack &gp, const april_graph_t *g, bool validate_ol
     // (incremental calls only ever look at the factors added since the previous call, aprilsam.c:508-511: first and last packed pointer
     // as a sanity check instead of all of them -- the comparison of 5 000 pointers was a microsecond of every step)
     if (valid && trust) valid = from == 0 || (validate_old ? memcmp(gp.fptr.data(), fs, sizeof(void *) * from) == 0 : (gp.fptr[0] == fs[0] && gp.fptr[from - 1] == fs[from - 1]));
-    auto restart = [&]() { gp.topo_version++; from = 0; gp.F = 0; gp.F_on_device = 0; gp.host_idx.clear(); gp.host_evaluated = 0; gp.is_host.clear(); gp.p2g.clear(); gp.vslot.clear(); gp.g2p.assign(1, 0); gp.asym.clear(); gp.n_asym = 0; gp.mx_clear(); };
+    auto restart = [&]() { gp.topo_version++; from = 0; gp.F = 0; gp.F_on_device = 0; gp.host_idx.clear(); gp.host_evaluated = 0; gp.is_host.clear(); gp.p2g.clear(); gp.vslot.clear(); gp.g2p.assign(1, 0); gp.asym.clear(); gp.n_asym = 0; gp.mx_clear(); gp.rb_clear(); };
     if (!valid) restart();
     // one graph factor -> its packed entries (a, b, host flag, node slots of a host pair, what the pair carries)
     struct Ent { int a, b; bool host; unsigned short slots; unsigned char carry; };
-    Ent ents[64]; int ne = 0; bool is_max = false;
+    Ent ents[64]; int ne = 0; bool is_max = false, is_rb = false; int rb_kind = 0; double rb_c = 0;
     auto classify = [&](const april_graph_factor_t *f, int i) {
-        ne = 0; is_max = false;
+        ne = 0; is_max = false; is_rb = false;
         if (is_native_max(f)) {        // (before anything reads u.common: u.max aliases it)
             char why[192];
             if (f->nnodes != 2 || !max_check(f, why, sizeof why)) fail(ERR_UNSUPPORTED, "factor %d: max factor: %s", i, f->nnodes != 2 ? "not binary" : why);
             ents[ne++] = Ent{ f->nodes[0], f->nodes[1], false, 0, 3 }; is_max = true;
-        } else if (f->type == APRIL_GRAPH_FACTOR_XYT_TYPE && f->nnodes == 2) ents[ne++] = Ent{ f->nodes[0], f->nodes[1], false, 0, 3 };
-        else if (f->type == APRIL_GRAPH_FACTOR_XYTPOS_TYPE && f->nnodes == 1) ents[ne++] = Ent{ f->nodes[0], -1, false, 0, 3 };
+        } else if (f->type == APRIL_GRAPH_FACTOR_XYT_TYPE && f->nnodes == 2) { ents[ne++] = Ent{ f->nodes[0], f->nodes[1], false, 0, 3 }; is_rb = robust_of(f, &rb_kind, &rb_c); }
+        else if (f->type == APRIL_GRAPH_FACTOR_XYTPOS_TYPE && f->nnodes == 1) { ents[ne++] = Ent{ f->nodes[0], -1, false, 0, 3 }; is_rb = robust_of(f, &rb_kind, &rb_c); }
         else if ((f->nnodes == 1 || f->nnodes == 2) && f->eval)       // any other type: the factor's own eval(), on the host
             ents[ne++] = Ent{ f->nodes[0], f->nnodes == 2 ? f->nodes[1] : -1, true, (unsigned short)(f->nnodes == 2 ? 1 : 0xff), 3 };
         else if (f->nnodes >= 3 && f->nnodes <= 11 && f->eval) {      // a clique of pairs (see above); 11 nodes = 55 pairs
@@ -184,6 +196,8 @@ static void pack_factors(GraphPack &gp, const april_graph_t *g, bool validate_ol
             fail(ERR_UNSUPPORTED, "factor %d has type %d / %d nodes; factors of foreign types are supported with 1 to 11 nodes and an "
                                   "eval() function pointer (aprilsam.h:110-122)", i, f->type, f->nnodes);
         }
+        if (is_rb && !robust_spd(f->u.common.W->data))       // (set_robust checked it; the caller may have edited W since)
+            fail(ERR_UNSUPPORTED, "factor %d: a robust factor's W must be symmetric positive definite (DESIGN.md section 15)", i);
         for (int e = 0; e < ne; e++) {
             // -1 in `b` is the internal marker of a unary entry: a graph factor with two or more nodes must name real nodes on both sides
             // (a negative second endpoint used to pass as "unary" with its node slots still naming the missing node)
@@ -205,6 +219,7 @@ static void pack_factors(GraphPack &gp, const april_graph_t *g, bool validate_ol
             for (int e = 0; e < ne && !changed; e++)
                 changed = ents[e].a != gp.h_fa.p[p0 + e] || ents[e].b != gp.h_fb.p[p0 + e] || ents[e].host != (bool)gp.is_host[p0 + e];
             if (!changed) changed = is_max != (gp.mx_of[i] >= 0) || (is_max && gp.mx_k[gp.mx_of[i] + 1] - gp.mx_k[gp.mx_of[i]] != f->u.max.nfactors);
+            if (!changed) changed = is_rb != (i < (int)gp.rb_of.size() && gp.rb_of[i] >= 0);      // (a loss gained or lost: the table is packed again)
             if (changed) break;
             gp.fptr[i] = f;
             if (ents[0].host) continue;
@@ -224,6 +239,16 @@ static void pack_factors(GraphPack &gp, const april_graph_t *g, bool validate_ol
                 continue;
             }
             double *zp = gp.h_z.p + (size_t)3 * p0, *Wp = gp.h_W.p + (size_t)9 * p0;
+            if (is_rb) {               // the slot holds W_eff: z and W against the table's W0, kind and c against the table
+                const int q = gp.rb_of[i];
+                double *W0 = gp.rb_W0.data() + (size_t)9 * q;
+                if (memcmp(zp, f->u.common.z, 24) != 0 || memcmp(W0, f->u.common.W->data, 72) != 0 || gp.rb_kind[q] != rb_kind || memcmp(&gp.rb_c[q], &rb_c, 8) != 0) {
+                    memcpy(zp, f->u.common.z, 24); memcpy(W0, f->u.common.W->data, 72); memcpy(Wp, W0, 72);
+                    gp.rb_kind[q] = rb_kind; gp.rb_c[q] = rb_c;
+                    gp.rb_dirty = true; lo = std::min(lo, p0); hi = std::max(hi, p0 + 1);
+                }
+                continue;
+            }
             if (memcmp(zp, f->u.common.z, 24) != 0 || memcmp(Wp, f->u.common.W->data, 72) != 0) {
                 memcpy(zp, f->u.common.z, 24); memcpy(Wp, f->u.common.W->data, 72);
                 gp.note_asym(p0, Wp, true);
@@ -237,7 +262,7 @@ static void pack_factors(GraphPack &gp, const april_graph_t *g, bool validate_ol
             gp.content_version++;
         }
     }
-    gp.fptr.resize(Fg); gp.g2p.resize((size_t)Fg + 1); gp.mx_of.resize(Fg, -1);
+    gp.fptr.resize(Fg); gp.g2p.resize((size_t)Fg + 1); gp.mx_of.resize(Fg, -1); gp.rb_of.resize(Fg, -1);
     int F = gp.g2p[from];
     {   // the pinned mirrors are sized ONCE for everything this call appends (a pinned reallocation costs a quarter of a millisecond)
         size_t total = (size_t)F;
@@ -280,6 +305,11 @@ static void pack_factors(GraphPack &gp, const april_graph_t *g, bool validate_ol
                 memcpy(gp.h_z.p + (size_t)3 * F, f->u.common.z, 24);
                 memcpy(gp.h_W.p + (size_t)9 * F, f->u.common.W->data, 72);
                 gp.note_asym(F, gp.h_W.p + (size_t)9 * F, true);
+                if (is_rb) {           // the slot holds W0 until a weighting writes W_eff (k_robust_weight, select_new_robust)
+                    gp.rb_of[i] = gp.n_robust(); gp.rb_f.push_back(F); gp.rb_kind.push_back(rb_kind); gp.rb_c.push_back(rb_c); gp.rb_w.push_back(-1.0);
+                    gp.rb_W0.insert(gp.rb_W0.end(), f->u.common.W->data, f->u.common.W->data + 9);
+                    gp.rb_gen++;
+                }
             }
         }
         gp.g2p[i + 1] = F;
@@ -357,6 +387,72 @@ static void enqueue_chi2_mixture(GraphPack &gp, hipStream_t s) {
     hipLaunchKernelGGL(k_chi2_mixture, dim3((M + TPB - 1) / TPB), dim3(TPB), 0, s, M, gp.d_mx_f.p, gp.d_mx_k.p, gp.d_mx_z.p, gp.d_mx_W.p, gp.d_mx_c.p,
                        gp.d_fa.p, gp.d_fb.p, gp.d_state.p, gp.d_chi2f.p);
 }
+// the robust table -> device, the rule of upload_mixture: what was appended since the last upload, everything after
+// an edit or a move.  d_rb_w receives the host's weights of the appended factors only: the device's own of the older ones stay
+static void upload_robust(GraphPack &gp) {
+    const int R = gp.n_robust();
+    if (R == 0 || (gp.rb_on_device == R && !gp.rb_dirty)) return;
+    hipStream_t s = gp.stream;
+    HIPCHECK(hipStreamSynchronize(s));       // (the pinned staging buffer is written below)
+    if ((size_t)R > gp.d_rb_f.cap || (size_t)R > gp.d_rb_kind.cap || (size_t)R > gp.d_rb_c.cap || (size_t)R > gp.d_rb_w.cap || (size_t)9 * R > gp.d_rb_W0.cap) {
+        if (gp.rb_on_device > 0) {
+            gp.rb_stage.need((size_t)gp.rb_on_device);
+            HIPCHECK(hipMemcpyAsync(gp.rb_stage.p, gp.d_rb_w.p, (size_t)8 * gp.rb_on_device, hipMemcpyDeviceToHost, s));
+            HIPCHECK(hipStreamSynchronize(s));
+            memcpy(gp.rb_w.data(), gp.rb_stage.p, (size_t)8 * gp.rb_on_device);
+        }
+        const size_t cap = (size_t)R + R / 2 + 64;
+        gp.d_rb_f.need(cap); gp.d_rb_kind.need(cap); gp.d_rb_c.need(cap); gp.d_rb_w.need(cap); gp.d_rb_W0.need(9 * cap);
+        gp.rb_on_device = 0; gp.rb_dirty = true; gp.rb_gen++;
+    }
+    const int q0 = gp.rb_dirty ? 0 : gp.rb_on_device, s0 = std::min(gp.rb_on_device, R);
+    // staging layout (8-byte words): W0 | c | w | f, kind (ints, packed by two)
+    const size_t n = (size_t)(R - q0), nw = (size_t)(R - s0);
+    gp.rb_stage.need(9 * n + n + nw + n);
+    double *st = gp.rb_stage.p;
+    memcpy(st, gp.rb_W0.data() + (size_t)9 * q0, 72 * n);
+    memcpy(st + 9 * n, gp.rb_c.data() + q0, 8 * n);
+    memcpy(st + 10 * n, gp.rb_w.data() + s0, 8 * nw);
+    int *si = (int *)(st + 10 * n + nw);
+    memcpy(si, gp.rb_f.data() + q0, 4 * n);
+    memcpy(si + n, gp.rb_kind.data() + q0, 4 * n);
+    if (n) {
+        HIPCHECK(hipMemcpyAsync(gp.d_rb_W0.p + (size_t)9 * q0, st, 72 * n, hipMemcpyHostToDevice, s));
+        HIPCHECK(hipMemcpyAsync(gp.d_rb_c.p + q0, st + 9 * n, 8 * n, hipMemcpyHostToDevice, s));
+        HIPCHECK(hipMemcpyAsync(gp.d_rb_f.p + q0, si, 4 * n, hipMemcpyHostToDevice, s));
+        HIPCHECK(hipMemcpyAsync(gp.d_rb_kind.p + q0, si + n, 4 * n, hipMemcpyHostToDevice, s));
+    }
+    if (nw) HIPCHECK(hipMemcpyAsync(gp.d_rb_w.p + s0, st + 10 * n, 8 * nw, hipMemcpyHostToDevice, s));
+    gp.rb_on_device = R; gp.rb_dirty = false;
+}
+// incremental steps: the robust factors packed at or after entry f_from are weighted on the host (robust_host_s + robust_weight, the rule
+// k_robust_weight applies) at the point the fast path linearises them -- the l_point mirror (xyt) or the state mirror (xytpos, as
+// record_unary_points) -- and their slots of h_W take W_eff = w W0
+static void select_new_robust(GraphPack &gp, int f_from) {
+    for (int q = gp.n_robust() - 1; q >= 0 && gp.rb_f[q] >= f_from; q--) {
+        const int p = gp.rb_f[q], a = gp.h_fa.p[p], b = gp.h_fb.p[p];
+        const double *W0 = gp.rb_W0.data() + (size_t)9 * q;
+        const double s = robust_host_s(gp.h_z.p + (size_t)3 * p, W0, b >= 0 ? gp.h_lp.p + (size_t)3 * a : gp.h_state.p + (size_t)3 * a,
+                                       b >= 0 ? gp.h_lp.p + (size_t)3 * b : nullptr);
+        const double w = robust_weight(gp.rb_kind[q], gp.rb_c[q], s);
+        gp.rb_w[q] = w;
+        for (int k = 0; k < 9; k++) gp.h_W.p[(size_t)9 * p + k] = w * W0[k];
+    }
+}
+// the launch every linearisation of a pack with robust factors is preceded by (none for a pack without); upt: the unary factors' points
+// as the linearisation that follows reads them (k_linearize_t's argument)
+static void enqueue_robust(GraphPack &gp, hipStream_t s, const double *upt) {
+    const int R = gp.n_robust();
+    if (R == 0) return;
+    hipLaunchKernelGGL(k_robust_weight, dim3((R + TPB - 1) / TPB), dim3(TPB), 0, s, R, gp.d_rb_f.p, gp.d_rb_kind.p, gp.d_rb_c.p, gp.d_rb_W0.p,
+                       gp.d_fa.p, gp.d_fb.p, gp.d_z.p, gp.d_lp.p, gp.d_state.p, upt, gp.d_W.p, gp.d_rb_w.p);
+}
+static void enqueue_chi2_robust(GraphPack &gp, hipStream_t s) {
+    const int R = gp.n_robust();
+    if (R == 0) return;
+    hipLaunchKernelGGL(k_chi2_robust, dim3((R + TPB - 1) / TPB), dim3(TPB), 0, s, R, gp.d_rb_f.p, gp.d_rb_kind.p, gp.d_rb_c.p, gp.d_rb_W0.p,
+                       gp.d_fa.p, gp.d_fb.p, gp.d_z.p, gp.d_state.p, gp.d_chi2f.p);
+}
 static void upload_factors(GraphPack &gp) {
     const int F = gp.F;
     if (F > gp.F_cap) {           // reallocation loses the old content: re-upload everything
@@ -382,6 +478,7 @@ static void upload_factors(GraphPack &gp) {
     gp.F_on_device = F;
     gp.d_scalar.need(8); gp.h_scalar.need(8);
     upload_mixture(gp);
+    upload_robust(gp);
 }
 // evaluate the host factors [from, end) through their vtable (aprilsam.c:156 calls factor->eval the same way) and form
 // (J_a^T W) J_a, (J_a^T W) J_b, (J_b^T W) J_b, (J^T W) r in the reference's association (aprilsam.c:162-187)

@@ -131,6 +131,11 @@ class SolverLib:
                 d.aprilsam_amd_factor_max_create.argtypes = [C.POINTER(C.POINTER(abi.Factor)), _dp, C.c_int]
             if hasattr(d, "aprilsam_amd_max_selected"):      # (defined in the HIP translation unit)
                 d.aprilsam_amd_max_selected.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.c_int, _ip, _ip]
+            if hasattr(d, "aprilsam_amd_factor_set_robust"):
+                d.aprilsam_amd_factor_set_robust.argtypes = [C.POINTER(abi.Factor), C.c_int, C.c_double]
+                d.aprilsam_amd_factor_get_robust.argtypes = [C.POINTER(abi.Factor), C.POINTER(C.c_int), C.POINTER(C.c_double)]
+            if hasattr(d, "aprilsam_amd_robust_weights"):    # (defined in the HIP translation unit)
+                d.aprilsam_amd_robust_weights.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.c_int, _ip, _dp]
             d.aprilsam_amd_graph_save_ex.argtypes = [C.POINTER(abi.Graph), C.c_char_p, C.c_ulonglong]
             d.aprilsam_amd_graph_load.restype = C.POINTER(abi.Graph)
             d.aprilsam_amd_graph_load.argtypes = [C.c_char_p]
@@ -313,6 +318,27 @@ class Graph:
             raise RuntimeError(f"aprilsam_amd_max_selected failed rc={rc}: {self.lib.last_error()}")
         return out
 
+    def set_robust(self, i, kind, c=1.0):
+        """give factor i a robust loss (include/aprilsam_amd.h: aprilsam_amd_factor_set_robust): kind one of
+        abi.ROBUST_* (ROBUST_NONE clears it), c the threshold on sqrt(r'Wr).  Returns the library's code (0, -12, -13)."""
+        return int(self.lib.dll.aprilsam_amd_factor_set_robust(self.factor_ptr(i), int(kind), float(c)))
+
+    def get_robust(self, i):
+        """(kind, c) of factor i's robust loss; (ROBUST_NONE, 0.0) for a factor without one"""
+        k = C.c_int(-1); c = C.c_double(-1)
+        self.lib.dll.aprilsam_amd_factor_get_robust(self.factor_ptr(i), C.byref(k), C.byref(c))
+        return k.value, c.value
+
+    def robust_weights(self, param, factors=None):
+        """float array: the weight each listed factor's most recent linearisation used, -1 for a non-robust factor or one not yet
+        linearised (include/aprilsam_amd.h: aprilsam_amd_robust_weights); all factors when `factors` is None"""
+        idx = np.arange(self.n_factors, dtype=np.int32) if factors is None else np.ascontiguousarray(factors, dtype=np.int32).ravel()
+        out = np.full(len(idx), -1.0)
+        rc = self.lib.dll.aprilsam_amd_robust_weights(self.ptr, param.ptr if param is not None else None, len(idx), _np_i(idx), _np_d(out))
+        if rc != 0:
+            raise RuntimeError(f"aprilsam_amd_robust_weights failed rc={rc}: {self.lib.last_error()}")
+        return out
+
     def add_factor_xytpos(self, a, z, W):
         zz = (C.c_double * 3)(*z)
         m = self._matd(W)
@@ -378,6 +404,13 @@ class Graph:
     def factor(self, i):
         arr = C.cast(self.ptr.contents.factors.contents.data, C.POINTER(C.POINTER(abi.Factor)))
         return arr[i].contents
+
+    def factor_ptr(self, i):
+        """the factor object pointer of factor i (what the C entry points that take one factor expect)"""
+        if not 0 <= int(i) < self.n_factors:
+            raise IndexError(f"factor {i} out of range ({self.n_factors} factors)")
+        arr = C.cast(self.ptr.contents.factors.contents.data, C.POINTER(C.POINTER(abi.Factor)))
+        return arr[int(i)]
 
     def _gather(self, field):
         n = self.n_nodes

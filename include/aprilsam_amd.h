@@ -528,6 +528,32 @@ april_graph_factor_t *aprilsam_amd_factor_max_create(april_graph_factor_t **comp
  * linearised; returns 0 or a negative error code (-13 for an index out of range or a bad argument) */
 int aprilsam_amd_max_selected(april_graph_t *graph, april_graph_cholesky_param_t *param, int n, const int *factors, int *out);
 
+/* ---- robust losses on xyt / xytpos factors (iteratively reweighted least squares) ----------------------------
+ * A library-made xyt factor (april_graph_factor_xyt_create) or xytpos factor (april_graph_factor_xytpos_create) may carry a loss kind and
+ * a scale c (finite, > 0), a threshold on the Mahalanobis distance sqrt(s).  Its W must be symmetric (mirror entries bitwise equal) with
+ * all three leading minors > 0.  With r the plain factor's residual (theta wrapped) and s = r' W r:
+ *     HUBER   rho = s if s <= c^2, else 2 c sqrt(s) - c^2          w = 1 if s <= c^2, else c / sqrt(s)
+ *     CAUCHY  rho = c^2 log1p(s / c^2)                              w = 1 / (1 + s / c^2)
+ *     DCS     rho = s if s <= c^2, else c^2 (3 s - c^2) / (s + c^2)  w = 1 if s <= c^2, else 4 c^4 / (s + c^2)^2
+ * (DCS: dynamic covariance scaling, Agarwal et al., ICRA 2013, Phi = c^2.)  A NaN s gives a NaN weight: the call fails as for a plain
+ * factor that went non-finite.  Wherever the solver linearises the factor -- batch, resident and LM steps on the GPU, every fall-back
+ * of an incremental run -- it linearises the plain factor with W_eff = w(s) * W (one multiply per entry), s taken at the factor's
+ * linearisation point (xyt: the l_points; xytpos: the node's state, as the plain prior).  An incremental fast step weights a NEW
+ * robust factor on the host when it first linearises it; older factors keep their weight until a fall-back re-linearises everything.
+ * april_graph_chi2 and aprilsam_amd_resident_chi2 count 0.5 rho(s) for an xyt factor and rho(s) for an xytpos factor; the LM objective
+ * counts rho(s), and its model decrease is that of the weighted system solved.  Marginals, joint covariances and gating describe the
+ * system that was factorised: the weighted one.  eval / state_eval return the plain r and J with W = w(s) W and chi2 = rho(s).
+ * Sharded runs refuse robust factors (-12); .graph files cannot hold them (save returns 0 and writes nothing); max factors refuse
+ * components that carry a loss (-12). */
+enum { APRILSAM_AMD_ROBUST_NONE = 0, APRILSAM_AMD_ROBUST_HUBER = 1, APRILSAM_AMD_ROBUST_CAUCHY = 2, APRILSAM_AMD_ROBUST_DCS = 3 };
+/* kind NONE clears the loss; 0, -12 (not a library xyt / xytpos factor, a max factor, W not symmetric positive definite), -13 (NULL, kind
+ * out of range, c not finite or <= 0); sets aprilsam_amd_last_error on failure, factor unchanged then */
+int aprilsam_amd_factor_set_robust(april_graph_factor_t *factor, int kind, double c);
+int aprilsam_amd_factor_get_robust(const april_graph_factor_t *factor, int *kind, double *c);   /* NONE / 0 for any other factor */
+/* for each listed graph factor: the weight its most recent linearisation used; -1 for a non-robust factor or one not yet linearised.
+ * Returns 0 or -13 (an index out of range or a bad argument) */
+int aprilsam_amd_robust_weights(april_graph_t *graph, april_graph_cholesky_param_t *param, int n, const int *factors, double *w);
+
 /* ---- multi-GPU: nested-dissection subtree sharding, one process per GPU -------
  * The reference has no counterpart (it is sequential); a C host drives a sharded solve through the same graph / param
  * objects it hands to april_graph_cholesky (aprilsam.h:268-281):
