@@ -5,14 +5,22 @@ guard bands behind every frontal array: a stray read that is used changes the re
 import numpy as np
 
 from aprilsam_amd import datasets
+from tests.support.normal_eq import normal_equation_residual
+
+# every iteration's normal-equation residual (tests/support/normal_eq.py, relative to the terms of the right-hand side); the oracle's
+# own step leaves at most 7e-14 on every graph of these sweeps
+NORMAL_EQ_RTOL = 1e-10
 
 
 def run_batch(lib, arr, iters):
+    """chi^2 trace, final states and the last call's stats; stats["normal_eq_rel"]: the worst normal-equation residual of the iterations"""
     g = lib.new_graph(); g.build_from_arrays(*arr); p = lib.new_param()
-    chi2 = [g.chi2()]
+    chi2 = [g.chi2()]; res = 0.0
     for _ in range(iters):
         g.cholesky(p); chi2.append(g.chi2())
+        res = max(res, normal_equation_residual(g.l_points(), *arr[1:], g.deltas(), p.c.tikhanov)["rel_max"])
     st = g.states(); s = p.stats(); p.destroy(); g.destroy()
+    s["normal_eq_rel"] = res
     return np.array(chi2), st, s
 
 
@@ -51,9 +59,11 @@ def sweep_batch(lib, oracle, cases, option_sets, chi2_tol, state_tol, log=print)
                 c, st, s = run_batch(lib, arr, 2)
             e1 = float(np.max(np.abs(c - oc) / np.maximum(oc, 1e-12))); e2 = float(np.max(np.abs(st - ost)))
             worst = max(worst, e1)
-            log(f"{label} {o}: fronts {s['n_fronts']} levels {s['n_levels']} rows {s['max_front_rows']} chi2 relerr {e1:.2e} states {e2:.2e}")
+            log(f"{label} {o}: fronts {s['n_fronts']} levels {s['n_levels']} rows {s['max_front_rows']} chi2 relerr {e1:.2e} states {e2:.2e} "
+                f"normal equations {s['normal_eq_rel']:.2e}")
             assert s["error_code"] == 0 and s["not_spd"] == 0, (label, o, s)
             assert e1 < chi2_tol and e2 < state_tol, ("MISMATCH", label, o, e1, e2, c.tolist(), oc.tolist(), s)
+            assert s["normal_eq_rel"] < NORMAL_EQ_RTOL, ("NORMAL EQUATIONS", label, o, s["normal_eq_rel"])
     return worst
 
 
