@@ -1,6 +1,7 @@
 // capi.cpp — the C-ABI entry points of libaprilsam_amd.so (include/aprilsam_amd.h PART 2 and 4).
 // Same names, argument meaning and error behaviour as the reference functions they replace; each one
 // forwards to the HIP runtime in solver.hip.cpp.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -160,6 +161,22 @@ long long aprilsam_amd_shard_plan(const aprilsam_amd_plan_t *plan, int world, in
     else if (what == 4) v = asam::shard_critical_path(plan->P, world, owner, top); else return -1;
     if (out) for (long long i = 0; i < (long long)v.size() && i < cap; i++) out[i] = v[i];
     return (long long)v.size();
+}
+
+// XCD placement of a tree's multi-level launches (plan.h: xcd_place): fronts of levels >= l0 in level order, leaves = level 0 when l0 == 1.
+// which: 0 up-sweep list, 1 down-sweep list, 2 leaf list (returns the length, fills out up to out_cap), 3 xcd_check's code
+int aprilsam_amd_xcd_place(int nF, const int *parent, const int *level, const int *nsb, int l0, int cap, int cap_leaf, int which, int *out, int out_cap) {
+    if (nF < 0 || !parent || !level || !nsb || which < 0 || which > 3) return -100;
+    std::vector<int> up, leaves;
+    int top = 0;
+    for (int t = 0; t < nF; t++) top = std::max(top, level[t]);
+    for (int l = l0; l <= top; l++) for (int t = 0; t < nF; t++) if (level[t] == l) up.push_back(t);
+    if (l0 == 1) for (int t = 0; t < nF; t++) if (level[t] == 0) leaves.push_back(t);
+    const asam::XcdLists x = asam::xcd_place(up, leaves, parent, nsb, nF, cap, cap_leaf);
+    if (which == 3) return asam::xcd_check(x, up, leaves, parent, nF, cap, cap_leaf);
+    const std::vector<int> &v = which == 0 ? x.up : which == 1 ? x.dn : x.leaf;
+    if (out) for (int i = 0; i < (int)v.size() && i < out_cap; i++) out[i] = v[i];
+    return (int)v.size();
 }
 
 long long aprilsam_amd_plan_query(const aprilsam_amd_plan_t *plan, const char *what, long long **out) {

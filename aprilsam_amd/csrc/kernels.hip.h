@@ -43,6 +43,9 @@
 namespace asam {
 
 constexpr int PROF_SLOTS = 16;    // debug stamps per front (DevPlan::prof)
+constexpr int PROF_XCD_UP = 12, PROF_XCD_DN = 13;     // ... slots of the XCD a front's k_front_small / k_backsolve_w ran on (1 + XCC id; tools/front_times.py)
+// the XCD this workgroup runs on (0-7): a hardware register read, for the profile stamps only -- placement is never relied upon
+__device__ __forceinline__ int xcc_id() { return __builtin_amdgcn_s_getreg(20 | (0 << 6) | ((4 - 1) << 11)) & 7; }     // hwreg(HW_REG_XCC_ID, 0, 4)
 constexpr int TPB = 256;          // threads per workgroup (4 waves)
 constexpr int NB = 32;            // panel width of the big-front path
 constexpr int TILE = 64;          // syrk output tile (4 waves x 32x32)
@@ -1183,6 +1186,7 @@ __device__ __forceinline__ void front_small_body(const DevPlan &P, const int t, 
     const int nsb = D.nsb, nbc = D.nsb + D.nub;
     const int R = 3 * (nbc + 1), C = 3 * nbc, ld = R | 1;
     double *Fg = pool + D.off;
+    if (P.prof && threadIdx.x == 0) P.prof[(size_t)t * PROF_SLOTS + PROF_XCD_UP] = 1 + xcc_id();
     // full_lds_limit (per launch): fronts whose whole array fits run fully in LDS, the others in panel mode.  On levels with
     // far more fronts than compute units the host lowers it, trading per-front latency for workgroups per CU.
     if ((long long)small_front_lds(R, C, NT / 64) <= full_lds_limit) {
@@ -1561,11 +1565,13 @@ __global__ void __launch_bounds__(NT) k_front_small(DevPlan P, const int *__rest
                                                     const double *__restrict__ Hc, int *bad, long long full_lds_limit,
                                                     int *flags = nullptr, int wait = 0, UpdCtx uc = UpdCtx{}) {
     extern __shared__ __attribute__((aligned(16))) double S[];
+    const int t = fronts[blockIdx.x];
+    if (t < 0) return;                               // an empty slot of an XCD-placed list (xcd_place): no wait, no publish
     if (uc.recs) {                                   // an incremental step: some fronts of the list are updated, not re-factorised
         const UpdRec *rec = uc.recs + blockIdx.x;
-        if (rec->mode) { front_update_body<NT>(P, fronts[blockIdx.x], *rec, uc, pool, flags, bad, S); return; }
+        if (rec->mode) { front_update_body<NT>(P, t, *rec, uc, pool, flags, bad, S); return; }
     }
-    front_small_body<NT>(P, fronts[blockIdx.x], pool, Hc, bad, full_lds_limit, flags, wait, S);
+    front_small_body<NT>(P, t, pool, Hc, bad, full_lds_limit, flags, wait, S);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -2232,6 +2238,7 @@ __global__ void __launch_bounds__(TPB) k_backsolve_t(DevPlan P, const int *__res
                                                      double *__restrict__ x, int split, int *xflags, int wait, int *bad, UpdArgs upd) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int t = fronts[blockIdx.x];
+    if (t < 0) return;                 // an empty slot of an XCD-placed list
     const int ev = xflags ? flag_value(P) : 0;
     const FrontDesc D_ = P.fd[t];
     const int nsb = D_.nsb, nub = D_.nub, nbc = nsb + nub;
@@ -2613,6 +2620,7 @@ __device__ __forceinline__ void backsolve_w_body(const DevPlan &P, const int t, 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int *rows = P.f_rows + D_.rows_begin;
     long long *pf = (P.prof && P.prof_mode == 2) ? P.prof + (size_t)t * PROF_SLOTS : nullptr;
+    if (pf && tid == 0) pf[PROF_XCD_DN] = 1 + xcc_id();
     {
         const int ne = ns * R;                           // (the own columns are contiguous in the front: element e)
         for (int e0 = tid; e0 < ne; e0 += 8 * TPB) {
@@ -2686,7 +2694,9 @@ __device__ __forceinline__ void backsolve_w_body(const DevPlan &P, const int t, 
 __global__ void __launch_bounds__(TPB) k_backsolve_w(DevPlan P, const int *__restrict__ fronts, const double *__restrict__ pool,
                                                      double *__restrict__ x, int *xflags, int *bad, UpdArgs upd) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
-    backsolve_w_body(P, fronts[blockIdx.x], pool, x, xflags, bad, upd, smem);
+    const int t = fronts[blockIdx.x];
+    if (t < 0) return;                               // an empty slot of an XCD-placed list
+    backsolve_w_body(P, t, pool, x, xflags, bad, upd, smem);
 }
 
 // Multi-GPU exchange: the Schur update of a front whose parent lives on another rank, packed for the wire.  Only the

@@ -82,6 +82,22 @@ struct Plan {
 void build_plan(Plan &P, int N, int F, const int *factor_nodes, const double *xy, int leaf_nodes);
 void build_gather_lists(Plan &P);     // fills bd_* / rd_* (only the tests' host-side emulator reads them: derived on demand)
 
+// ---- XCD placement of the batch step's latency-bound launches (option xcd_place) --------------------------------------------------
+// Workgroups are dealt round-robin over the 8 XCDs (observed, not promised): ids b and b + 8 share an XCD and its L2, where a
+// hand-over written with plain stores is read about 1.7 x faster than from another XCD.  A heavy-path decomposition of the fronts of
+// the multi-level launches gives each front a class 0..7: a front takes the class of its costliest child (critical path of a cost
+// model), so the tree's critical path stays in one class from leaf to root, and the other children start classes of their own,
+// balanced by count and cost, at most `cap` fronts per class (what an XCD holds at once; spill to the next class).  A front of class
+// c goes to workgroup id 8 k + c, empty slots hold -1 (the kernels return at once there).  Every dependency keeps a lower workgroup
+// id -- up: children before parents, down: parents before children -- the invariant that keeps the flag waits deadlock-free.  Leaves
+// (the level-0 launch before the multi-level one) take their parent's class, at most cap_leaf per class.  Speed only: no result
+// depends on where a workgroup runs.
+struct XcdLists { std::vector<int> up, dn, leaf; };
+// up: the fronts of the multi-level launches, children before parents; leaves: the fronts of the launch before them (may be empty)
+XcdLists xcd_place(const std::vector<int> &up, const std::vector<int> &leaves, const int *parent, const int *nsb, int nF, int cap, int cap_leaf);
+// 0, or a negative code naming the first violated invariant (permutation plus padding, dependencies at lower ids, classes within cap)
+int xcd_check(const XcdLists &x, const std::vector<int> &up, const std::vector<int> &leaves, const int *parent, int nF, int cap, int cap_leaf);
+
 // ---- pieces, exposed for tests --------------------------------------------------------------------------
 struct NDTree {
     struct Node { std::vector<int> verts; std::vector<int> children; };

@@ -74,7 +74,7 @@ static const OptionDef OPTION_TABLE[] = {
     { "inc_inline", &Options::inc_inline, 0, true }, { "inc_update", &Options::inc_update, 0, true }, { "inc_tail_solve", &Options::inc_tail_solve, 0, true },
     { "inc_lazy_states", &Options::inc_lazy_states, 0, true }, { "inc_replan_tall", &Options::inc_replan_tall, 0, true },
     { "speculate_factors", &Options::speculate_factors, 0, true }, { "warm_up", &Options::warm_up, 0, true }, { "pin_last", &Options::pin_last, 0, false }, { "persist", &Options::persist, 0, false },
-    { "persist_max_fronts", &Options::persist_max_fronts, 0, false }, { "linearize_staged_min", &Options::linearize_staged_min, 0, false },
+    { "persist_max_fronts", &Options::persist_max_fronts, 0, false }, { "xcd_place", &Options::xcd_place, 0, false }, { "linearize_staged_min", &Options::linearize_staged_min, 0, false },
     { "wave_backsolve", &Options::wave_backsolve, 0, false }, { "blk_backsolve", &Options::blk_backsolve, 0, false }, { "tail_poses", &Options::tail_poses, 8, false },
     { "batch_extend", &Options::batch_extend, 0, true }, { "extend_tail_fronts", &Options::extend_tail_fronts, 0, true }, { "mem_cap_mb", &Options::mem_cap_mb, 0, true },
     { "pool_guard", &Options::pool_guard, 0, false }, { "amalg", &Options::amalg, 0, false }, { "amalg_max", &Options::amalg_max, 1, false }, { "pool_poison", &Options::pool_poison, 0, false }, { "skip_flag_waits", &Options::skip_flag_waits, 0, false },
@@ -403,6 +403,32 @@ int selftest() {
                 if (panel_front_lds(R, 3 * nsb, nw) > small_front_lds(R, C, nw)) return -41;
                 if (small_front_lds(R, C, nw) != (size_t)(R | 1) * C * 8 + (size_t)wl_bytes(nw)) return -42;
             }
+    // (5) XCD placement (plan.h: xcd_place) of a random tree, a chain with short side branches, and a star: every list a permutation of the
+    //     level-ordered one plus empty slots, every dependency at a lower workgroup id, every class within its cap
+    for (int kind = 0; kind < 3; kind++)
+        for (int cap : { 2, 8, 32 }) {
+            const int nF = kind == 2 ? 150 : 400;
+            std::vector<int> parent(nF, -1), nsb(nF), level(nF, 0);
+            unsigned r = 12345u + 77u * kind + (unsigned)cap;
+            auto rnd = [&](int m) { r = r * 1103515245u + 12345u; return (int)((r >> 8) % (unsigned)m); };
+            for (int t = 0; t < nF - 1; t++) {              // parents have higher ids
+                if (kind == 0) parent[t] = t + 1 + rnd(std::min(20, nF - 1 - t));
+                else if (kind == 1) parent[t] = t % 3 == 0 ? t + 1 : std::min(nF - 1, t + 3 - t % 3);
+                else parent[t] = nF - 1;
+                nsb[t] = 1 + rnd(30);
+            }
+            nsb[nF - 1] = 12;
+            for (int t = 0; t < nF - 1; t++) level[parent[t]] = std::max(level[parent[t]], level[t] + 1);
+            int top = 0; for (int t = 0; t < nF; t++) top = std::max(top, level[t]);
+            for (int l0 : { 0, 1, 2 }) {
+                std::vector<int> up, leaves;
+                for (int l = l0; l <= top; l++) for (int t = 0; t < nF; t++) if (level[t] == l) up.push_back(t);
+                if (l0 == 1) for (int t = 0; t < nF; t++) if (level[t] == 0) leaves.push_back(t);
+                const XcdLists x = xcd_place(up, leaves, parent.data(), nsb.data(), nF, cap, cap);
+                const int rc = xcd_check(x, up, leaves, parent.data(), nF, cap, cap);
+                if (rc) return -50 + rc;
+            }
+        }
     return 0;
 }
 

@@ -138,6 +138,8 @@ struct Context {
     // dependency flags instead of on kernel boundaries (kernels.hip.h: wait_flag / publish_flag)
     int persist_l0 = -1;                  // first level of the multi-level launch, -1: none
     int p_up_off = 0, p_up_n = 0, p_dn_off = 0, p_dn_n = 0, p_nt = 1024; size_t p_up_lds = 0, p_dn_lds = 0; long long p_up_full = 0; int p_dn_maxns = 0;
+    int x_up_off = 0, x_up_n = 0, x_dn_off = 0, x_dn_n = 0;      // the same two lists in XCD-placed order (option xcd_place; x_up_n = 0: not placed)
+    int x_leaf_off = 0, x_leaf_n = 0;                           // ... and level 0's fronts for its two launches (x_leaf_n = 0: level 0 keeps its own list)
     DBuf<int> d_flags, d_flevel, d_perm, d_epoch, d_marks;   // d_epoch: the step counter every dependency flag carries (kernels.hip.h wait_flag); d_marks: fronts regenerated by an incremental step
     int flag_stride = 0;                  // d_flags = three arrays of this many words: "factor done", "x done", "vectors ready" per front
     long long epoch_steps = 0;            // numeric phases enqueued since the counter was (re)started (rewind_epoch)
@@ -604,6 +606,26 @@ static void upload_plan(Context &c, hipStream_t s, const ShardLayout *lay = null
             for (int l = P.nLevels - 1; l >= l0; l--) { const LevelPlan &L = c.levels[l]; for (int k = 0; k < L.n_all; k++) tab.push_back(tab[L.all_off + k]); }
         }
     }
+    c.x_up_n = c.x_dn_n = c.x_leaf_n = 0;
+    if (c.persist_l0 >= 0 && g_opt.xcd_place) {
+        // XCD-placed copies of the multi-level lists (plan.h: xcd_place), and of level 0's when it is the one launch below them and holds
+        // small fronts only (the kernels that may run it return at once on an empty slot).  Classes hold what an XCD runs at once: its
+        // compute units times the workgroups per unit the launch's LDS allows.
+        int cus = 0;
+        HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, physical_device(t_slot)));
+        const int per_xcd = std::max(1, cus / 8);
+        auto per_cu = [](size_t lds, int nt) { return std::max(1, std::min(2048 / std::max(nt, 64), (int)((160 * 1024) / std::max<size_t>(lds, 1)))); };
+        const std::vector<int> up(tab.begin() + c.p_up_off, tab.begin() + c.p_up_off + c.p_up_n);
+        const LevelPlan &L0 = c.levels[0];
+        const bool leaf = c.persist_l0 == 1 && L0.n_big == 0 && L0.bs_gemv.grid == 0 && L0.bs_blk.grid == 0 && L0.n_small == L0.n_all;
+        const std::vector<int> leaves = leaf ? std::vector<int>(tab.begin() + L0.small_off, tab.begin() + L0.small_off + L0.n_small) : std::vector<int>();
+        // (leaves: an even share per class, rounded up to whole rounds of the XCD's units -- no class runs more rounds than before)
+        const int cap = per_xcd * per_cu(c.p_up_lds, c.p_nt), cap_leaf = per_xcd * (((int)leaves.size() + 8 * per_xcd - 1) / (8 * per_xcd));
+        const XcdLists x = xcd_place(up, leaves, P.f_parent.data(), P.f_nsb.data(), P.nF, cap, cap_leaf);
+        c.x_up_off = (int)tab.size(); c.x_up_n = (int)x.up.size(); tab.insert(tab.end(), x.up.begin(), x.up.end());
+        c.x_dn_off = (int)tab.size(); c.x_dn_n = (int)x.dn.size(); tab.insert(tab.end(), x.dn.begin(), x.dn.end());
+        c.x_leaf_off = (int)tab.size(); c.x_leaf_n = (int)x.leaf.size(); tab.insert(tab.end(), x.leaf.begin(), x.leaf.end());
+    }
     // (dependency flags / front levels: also used by the extended-plan batch step, whose tail fronts get levels of their own)
     {
         // No flag is ever reset: a finished front publishes the step number, which only grows (a flag that is read late or stale can then only
@@ -685,8 +707,9 @@ static void set_small_attr() {
 }
 
 // back substitution of one level: update-row products of the large fronts on many workgroups, then one workgroup per front
+// (list_off >= 0: the level's list of every front replaced by the list_n entries there -- an XCD-placed list of a level of small fronts only)
 template <class Tic, class Toc>
-static void launch_backsolve(Context &c, const LevelPlan &L, hipStream_t s, Tic tic, Toc toc, const int *tab = nullptr, UpdArgs upd = UpdArgs{}) {
+static void launch_backsolve(Context &c, const LevelPlan &L, hipStream_t s, Tic tic, Toc toc, const int *tab = nullptr, UpdArgs upd = UpdArgs{}, int list_off = -1, int list_n = 0) {
     if (!tab) tab = c.d_tab.p;
     if (!L.n_all) return;
     tic(K_BACKSOLVE);
@@ -694,7 +717,7 @@ static void launch_backsolve(Context &c, const LevelPlan &L, hipStream_t s, Tic 
         hipLaunchKernelGGL(k_backsolve_gemv, dim3(L.bs_gemv.grid), dim3(TPB), 0, s, c.dp, tab + L.bs_gemv.list_off, tab + L.bs_gemv.pre_off,
                            L.bs_gemv.n, c.d_pool.p, c.d_x.p);
     // wide fronts: chain + helper workgroups (k_backsolve_blk); the level's other fronts below
-    int n_all = L.n_all, all_off = L.all_off; size_t solve_lds = L.solve_lds;
+    int n_all = list_off >= 0 ? list_n : L.n_all, all_off = list_off >= 0 ? list_off : L.all_off; size_t solve_lds = L.solve_lds;
     if (L.bs_blk.grid > 0) {
         hipLaunchKernelGGL(k_backsolve_blk, dim3(L.bs_blk.grid), dim3(TPB), L.bs_blk_lds, s, c.dp, tab + L.bs_blk.list_off, tab + L.bs_blk.pre_off, L.bs_blk.n,
                            c.d_pool.p, c.d_x.p, c.d_dinv.p, c.d_bsb_flags.p, c.d_bsb_far.p, L.bs_gemv.grid > 0 ? 1 : 0, c.d_bad.p, upd);
@@ -733,21 +756,23 @@ static void enqueue_poison(Context &c, hipStream_t s, const int *list, int n, in
                        (int)(sizeof(UpdRec) / 4), what, c.d_pool.p, c.d_x.p);
 }
 static void launch_front_persist(Context &c, hipStream_t s) {
-    const int *list = c.d_tab.p + c.p_up_off;
+    const bool xp = c.x_up_n > 0;                          // the XCD-placed list (empty slots included)
+    const int *list = c.d_tab.p + (xp ? c.x_up_off : c.p_up_off), n = xp ? c.x_up_n : c.p_up_n;
     int *fl = c.d_flags.p;
     DevPlan dpe = persist_plan(c);
     if (g_opt.skip_flag_waits > 0) dpe.l0 = 1 << 30;       // debug (negative control of pool_poison): no front of this launch waits for its children
-    if (c.p_nt >= 1024) hipLaunchKernelGGL(k_front_small<1024>, dim3(c.p_up_n), dim3(1024), c.p_up_lds, s, dpe, list, c.d_pool.p, c.d_H.p, c.d_bad.p, c.p_up_full, fl, 1);
-    else if (c.p_nt >= 512) hipLaunchKernelGGL(k_front_small<512>, dim3(c.p_up_n), dim3(512), c.p_up_lds, s, dpe, list, c.d_pool.p, c.d_H.p, c.d_bad.p, c.p_up_full, fl, 1);
-    else hipLaunchKernelGGL(k_front_small<256>, dim3(c.p_up_n), dim3(256), c.p_up_lds, s, dpe, list, c.d_pool.p, c.d_H.p, c.d_bad.p, c.p_up_full, fl, 1);
+    if (c.p_nt >= 1024) hipLaunchKernelGGL(k_front_small<1024>, dim3(n), dim3(1024), c.p_up_lds, s, dpe, list, c.d_pool.p, c.d_H.p, c.d_bad.p, c.p_up_full, fl, 1);
+    else if (c.p_nt >= 512) hipLaunchKernelGGL(k_front_small<512>, dim3(n), dim3(512), c.p_up_lds, s, dpe, list, c.d_pool.p, c.d_H.p, c.d_bad.p, c.p_up_full, fl, 1);
+    else hipLaunchKernelGGL(k_front_small<256>, dim3(n), dim3(256), c.p_up_lds, s, dpe, list, c.d_pool.p, c.d_H.p, c.d_bad.p, c.p_up_full, fl, 1);
 }
 
-static void launch_front_small(Context &c, const LevelPlan &L, hipStream_t s, const int *tab = nullptr) {
+// (list_off >= 0: the list_n entries there instead of the level's own list -- an XCD-placed list)
+static void launch_front_small(Context &c, const LevelPlan &L, hipStream_t s, const int *tab = nullptr, int list_off = -1, int list_n = 0) {
     if (!tab) tab = c.d_tab.p;
-    const int nt = L.small_nt;
-    if (nt >= 1024) hipLaunchKernelGGL(k_front_small<1024>, dim3(L.n_small), dim3(1024), L.small_lds, s, c.dp, tab + L.small_off, c.d_pool.p, c.d_H.p, c.d_bad.p, L.full_limit, (int *)nullptr, 0);
-    else if (nt >= 512) hipLaunchKernelGGL(k_front_small<512>, dim3(L.n_small), dim3(512), L.small_lds, s, c.dp, tab + L.small_off, c.d_pool.p, c.d_H.p, c.d_bad.p, L.full_limit, (int *)nullptr, 0);
-    else hipLaunchKernelGGL(k_front_small<256>, dim3(L.n_small), dim3(256), L.small_lds, s, c.dp, tab + L.small_off, c.d_pool.p, c.d_H.p, c.d_bad.p, L.full_limit, (int *)nullptr, 0);
+    const int nt = L.small_nt, off = list_off >= 0 ? list_off : L.small_off, n = list_off >= 0 ? list_n : L.n_small;
+    if (nt >= 1024) hipLaunchKernelGGL(k_front_small<1024>, dim3(n), dim3(1024), L.small_lds, s, c.dp, tab + off, c.d_pool.p, c.d_H.p, c.d_bad.p, L.full_limit, (int *)nullptr, 0);
+    else if (nt >= 512) hipLaunchKernelGGL(k_front_small<512>, dim3(n), dim3(512), L.small_lds, s, c.dp, tab + off, c.d_pool.p, c.d_H.p, c.d_bad.p, L.full_limit, (int *)nullptr, 0);
+    else hipLaunchKernelGGL(k_front_small<256>, dim3(n), dim3(256), L.small_lds, s, c.dp, tab + off, c.d_pool.p, c.d_H.p, c.d_bad.p, L.full_limit, (int *)nullptr, 0);
 }
 
 // The big fronts of one level, 128 columns (an outer block of OBP panels) at a time: diagonal block in LDS with the inverses of its four
@@ -841,7 +866,11 @@ static void enqueue_numeric(Context &c, GraphPack &gp, hipStream_t s, hipEvent_t
     toc();
     if (ev) HIPCHECK(hipEventRecord(ev[1], s));
     const int l0 = c.persist_l0 >= 0 ? c.persist_l0 : P.nLevels;        // levels >= l0: one multi-level launch each way
-    for (int l = 0; l < l0; l++) { cur_level = l; enqueue_factor_level(c, c.levels[l], s, tic, toc); }
+    for (int l = 0; l < l0; l++) {
+        cur_level = l;
+        if (l == 0 && c.x_leaf_n > 0) { tic(K_FRONT_SMALL); launch_front_small(c, c.levels[0], s, nullptr, c.x_leaf_off, c.x_leaf_n); toc(); }      // (small fronts only)
+        else enqueue_factor_level(c, c.levels[l], s, tic, toc);
+    }
     cur_level = l0;
     if (l0 < P.nLevels) { tic(K_FRONT_SMALL); launch_front_persist(c, s); toc(); }
     if (ev) HIPCHECK(hipEventRecord(ev[2], s));
@@ -851,16 +880,19 @@ static void enqueue_numeric(Context &c, GraphPack &gp, hipStream_t s, hipEvent_t
     if (l0 < P.nLevels) {
         UpdArgs u = upd; if (l0 == 0) u.bad_out = io_host ? c.h_bad.p : nullptr;
         tic(K_BACKSOLVE);
+        const bool xp = c.x_dn_n > 0;                            // the XCD-placed list (empty slots included)
+        const int *dn = c.d_tab.p + (xp ? c.x_dn_off : c.p_dn_off), n_dn = xp ? c.x_dn_n : c.p_dn_n;
         if (g_opt.wave_backsolve && c.p_dn_maxns <= BSW_MAX_NS)
-            hipLaunchKernelGGL(k_backsolve_w, dim3(c.p_dn_n), dim3(TPB), c.p_dn_lds, s, persist_plan(c), c.d_tab.p + c.p_dn_off, c.d_pool.p, c.d_x.p, c.d_flags.p + c.flag_stride, c.d_bad.p, u);
+            hipLaunchKernelGGL(k_backsolve_w, dim3(n_dn), dim3(TPB), c.p_dn_lds, s, persist_plan(c), dn, c.d_pool.p, c.d_x.p, c.d_flags.p + c.flag_stride, c.d_bad.p, u);
         else
-            hipLaunchKernelGGL((k_backsolve_t<true>), dim3(c.p_dn_n), dim3(TPB), c.p_dn_lds, s, persist_plan(c), c.d_tab.p + c.p_dn_off, c.d_pool.p, c.d_x.p, 0, c.d_flags.p + c.flag_stride, 1, c.d_bad.p, u);
+            hipLaunchKernelGGL((k_backsolve_t<true>), dim3(n_dn), dim3(TPB), c.p_dn_lds, s, persist_plan(c), dn, c.d_pool.p, c.d_x.p, 0, c.d_flags.p + c.flag_stride, 1, c.d_bad.p, u);
         toc();
     }
     for (int l = l0 - 1; l >= 0; l--) {
         UpdArgs u = upd; if (l == 0) u.bad_out = io_host ? c.h_bad.p : nullptr;
         cur_level = l;
-        launch_backsolve(c, c.levels[l], s, tic, toc, nullptr, u);
+        if (l == 0 && c.x_leaf_n > 0) launch_backsolve(c, c.levels[0], s, tic, toc, nullptr, u, c.x_leaf_off, c.x_leaf_n);
+        else launch_backsolve(c, c.levels[l], s, tic, toc, nullptr, u);
     }
     if (ev) HIPCHECK(hipEventRecord(ev[3], s));
     HIPCHECK(hipGetLastError());

@@ -406,3 +406,111 @@ void build_gather_lists(Plan &P) {
 }
 
 }  // namespace asam
+
+namespace asam {
+
+// ---- XCD placement (plan.h) ------------------------------------------------------------------------------------------------------------
+XcdLists xcd_place(const std::vector<int> &up, const std::vector<int> &leaves, const int *parent, const int *nsb, int nF, int cap, int cap_leaf) {
+    constexpr int NX = 8;                                    // XCDs: workgroups b and b + 8 share one
+    const double HAND = 12.0, PERCOL = 0.19;                 // us per front of the up-sweep's path: amalgamate's model above (front stamps)
+    auto cost = [&](int t) { return HAND + PERCOL * 3.0 * (double)nsb[t]; };
+    XcdLists x;
+    const int n = (int)up.size();
+    std::vector<int> at((size_t)nF, -1);                     // front -> position in up
+    for (int i = 0; i < n; i++) at[up[i]] = i;
+    auto up_parent = [&](int i) { const int p = parent[up[i]]; return p >= 0 ? at[p] : -1; };
+    // critical path of each subtree (children come first in up) and the child on it
+    std::vector<double> cp(n, 0.0), best(n, 0.0);
+    std::vector<int> heavy(n, -1);
+    for (int i = 0; i < n; i++) {
+        cp[i] = cost(up[i]) + best[i];
+        const int p = up_parent(i);
+        if (p >= 0 && (heavy[p] < 0 || cp[i] > best[p])) { best[p] = cp[i]; heavy[p] = i; }
+    }
+    // heavy paths, costliest first (the root's: the critical path); each starts in the emptiest class and spills when a class is full
+    std::vector<int> heads;
+    for (int i = 0; i < n; i++) { const int p = up_parent(i); if (p < 0 || heavy[p] != i) heads.push_back(i); }
+    std::stable_sort(heads.begin(), heads.end(), [&](int a, int b) { return cp[a] > cp[b]; });
+    std::vector<int> cls(n, 0), cnt(NX, 0);
+    std::vector<double> load(NX, 0.0);
+    const bool capped = n <= NX * cap;                       // (otherwise no placement holds the launch: balance only)
+    auto room = [&](int c) { return !capped || cnt[c] < cap; };
+    auto emptiest = [&](const std::vector<int> &cn, const std::vector<double> &ld) {
+        int c = 0;
+        for (int k = 1; k < NX; k++) if (cn[k] < cn[c] || (cn[k] == cn[c] && ld[k] < ld[c])) c = k;
+        return c;
+    };
+    for (int h : heads) {
+        int c = emptiest(cnt, load);
+        for (int i = h; i >= 0; i = heavy[i]) {
+            while (!room(c)) c = (c + 1) % NX;
+            cls[i] = c; cnt[c]++; load[c] += cost(up[i]);
+        }
+    }
+    // slots: a front of class c takes the first id 8 k + c above its class's last one and above every dependency's
+    auto place = [&](bool down, std::vector<int> &list) {
+        std::vector<int> id(n, -1), dep(n, -1), cur(NX, 0);
+        int kmax = 0;
+        for (int j = 0; j < n; j++) {
+            const int i = down ? n - 1 - j : j, c = cls[i], p = up_parent(i);
+            const int need = (down ? (p >= 0 ? id[p] : -1) : dep[i]) + 1;
+            const int k = std::max(cur[c], need > c ? (need - c + NX - 1) / NX : 0);
+            id[i] = NX * k + c; cur[c] = k + 1; kmax = std::max(kmax, k + 1);
+            if (!down && p >= 0) dep[p] = std::max(dep[p], id[i]);
+        }
+        list.assign((size_t)NX * kmax, -1);
+        for (int i = 0; i < n; i++) list[id[i]] = up[i];
+    };
+    place(false, x.up);
+    place(true, x.dn);
+    // leaves: their parent's class (the parent's extend-add then reads them from its own L2 across the launch boundary), costliest first
+    std::vector<int> lv(leaves);
+    std::stable_sort(lv.begin(), lv.end(), [&](int a, int b) { return cost(a) > cost(b); });
+    std::vector<int> lcnt(NX, 0), lslot(lv.size());
+    std::vector<double> lload(NX, 0.0);
+    const bool lcapped = (long long)lv.size() <= (long long)NX * cap_leaf;
+    int kmax = 0;
+    for (size_t j = 0; j < lv.size(); j++) {
+        const int p = parent[lv[j]] >= 0 ? at[parent[lv[j]]] : -1;
+        int c = p >= 0 ? cls[p] : emptiest(lcnt, lload);
+        while (lcapped && lcnt[c] >= cap_leaf) c = (c + 1) % NX;
+        lslot[j] = NX * lcnt[c] + c; lcnt[c]++; lload[c] += cost(lv[j]); kmax = std::max(kmax, lcnt[c]);
+    }
+    x.leaf.assign((size_t)NX * kmax, -1);
+    for (size_t j = 0; j < lv.size(); j++) x.leaf[lslot[j]] = lv[j];
+    return x;
+}
+
+int xcd_check(const XcdLists &x, const std::vector<int> &up, const std::vector<int> &leaves, const int *parent, int nF, int cap, int cap_leaf) {
+    constexpr int NX = 8;
+    auto same_set = [&](const std::vector<int> &list, const std::vector<int> &old) {
+        if (list.size() % NX) return false;
+        std::vector<int> a, b(old);
+        for (int t : list) { if (t >= 0) a.push_back(t); else if (t != -1) return false; }
+        std::sort(a.begin(), a.end()); std::sort(b.begin(), b.end());
+        return a == b;
+    };
+    if (!same_set(x.up, up)) return -1;
+    if (!same_set(x.dn, up)) return -2;
+    if (!same_set(x.leaf, leaves)) return -3;
+    std::vector<int> iu((size_t)nF, -1), id((size_t)nF, -1);
+    for (size_t b = 0; b < x.up.size(); b++) if (x.up[b] >= 0) iu[x.up[b]] = (int)b;
+    for (size_t b = 0; b < x.dn.size(); b++) if (x.dn[b] >= 0) id[x.dn[b]] = (int)b;
+    for (int t : up) {
+        const int p = parent[t];
+        if (p >= 0 && iu[p] >= 0 && iu[t] >= iu[p]) return -4;          // up: every child below its parent
+        if (p >= 0 && id[p] >= 0 && id[t] <= id[p]) return -5;          // down: every parent below its children
+        if (iu[t] % NX != id[t] % NX) return -6;                        // one class per front in both sweeps
+    }
+    auto fits = [&](const std::vector<int> &list, size_t n, int c) {
+        if (n > (size_t)NX * c) return true;
+        std::vector<int> cnt(NX, 0);
+        for (size_t b = 0; b < list.size(); b++) if (list[b] >= 0 && ++cnt[b % NX] > c) return false;
+        return true;
+    };
+    if (!fits(x.up, up.size(), cap) || !fits(x.dn, up.size(), cap)) return -7;
+    if (!fits(x.leaf, leaves.size(), cap_leaf)) return -8;
+    return 0;
+}
+
+}  // namespace asam

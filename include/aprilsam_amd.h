@@ -342,6 +342,9 @@ void aprilsam_amd_clear_error(void);
  *                       profiles/r05_flag_soak.txt; the soak of the corrected build is profiles/r06_flag_soak.txt);
  *                       0 = one launch per level, no flags -- the conservative setting, M3500 then
  *                       costs about a quarter more per iteration (what the multi-level launches bought when they were introduced: 0.366 -> 0.294 ms)
+ *   "xcd_place"         1 (default): the lists of those launches, and of the level-0 launches below them, are ordered so that a front
+ *                       runs on the XCD of the child on its critical path (workgroups b and b + 8 share an XCD: observed, not promised);
+ *                       speed only, results bitwise the same; 0 = level by level
  *   "blk_backsolve"     1 (default): multi-workgroup fronts are back-substituted 128 columns at a time by a chain
  *                       workgroup + helper workgroups, with the inverse diagonal blocks the factorisation left behind; 0 = one
  *                       workgroup per front, 32 columns at a time
@@ -619,6 +622,10 @@ long long aprilsam_amd_plan_query(const aprilsam_amd_plan_t *plan, const char *w
 /* Ownership map and exchange lists of a `world`-rank sharded run of this plan, as aprilsam_amd_shard_info reports them
  * (what: 1 transfers x6, 2 broadcasts x5, 3 owner per front, 4 modelled critical path x4); host logic only. */
 long long aprilsam_amd_shard_plan(const aprilsam_amd_plan_t *plan, int world, int what, long long *out, long long cap);
+/* XCD placement of the batch step's multi-level launches for an assembly tree (parent, level, own pose blocks per front): the fronts
+ * of levels >= l0 (and, when l0 == 1, the level-0 leaves) as padded workgroup lists, -1 = empty slot.  which: 0 up-sweep list,
+ * 1 down-sweep list, 2 leaf list (returns the length; fills out up to out_cap), 3 the self-check (0 or a negative code); host logic only. */
+int aprilsam_amd_xcd_place(int nF, const int *parent, const int *level, const int *nsb, int l0, int cap, int cap_leaf, int which, int *out, int out_cap);
 void aprilsam_amd_free(void *p);
 
 /* Host logic behind the incremental path: the reference's elimination order (aprilsam.c:999-1249, restated

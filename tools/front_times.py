@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""debug: per-level phase breakdown of k_front_small (needs APRILSAM_AMD_KPROF=1)"""
+"""debug: per-level phase breakdown of k_front_small (needs APRILSAM_AMD_KPROF=1); then the after-wait extend-add of every parent split by
+whether its children ran on its XCD (stamp slot 12 = 1 + XCC id), and the XCD of each hop of the stamped critical path.
+APRILSAM_AMD_XCD_PLACE=0 / 1 compares the level-by-level lists with the XCD-placed ones."""
 import ctypes as C, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -30,3 +32,33 @@ for l in range(P.nLevels):
     big = max(fr, key=lambda t: T[t, 3] - T[t, 0])
     print(f"level {l}: {len(fr):4d} fronts  span {span:7.1f} us | mean asm {a[:,0].mean():6.1f} fac {a[:,1].mean():6.1f} store {a[:,2].mean():6.1f} | "
           f"slowest nsb={P.front_nsb[big]} nub={P.front_nub[big]} nch={P.ch_ptr[big+1]-P.ch_ptr[big]}: asm {T[big,1]-T[big,0]:.1f} fac {T[big,2]-T[big,1]:.1f} store {T[big,3]-T[big,2]:.1f} | chain+far {buf[big,8]*0.01:.1f} next-block syrk {buf[big,9]*0.01:.1f} (pure look-ahead chains {buf[big,15]*0.01:.2f} us = {buf[big,10]} cycles) | asm: zero {(buf[big,4]-buf[big,0])*0.01:.1f} dest {(buf[big,5]-buf[big,4])*0.01:.1f} fill {(buf[big,6]-buf[big,5])*0.01:.1f} (n={buf[big,7]}) rest {(buf[big,1]-buf[big,6])*0.01:.1f} (after wait {(buf[big,1]-buf[big,11])*0.01 if buf[big,11] else 0:.1f})")
+
+# XCD split: after-wait extend-add per parent (wait seen -> assembly done), by where its children ran (slot 12 = 1 + XCC id)
+X = buf[:, 12]
+if X.any():
+    groups = {}
+    for t in range(nF):
+        if P.front_level[t] < 1 or not buf[t, 11] or not X[t]:
+            continue
+        kids = [c for c in P.ch_idx[P.ch_ptr[t]:P.ch_ptr[t + 1]] if X[c]]
+        if not kids:
+            continue
+        last = max(kids, key=lambda c: buf[c, 3])              # the child the wait was for
+        frac = sum(X[c] == X[t] for c in kids) / len(kids)
+        key = ("level 1" if P.front_level[t] == 1 else "levels 2+", "all" if frac == 1 else ("none" if frac == 0 else "some"))
+        groups.setdefault(key, []).append((buf[t, 1] - buf[t, 11]) * 0.01)
+        groups.setdefault((key[0], "last child " + ("same" if X[last] == X[t] else "cross")), []).append((buf[t, 1] - buf[t, 11]) * 0.01)
+    for key in sorted(groups):
+        v = np.array(groups[key])
+        print(f"after wait, {key[0]:9s} children on the parent's XCD: {key[1]:17s} n={len(v):3d}  mean {v.mean():5.2f} us  median {np.median(v):5.2f} us")
+    # the stamped critical path: from the root, the child that finished last
+    t = int(max(range(nF), key=lambda u: buf[u, 3]))
+    hops = []
+    while True:
+        kids = [c for c in P.ch_idx[P.ch_ptr[t]:P.ch_ptr[t + 1]] if X[c]]
+        if not kids:
+            break
+        c = int(max(kids, key=lambda u: buf[u, 3]))
+        hops.append(f"L{P.front_level[t]}:{'same' if X[c] == X[t] else 'cross'}({(buf[t, 1] - buf[t, 11]) * 0.01:.1f})")
+        t = c
+    print("critical path (level: child's XCD vs parent's, after-wait us):", " ".join(hops))
