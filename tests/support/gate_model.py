@@ -39,6 +39,17 @@ def gate(states, a, b, z, W, joint):
     return d2, S
 
 
+def gate_inputs(arr, n, seed):
+    """n random candidates on distinct poses of arr: a, b, z, W [n, 9] (symmetric positive definite)"""
+    rng = np.random.default_rng(seed)
+    N = len(arr[0])
+    a = rng.integers(0, N, n).astype(np.int32); b = (a + 1 + rng.integers(0, N - 1, n)).astype(np.int32) % N
+    z = rng.normal(size=(n, 3)) * [2, 2, 1]
+    L = rng.normal(size=(n, 3, 3)) * 0.3 + np.eye(3) * 3
+    W = np.einsum("nij,nkj->nik", L, L).reshape(n, 9)
+    return a, b, z, W
+
+
 def false_candidates(arr, closures, n, min_gap=50, seed=7):
     """n candidates that each take a true closure's z and W and place them on a wrong pair of poses at least min_gap apart"""
     states, fa, fb, z, W = arr

@@ -8,13 +8,15 @@ import numpy as np
 import pytest
 
 from aprilsam_amd import datasets, harness
-from tests.support.gate_model import CHI2_3_999, gate, held_out_closures
+from tests.support.gate_model import CHI2_3_999, gate, gate_inputs as _gate_inputs, held_out_closures
 from tests.support.marginal_cases import case_arrays, factor_pairs
 from tests.support.selinv_model import dense_system, sparse_system, system_blocks
+from tests.support.sigma_compare import (SIG_RTOL, Recorder, compare_dense_any as _compare_dense, demo_checkpoints, dense as _dense,
+                                         random_pairs as _pairs, ref_joint as _ref_joint)
 from tests.test_pathsolve_model import FALSE_REJECTED, GATE_ITERS, TRUE_ACCEPTED, m3500_gate_scenario
 
 pytestmark = pytest.mark.gpu
-SIG_RTOL = 1e-9          # against the dense inverse, of the two poses' block rows' largest entry (tests/test_gpu_marginals.py)
+# SIG_RTOL = 1e-9 against the dense inverse, of the two poses' block rows' largest entry (tests/support/sigma_compare.py)
 SPLU_RTOL = 1e-8         # against splu solves (10^5-pose lattice; tests/test_gpu_marginals.py)
 GATE_RTOL = 1e-9         # d2 and S against the numpy model
 
@@ -25,33 +27,6 @@ def _solved(lib, arr, steps=1):
         g.cholesky(p)
         assert p.stats()["not_spd"] == 0
     return g, p
-
-
-def _pairs(N, seed, k=100):
-    rng = np.random.default_rng(seed)
-    a = rng.integers(0, N, k).astype(np.int32); b = rng.integers(0, N, k).astype(np.int32)
-    return np.r_[a, b, a[:10]], np.r_[b, a, a[:10]]
-
-
-def _dense(g, p, lam_nodes=None):
-    states, fa, fb, z, W = g.arrays()
-    Aii, Aab = system_blocks(g.l_points(), fa, fb, z, W, p.c.tikhanov, lam_nodes)
-    Sig = np.linalg.inv(dense_system(Aii, Aab, fa, fb))
-    N = len(states)
-    return Sig, np.abs(Sig).reshape(N, 3, 3 * N).max(axis=(1, 2))
-
-
-def _ref_joint(Sig, a, b):
-    return np.stack([Sig[np.ix_(np.r_[3 * x:3 * x + 3, 3 * y:3 * y + 3], np.r_[3 * x:3 * x + 3, 3 * y:3 * y + 3])] for x, y in zip(a, b)])
-
-
-def _compare_dense(g, p, a, b, lam_nodes=None):
-    Sig, scale = _dense(g, p, lam_nodes)
-    J = g.marginals_joint_any(p, a, b)
-    assert np.isfinite(J).all()
-    err = np.abs(J - _ref_joint(Sig, a, b)).reshape(len(a), 36).max(axis=1) / np.maximum(scale[a], scale[b])
-    assert err.max() < SIG_RTOL, err.max()
-    return J
 
 
 def _heldout_m3500():
@@ -128,42 +103,20 @@ def test_lattice_1m_agrees_with_the_selected_inversion_and_runs_none(lib):
     p.destroy(); g.destroy()
 
 
-class _Recorder:
-    """lib stand-in for harness.run_demo that keeps the graph it makes"""
-    def __init__(self, lib):
-        self.lib, self.graphs = lib, []
-
-    def __getattr__(self, k):
-        return getattr(self.lib, k)
-
-    def new_graph(self):
-        g = self.lib.new_graph(); self.graphs.append(g)
-        return g
-
-
 def test_incremental_demo_checkpoints_and_non_interference(lib):
     """First 600 steps of the M3500 incremental demo, the checkpoints of tests/test_gpu_marginals.py: joint_any of random pairs, the
     newest pose against old ones, and a == b, against inv(A(l_point)) with lambda on the poses of the last batch step; the chi^2 trace
     and states bitwise those of the run without the calls."""
     arr = datasets.m3500_arrays()
     plain = harness.run_demo(lib, arr, max_poses=600, record_states_every=50)
-    rec = _Recorder(lib)
-    seen = dict(batch=0, replanned=0, updated=0, fast=0, n_batch=0)
-    closes = {max(int(a), int(b)) for a, b in zip(arr[1], arr[2]) if b >= 0 and abs(int(a) - int(b)) > 1}
+    rec = Recorder(lib)
 
-    def on_step(k, p, was_batch):
-        g = rec.graphs[-1]
-        st = p.stats()
-        if was_batch:
-            seen["n_batch"] = k + 1
-        kind = "batch" if was_batch else "replanned" if st["inc_replanned"] == 1 else "updated" if st["inc_fronts_updated"] > 0 else "fast"
-        if kind in ("batch", "replanned") or (kind == "updated" and seen["updated"] < 5) or \
-                (kind == "fast" and (k % 50 == 0 or (k in closes and seen["fast"] < 12))):
-            N = g.n_nodes
-            a, b = _pairs(N, k, 20)
-            a = np.r_[a, np.full(min(N, 20), N - 1)].astype(np.int32); b = np.r_[b, np.arange(min(N, 20))].astype(np.int32)
-            _compare_dense(g, p, a, b, None if was_batch else seen["n_batch"])
-            seen[kind] += 1
+    def check(g, p, k, lam_nodes):
+        N = g.n_nodes
+        a, b = _pairs(N, k, 20)
+        a = np.r_[a, np.full(min(N, 20), N - 1)].astype(np.int32); b = np.r_[b, np.arange(min(N, 20))].astype(np.int32)
+        _compare_dense(g, p, a, b, lam_nodes)
+    on_step, seen = demo_checkpoints(rec, arr, check)
     res = harness.run_demo(rec, arr, max_poses=600, record_states_every=50, on_step=on_step)
     assert seen["batch"] >= 5 and seen["updated"] >= 1 and seen["fast"] >= 12, seen
     assert res["chi2"].tobytes() == plain["chi2"].tobytes()
@@ -179,16 +132,6 @@ def test_after_batch_resident(lib):
     a, b = _pairs(len(arr[0]), 9)
     _compare_dense(g, p, a, b)
     p.destroy(); g.destroy()
-
-
-def _gate_inputs(arr, n, seed):
-    rng = np.random.default_rng(seed)
-    N = len(arr[0])
-    a = rng.integers(0, N, n).astype(np.int32); b = (a + 1 + rng.integers(0, N - 1, n)).astype(np.int32) % N
-    z = rng.normal(size=(n, 3)) * [2, 2, 1]
-    L = rng.normal(size=(n, 3, 3)) * 0.3 + np.eye(3) * 3
-    W = np.einsum("nij,nkj->nik", L, L).reshape(n, 9)
-    return a, b, z, W
 
 
 def test_gate_matches_the_model(lib):

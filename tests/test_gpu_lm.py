@@ -44,12 +44,12 @@ def _accepted_monotone(r):
     return bool(np.all(np.diff(np.concatenate([[r["F_initial"]], acc])) <= 0))
 
 
-@pytest.mark.parametrize("name,make,iters", CASES, ids=[c[0] for c in CASES])
-def test_parity_with_the_model(lib, name, make, iters):
-    x0, plain = make()
+def _parity_with_the_model(lib, x0, plain, iters, name="", **lm_opts):
+    """aprilsam_amd_optimize_lm against tests/support/lm_model.py under the library options in force: decisions exact, lambda at 1e-6,
+    F and the states at 1e-9.  Returns the trace and the final states"""
     ref = M.optimize(x0, plain, max_iters=iters)
     g = _graph(lib, x0, *plain); p = lib.new_param()
-    r = g.optimize_lm(p, trace=True, max_iters=iters)
+    r = g.optimize_lm(p, trace=True, max_iters=iters, **lm_opts)
     assert abs(r["F_initial"] - ref["F_initial"]) <= 1e-12 * abs(ref["F_initial"])
     n = M.comparable_rows(ref["trace"], ref["F_initial"])
     assert n >= 1, name
@@ -66,16 +66,56 @@ def test_parity_with_the_model(lib, name, make, iters):
         assert _ang(g.states(), ref["x"]) < 1e-9, (name, _ang(g.states(), ref["x"]))
     # the states after the comparable prefix (trial buffer and commit): a run cut at n iterations against the model's x after n
     gn = _graph(lib, x0, *plain); pn = lib.new_param()
-    rn = gn.optimize_lm(pn, trace=True, max_iters=n)
+    rn = gn.optimize_lm(pn, trace=True, max_iters=n, **lm_opts)
     assert rn["iterations"] == n and rn["trace"].tobytes() == t[:n].tobytes()
     assert _ang(gn.states(), ref["xs"][n - 1]) < 1e-9, (name, n, _ang(gn.states(), ref["xs"][n - 1]))
     pn.destroy(); gn.destroy()
     assert _accepted_monotone(r), name
     assert r["iterations"] <= iters and r["status"] in (1, 2, 3, 4)
+    out = (r["trace"].copy(), g.states())
     p.destroy(); g.destroy()
+    return out
 
 
-def test_monotone_with_max_mixture_factors(lib):
+@pytest.mark.parametrize("name,make,iters", CASES, ids=[c[0] for c in CASES])
+def test_parity_with_the_model(lib, name, make, iters):
+    x0, plain = make()
+    _parity_with_the_model(lib, x0, plain, iters, name)
+
+
+# The iteration under the batch step's kernel paths: without its captured graph (use_graph=0, alone and with stop tests every 7th
+# iteration), fronts on the multi-workgroup and panel paths, both back-substitution forms, per-level launches, unplaced fronts, and the
+# front pool poisoned / guard-banded before every factorisation -- a rejected step re-factorises over the previous step's numbers.
+LM_PATHS = [dict(use_graph=0), dict(small_lds_kb=0), dict(small_lds_kb=48), dict(wave_backsolve=0), dict(blk_backsolve=0, small_lds_kb=0),
+            dict(persist=0), dict(xcd_place=0), dict(pool_poison=1), dict(pool_guard=64), dict(use_graph=0, check_every=7)]
+# the same kernels in the same order as the default run: the trace and the states bitwise
+LM_BITWISE = [dict(use_graph=0), dict(xcd_place=0), dict(pool_poison=1), dict(pool_guard=64)]
+
+
+def _ids(o):
+    return ",".join(f"{k}={v}" for k, v in o.items())
+
+
+def _split(opts):
+    """(library options, optimize_lm options)"""
+    return {k: v for k, v in opts.items() if k != "check_every"}, {k: v for k, v in opts.items() if k == "check_every"}
+
+
+@pytest.mark.parametrize("opts", LM_PATHS, ids=_ids)
+@pytest.mark.parametrize("name,make,iters", [CASES[0], CASES[4]], ids=[CASES[0][0], CASES[4][0]])
+def test_parity_with_the_model_on_every_path(lib, name, make, iters, opts):
+    x0, plain = make()
+    lo, lm = _split(opts)
+    with lib.options(**lo):
+        t, x = _parity_with_the_model(lib, x0, plain, iters, name, **lm)
+    if opts in LM_BITWISE:
+        g = _graph(lib, x0, *plain); p = lib.new_param()
+        r = g.optimize_lm(p, trace=True, max_iters=iters)
+        assert r["trace"].tobytes() == t.tobytes() and g.states().tobytes() == x.tobytes(), (name, opts)
+        p.destroy(); g.destroy()
+
+
+def _monotone_with_max_mixture_factors(lib):
     states, base, loops, outliers = maxmix_model.m3500_outliers()
     g = maxmix_model.build(lib, states, base, loops + outliers, as_max=True)
     p = lib.new_param()
@@ -90,6 +130,20 @@ def test_monotone_with_max_mixture_factors(lib):
     want = [maxmix_model.select(x[a], x[b], zs, Ws, lw) for a, b, zs, Ws, lw in mixes]
     assert list(sel) == want
     p.destroy(); g.destroy()
+    return r["trace"].copy(), x
+
+
+def test_monotone_with_max_mixture_factors(lib):
+    _monotone_with_max_mixture_factors(lib)
+
+
+@pytest.mark.parametrize("opts", [dict(use_graph=0), dict(small_lds_kb=0)], ids=_ids)
+def test_monotone_with_max_mixture_factors_on_other_paths(lib, opts):
+    with lib.options(**opts):
+        t, x = _monotone_with_max_mixture_factors(lib)
+    if opts in LM_BITWISE:                                      # (use_graph=0: the kernels and their order are the default run's)
+        t0, x0 = _monotone_with_max_mixture_factors(lib)
+        assert t.tobytes() == t0.tobytes() and x.tobytes() == x0.tobytes()
 
 
 def test_plain_step_diverges_where_lm_does_not(lib):

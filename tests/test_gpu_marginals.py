@@ -10,14 +10,12 @@ import pytest
 from aprilsam_amd import datasets, harness
 from tests.support.marginal_cases import case_arrays, factor_pairs, tutorial_arrays
 from tests.support.marginal_identity import identity_residual
-from tests.support.normal_eq import normal_equation_residual
 from tests.support.selinv_model import dense_system, sparse_system, system_blocks
+from tests.support.sigma_compare import SIG_RTOL, Recorder, compare_dense as _compare_dense, demo_checkpoints
 
 pytestmark = pytest.mark.gpu
-# |GPU - reference| / (largest |entry| of the pose's block row of Sigma).  Calibration on the CPU, two independent references of the
-# same system: the dense inverse and scipy splu solves disagree by up to 7e-12 (M3500) and 2.2e-11 (lattice K = 60); splu with two
-# orderings (COLAMD, MMD on A + A') by 7e-11 (K = 60) and 3.4e-10 (K = 120) -- the figure grows with the lattice's condition number.
-SIG_RTOL = 1e-9          # against the dense inverse (every graph up to 10 800 unknowns)
+# |GPU - reference| / (largest |entry| of the pose's block row of Sigma).  SIG_RTOL = 1e-9 against the dense inverse and its
+# calibration on the CPU: tests/support/sigma_compare.py.  splu with two orderings (COLAMD, MMD on A + A') disagrees by 3.4e-10 at K = 120.
 SPLU_RTOL = 1e-8         # against splu solves (lattices K = 120, 316): 30 x the K = 120 disagreement of the two CPU references
 IDENT_RTOL = 1e-9        # identity residual (relative to the terms it sums)
 
@@ -28,34 +26,6 @@ def _solved(lib, arr, steps=1):
         g.cholesky(p)
         assert p.stats()["not_spd"] == 0
     return g, p
-
-
-def _ref_blocks(Sig, N, fa, fb):
-    a, b = factor_pairs(fa, fb)
-    diag = np.stack([Sig[3 * i:3 * i + 3, 3 * i:3 * i + 3] for i in range(N)])
-    joint = np.stack([Sig[np.ix_(np.r_[3 * x:3 * x + 3, 3 * y:3 * y + 3], np.r_[3 * x:3 * x + 3, 3 * y:3 * y + 3])] for x, y in zip(a, b)]) \
-        if len(a) else np.zeros((0, 6, 6))
-    return diag, joint
-
-
-def _compare_dense(g, p, lam_nodes=None):
-    states, fa, fb, z, W = g.arrays()
-    lp = g.l_points(); N = len(lp)
-    Aii, Aab = system_blocks(lp, fa, fb, z, W, p.c.tikhanov, lam_nodes)
-    Sig = np.linalg.inv(dense_system(Aii, Aab, fa, fb))
-    rd, rj = _ref_blocks(Sig, N, fa, fb)
-    scale = np.abs(Sig).reshape(N, 3, 3 * N).max(axis=(1, 2))
-    d = g.marginals(p)
-    err = (np.abs(d - rd).reshape(N, 9).max(axis=1) / scale).max()
-    a, b = factor_pairs(fa, fb)
-    worst = err
-    if len(a):
-        j = g.marginals_joint(p, a, b)
-        assert not np.isnan(j).any()
-        ej = np.abs(j - rj).reshape(len(a), 36).max(axis=1) / np.maximum(scale[a], scale[b])
-        worst = max(worst, ej.max())
-    assert worst < SIG_RTOL, worst
-    return worst
 
 
 @pytest.mark.parametrize("name", ["tutorial", "random0", "random1", "random2", "random3", "lattice6", "lattice24", "lattice60", "m3500"])
@@ -165,19 +135,6 @@ def test_params_on_two_slots(lib):
     assert out[0][2:] == out[1][2:]
 
 
-class _Recorder:
-    """lib stand-in for harness.run_demo that keeps the graph it makes"""
-    def __init__(self, lib):
-        self.lib, self.graphs = lib, []
-
-    def __getattr__(self, k):
-        return getattr(self.lib, k)
-
-    def new_graph(self):
-        g = self.lib.new_graph(); self.graphs.append(g)
-        return g
-
-
 def test_incremental_demo_checkpoints_and_non_interference(lib):
     """First 600 steps of the M3500 incremental demo.  Sigma = inv(A(l_point)) with lambda on the poses of the last batch step after
     every batch step (first pose, fall-backs), every re-planned step, the first steps that took low-rank updates of their root path,
@@ -185,22 +142,8 @@ def test_incremental_demo_checkpoints_and_non_interference(lib):
     states are bitwise those of the run without any marginals call."""
     arr = datasets.m3500_arrays()
     plain = harness.run_demo(lib, arr, max_poses=600, record_states_every=50)
-    rec = _Recorder(lib)
-    seen = dict(batch=0, replanned=0, updated=0, fast=0, n_batch=0)
-    closes = {max(int(a), int(b)) for a, b in zip(arr[1], arr[2]) if b >= 0 and abs(int(a) - int(b)) > 1}
-
-    def on_step(k, p, was_batch):
-        g = rec.graphs[-1]
-        st = p.stats()
-        if was_batch:
-            seen["n_batch"] = k + 1
-            out = normal_equation_residual(g.l_points(), *g.arrays()[1:], g.deltas(), p.c.tikhanov)
-            assert out["rel_max"] < 1e-10, out
-        kind = "batch" if was_batch else "replanned" if st["inc_replanned"] == 1 else "updated" if st["inc_fronts_updated"] > 0 else "fast"
-        if kind in ("batch", "replanned") or (kind == "updated" and seen["updated"] < 5) or \
-                (kind == "fast" and (k % 50 == 0 or (k in closes and seen["fast"] < 12))):
-            _compare_dense(g, p, None if was_batch else seen["n_batch"])
-            seen[kind] += 1
+    rec = Recorder(lib)
+    on_step, seen = demo_checkpoints(rec, arr, lambda g, p, k, lam_nodes: _compare_dense(g, p, lam_nodes), batch_residual=True)
     res = harness.run_demo(rec, arr, max_poses=600, record_states_every=50, on_step=on_step)
     assert seen["batch"] >= 5 and seen["updated"] >= 1 and seen["fast"] >= 12, seen
     assert res["chi2"].tobytes() == plain["chi2"].tobytes()

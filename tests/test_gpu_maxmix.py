@@ -146,6 +146,25 @@ def test_replace_by_selected_m3500(lib):
     _replace_by_selected(lib, states, base, loops + outl)
 
 
+# The selected component is written into the factor slots by its own kernel before k_linearize_t reads them: the LDS-staged write-out
+# of the linearisation, the per-level and no-graph forms, the multi-workgroup fronts and a new plan per call with both components
+# selected.  Tolerance-free: the max-mixture graph and the plain graph of the selected components run under the same options.
+BATCH_PATHS = [dict(linearize_staged_min=0), dict(use_graph=0), dict(small_lds_kb=0), dict(persist=0), dict(batch_extend=0),
+               dict(linearize_staged_min=0, use_graph=0)]
+INC_FORMS = [{"inc_one": 0, "inc_tail": 0}, {"inc_multi": 0}, {"inc_inline": 0}, {"inc_lazy_states": 0}, {"inc_update": 0}, {"tail_poses": 8}]
+
+
+def _ids(o):
+    return ",".join(f"{k}={v}" for k, v in o.items())
+
+
+@pytest.mark.parametrize("opts", BATCH_PATHS, ids=_ids)
+def test_replace_by_selected_m3500_on_other_paths(lib, opts):
+    states, base, loops, outl = mm.m3500_outliers()
+    with lib.options(**opts):
+        _replace_by_selected(lib, states, base, loops + outl)
+
+
 def test_replace_by_selected_lattice_100k(lib):
     states, fa, fb, z, W = lib.lattice_arrays(316)
     every = np.zeros(len(fa), bool); every[::10] = True; every &= fb >= 0
@@ -157,34 +176,29 @@ def test_replace_by_selected_lattice_100k(lib):
     _replace_by_selected(lib, states, base, edges)
 
 
-def test_incremental_parity_with_reference(lib, reflib, helper):
-    """growth in the style of test_gpu_parity._random_growth: loop closures and injected outliers as max factors, on the library
-    (native) and on the reference (checker factor): states at every step, selections of the new factors"""
+def _incremental_growth(L, add_max, selections, steps=160):
+    """growth in the style of test_gpu_parity._random_growth on L: loop closures and injected outliers as max factors.
+    add_max(g, a, b, zs, Ws, lw) adds one; selections(g, p) returns the components selected in every max factor so far.
+    Returns the states and the selections after every step"""
     rng = np.random.default_rng(11)
     truth = [np.zeros(3)]
-    sides = []
-    for L in (lib, reflib):
-        g = L.new_graph(); p = L.new_param(nthreshold=12, delta_xy=0.05, delta_theta=0.05)
-        g.add_node_xyt(truth[0]); g.add_factor_xytpos(0, [0, 0, 0], datasets.PRIOR_W)
-        g.cholesky(p)
-        sides.append((L, g, p))
-    rec = []
+    g = L.new_graph(); p = L.new_param(nthreshold=12, delta_xy=0.05, delta_theta=0.05)
+    g.add_node_xyt(truth[0]); g.add_factor_xytpos(0, [0, 0, 0], datasets.PRIOR_W)
+    g.cholesky(p)
 
     def rel(a, b):
         c, s = np.cos(a[2]), np.sin(a[2]); dx, dy = b[0] - a[0], b[1] - a[1]
         return np.array([c * dx + s * dy, -s * dx + c * dy, b[2] - a[2]])
 
     Wl = np.diag([40.0, 40.0, 120.0])
-    add_ref = mm.helper_adder(reflib, helper, 99, rec)
-    changed_sel = 0
-    for step in range(160):
+    out = []
+    for step in range(steps):
         last = truth[-1]
         new = np.array([last[0] + np.cos(last[2]) * 0.8, last[1] + np.sin(last[2]) * 0.8, last[2] + rng.uniform(-0.6, 0.6)])
         truth.append(new); n = len(truth) - 1
         init = new + rng.normal(0, [0.15, 0.15, 0.04])
         zo = rel(truth[n - 1], new) + rng.normal(0, [0.03, 0.03, 0.01])
-        for L, g, p in sides:
-            g.add_node_xyt(init); g.add_factor_xyt(n - 1, n, zo, Wl)
+        g.add_node_xyt(init); g.add_factor_xyt(n - 1, n, zo, Wl)
         closures = []
         if n > 4 and rng.random() < 0.5:
             o = int(rng.integers(0, n - 1))
@@ -194,22 +208,50 @@ def test_incremental_parity_with_reference(lib, reflib, helper):
             closures.append((o, n, rng.uniform([-5, -5, -3], [5, 5, 3])))
         for a, b, zz in closures:
             zs, Ws, lw = mm.two_component(zz, Wl)
-            sides[0][1].add_factor_max(a, b, zs, Ws, lw)
-            add_ref(sides[1][1], a, b, zs, Ws, lw)
-        for L, g, p in sides:
-            p.c.batch_time = 1e300
-            g.cholesky_inc(p)
-        sl, sr = sides[0][1].states(), sides[1][1].states()
-        assert np.max(np.abs(sl - sr)) < 1e-8, (step, np.max(np.abs(sl - sr)))
-        g = sides[0][1]
+            add_max(g, a, b, zs, Ws, lw)
+        p.c.batch_time = 1e300
+        g.cholesky_inc(p)
+        out.append((g.states(), np.array(selections(g, p))))
+    p.destroy(); g.destroy()
+    return out
+
+
+def _incremental_ours(lib):
+    def selections(g, p):
         mx = [i for i in range(g.n_factors) if g.factor(i).type == 3]
-        sel = g.max_selected(sides[0][2], mx)
-        ref_sel = np.array([helper.mm_last(f) for f in rec])
+        return g.max_selected(p, mx)
+    return _incremental_growth(lib, lambda g, a, b, zs, Ws, lw: g.add_factor_max(a, b, zs, Ws, lw), selections)
+
+
+@pytest.fixture(scope="module")
+def incremental_reference(reflib, helper):
+    """the unmodified reference driving the checker factor through the same growth (it has no options: one run serves every form)"""
+    rec = []
+    add_ref = mm.helper_adder(reflib, helper, 99, rec)
+    return _incremental_growth(reflib, add_ref, lambda g, p: [helper.mm_last(f) for f in rec])
+
+
+def _incremental_parity(ours, ref):
+    assert len(ours) == len(ref) == 160
+    changed_sel = 0
+    for step, ((sl, sel), (sr, ref_sel)) in enumerate(zip(ours, ref)):
+        assert np.max(np.abs(sl - sr)) < 1e-8, (step, np.max(np.abs(sl - sr)))
         assert np.array_equal(sel, ref_sel), step
         changed_sel += int(np.sum(ref_sel == 1))
     assert changed_sel > 0
-    for L, g, p in sides:
-        p.destroy(); g.destroy()
+
+
+def test_incremental_parity_with_reference(lib, incremental_reference):
+    """growth in the style of test_gpu_parity._random_growth: loop closures and injected outliers as max factors, on the library
+    (native) and on the reference (checker factor): states at every step, selections of the new factors"""
+    _incremental_parity(_incremental_ours(lib), incremental_reference)
+
+
+@pytest.mark.parametrize("opts", INC_FORMS, ids=_ids)
+def test_incremental_parity_with_reference_under_every_launch_form(lib, incremental_reference, opts):
+    with lib.options(**opts):
+        ours = _incremental_ours(lib)
+    _incremental_parity(ours, incremental_reference)
 
 
 def test_foreign_tag3_keeps_host_path(lib, helper):

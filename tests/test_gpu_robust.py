@@ -131,8 +131,7 @@ def test_identity_incremental(lib):
 
 
 # ---- 2. weighted-plain equivalence --------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("kind, c", [(rm.HUBER, 1.0), (rm.CAUCHY, 1.0), (rm.DCS, 3.0)])
-def test_weighted_plain_equivalence(lib, kind, c):
+def _weighted_plain_equivalence(lib, kind, c):
     states, plain, kinds, cs, nb, nl = rm.m3500_robust(kind, c)
     gr = rm.build(lib, states, plain, kinds, cs)
     gp = lib.new_graph(); gp.build_from_arrays(states, *plain)
@@ -161,6 +160,30 @@ def test_weighted_plain_equivalence(lib, kind, c):
     pr.destroy(); pp.destroy(); gr.destroy(); gp.destroy()
 
 
+@pytest.mark.parametrize("kind, c", [(rm.HUBER, 1.0), (rm.CAUCHY, 1.0), (rm.DCS, 3.0)])
+def test_weighted_plain_equivalence(lib, kind, c):
+    _weighted_plain_equivalence(lib, kind, c)
+
+
+# The weights are written into the factor slots by their own kernel before k_linearize_t reads them: the LDS-staged write-out of the
+# linearisation, the per-level and no-graph forms, the multi-workgroup fronts and a new plan per call with weights other than 1.
+# Tolerance-free: the robust graph and the plain graph carrying w * W0 run under the same options and agree bitwise.
+BATCH_PATHS = [dict(linearize_staged_min=0), dict(use_graph=0), dict(small_lds_kb=0), dict(persist=0), dict(batch_extend=0),
+               dict(linearize_staged_min=0, use_graph=0)]
+INC_FORMS = [{"inc_one": 0, "inc_tail": 0}, {"inc_multi": 0}, {"inc_inline": 0}, {"inc_lazy_states": 0}, {"inc_update": 0}, {"tail_poses": 8}]
+
+
+def _ids(o):
+    return ",".join(f"{k}={v}" for k, v in o.items())
+
+
+@pytest.mark.parametrize("opts", BATCH_PATHS, ids=_ids)
+@pytest.mark.parametrize("kind, c", [(rm.HUBER, 1.0), (rm.CAUCHY, 1.0), (rm.DCS, 3.0)])
+def test_weighted_plain_equivalence_on_other_paths(lib, kind, c, opts):
+    with lib.options(**opts):
+        _weighted_plain_equivalence(lib, kind, c)
+
+
 # ---- 3. reference parity ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind, c", [(rm.CAUCHY, 1.0), (rm.DCS, 3.0)])
 def test_batch_parity_with_reference(lib, reflib, helper, kind, c):
@@ -173,44 +196,72 @@ def test_batch_parity_with_reference(lib, reflib, helper, kind, c):
     pr.destroy(); pc.destroy(); gr.destroy(); gc.destroy()
 
 
-def test_incremental_parity_with_reference(lib, reflib, helper):
-    """M3500 + outliers grown pose by pose (Cauchy closures, each false closure inserted when its later pose arrives): both sides follow
-    the same fall-back schedule and agree on the states"""
+def _incremental_states(L, add, upto=1200):
+    """M3500 + outliers grown pose by pose on L (Cauchy closures, each false closure inserted when its later pose arrives);
+    add(g, i): adds factor i.  Returns the states at every 25th pose and at the end, and the number of robust factors added"""
     states, plain, kinds, cs, nb, nl = rm.m3500_robust(rm.CAUCHY, 1.0)
     fa, fb, z, W = plain
     order = np.argsort(np.maximum(fa, fb), kind="stable")
-    upto = 1200
-    sides = []
-    for L in (lib, reflib):
-        g = L.new_graph(); p = L.new_param(nthreshold=100)
-        sides.append((L, g, p))
+    g = L.new_graph(); p = L.new_param(nthreshold=100)
     k = 0
-    batches = [0, 0]
+    out = {}
     for n in range(upto):
-        for L, g, p in sides:
-            g.add_node_xyt(states[n])
+        g.add_node_xyt(states[n])
         while k < len(order) and max(fa[order[k]], fb[order[k]]) <= n:
-            i = order[k]; k += 1
-            gl = sides[0][1]
-            if fb[i] < 0:
-                gl.add_factor_xytpos(int(fa[i]), z[i], W[i].reshape(3, 3))
-            else:
-                gl.add_factor_xyt(int(fa[i]), int(fb[i]), z[i], W[i].reshape(3, 3))
-            if kinds[i]:
-                assert gl.set_robust(gl.n_factors - 1, int(kinds[i]), float(cs[i])) == 0
-            rm.add_factor(reflib, helper, sides[1][1], fa[i], fb[i], z[i], W[i], kinds[i], cs[i])
-        for j, (L, g, p) in enumerate(sides):
-            if n == 10:
-                g.cholesky(p)
-            elif n > 10:
-                p.c.batch_time = 1e300
-                g.cholesky_inc(p)
+            add(g, order[k]); k += 1
+        if n == 10:
+            g.cholesky(p)
+        elif n > 10:
+            p.c.batch_time = 1e300
+            g.cholesky_inc(p)
         if n > 10 and (n % 25 == 0 or n == upto - 1):
-            sl, sr = sides[0][1].states(), sides[1][1].states()
-            assert _ang(sl, sr) < 1e-8, (n, _ang(sl, sr))
-    assert np.sum(kinds[order[:k]] != 0) > 100
-    for L, g, p in sides:
-        p.destroy(); g.destroy()
+            out[n] = g.states()
+    p.destroy(); g.destroy()
+    return out, int(np.sum(kinds[order[:k]] != 0))
+
+
+def _incremental_ours(lib):
+    states, plain, kinds, cs, nb, nl = rm.m3500_robust(rm.CAUCHY, 1.0)
+    fa, fb, z, W = plain
+
+    def add(g, i):
+        if fb[i] < 0:
+            g.add_factor_xytpos(int(fa[i]), z[i], W[i].reshape(3, 3))
+        else:
+            g.add_factor_xyt(int(fa[i]), int(fb[i]), z[i], W[i].reshape(3, 3))
+        if kinds[i]:
+            assert g.set_robust(g.n_factors - 1, int(kinds[i]), float(cs[i])) == 0
+    return _incremental_states(lib, add)
+
+
+@pytest.fixture(scope="module")
+def incremental_reference(reflib, helper):
+    """the unmodified reference driving the checker factor through the same growth (it has no options: one run serves every form)"""
+    states, plain, kinds, cs, nb, nl = rm.m3500_robust(rm.CAUCHY, 1.0)
+    fa, fb, z, W = plain
+    return _incremental_states(reflib, lambda g, i: rm.add_factor(reflib, helper, g, fa[i], fb[i], z[i], W[i], kinds[i], cs[i]))
+
+
+def _incremental_parity(ours, ref):
+    (so, no), (sr, nr) = ours, ref
+    assert list(so) == list(sr) and len(so) > 40
+    for n in so:
+        assert _ang(so[n], sr[n]) < 1e-8, (n, _ang(so[n], sr[n]))
+    assert no == nr and no > 100
+
+
+def test_incremental_parity_with_reference(lib, incremental_reference):
+    """M3500 + outliers grown pose by pose (Cauchy closures, each false closure inserted when its later pose arrives): both sides follow
+    the same fall-back schedule and agree on the states"""
+    _incremental_parity(_incremental_ours(lib), incremental_reference)
+
+
+@pytest.mark.parametrize("opts", INC_FORMS, ids=_ids)
+def test_incremental_parity_with_reference_under_every_launch_form(lib, incremental_reference, opts):
+    """select_new_robust reads the l_point mirror or the state mirror, whichever the launch form keeps current"""
+    with lib.options(**opts):
+        ours = _incremental_ours(lib)
+    _incremental_parity(ours, incremental_reference)
 
 
 # ---- 4. chi^2 -----------------------------------------------------------------------------------------------------------------
@@ -230,7 +281,7 @@ def test_chi2_against_model(lib):
 
 
 # ---- 5. LM --------------------------------------------------------------------------------------------------------------------
-def test_lm_parity_with_model(lib):
+def _lm_parity_with_model(lib):
     states, plain, kinds, cs, nb, nl = rm.m3500_robust(rm.CAUCHY, 1.0)
     x0 = lm_model.perturbed(states, 0.01)
     iters = 25
@@ -260,8 +311,23 @@ def test_lm_parity_with_model(lib):
         d = a - b
         return float(np.mean(np.hypot(d[:, 0], d[:, 1])))
     assert err(gr.states(), gcl.states()) < 0.4 * err(gpl.states(), gcl.states())
+    out = (t.copy(), g.states(), gr.states())
     for gg, pp in ((g, p), (gcl, pcl), (gpl, ppl), (gr, prr)):
         pp.destroy(); gg.destroy()
+    return out
+
+
+def test_lm_parity_with_model(lib):
+    _lm_parity_with_model(lib)
+
+
+@pytest.mark.parametrize("opts", [dict(use_graph=0), dict(small_lds_kb=0)], ids=_ids)
+def test_lm_parity_with_model_on_other_paths(lib, opts):
+    with lib.options(**opts):
+        out = _lm_parity_with_model(lib)
+    if opts == dict(use_graph=0):                                # (the kernels and their order are the default run's: the same bits)
+        for v, v0 in zip(out, _lm_parity_with_model(lib)):
+            _same(v, v0)
 
 
 # ---- 6. scale -----------------------------------------------------------------------------------------------------------------
