@@ -44,6 +44,9 @@ namespace asam {
 
 constexpr int PROF_SLOTS = 16;    // debug stamps per front (DevPlan::prof)
 constexpr int PROF_XCD_UP = 12, PROF_XCD_DN = 13;     // ... slots of the XCD a front's k_front_small / k_backsolve_w ran on (1 + XCC id; tools/front_times.py)
+// ... and of the hand-over of x in a multi-level back substitution (prof_mode 2, tools/backsolve_times.py): the front's last x store issued,
+// its stores drained and the workgroup through the barrier (flag protocols), its flag store issued
+constexpr int PROF_X_STORED = 14, PROF_X_DRAINED = 11, PROF_X_FLAG = 15;
 // the XCD this workgroup runs on (0-7): a hardware register read, for the profile stamps only -- placement is never relied upon
 __device__ __forceinline__ int xcc_id() { return __builtin_amdgcn_s_getreg(20 | (0 << 6) | ((4 - 1) << 11)) & 7; }     // hwreg(HW_REG_XCC_ID, 0, 4)
 constexpr int TPB = 256;          // threads per workgroup (4 waves)
@@ -97,7 +100,16 @@ struct DevPlan {
     //   marks (incremental steps, else null): marks[t] == step number <=> front t is regenerated by THIS step's launch (written by the prologue,
     //   one kernel boundary earlier -- data, not a flag: an older value means "not in this step", its factor of an earlier step is what is wanted).
     int *epoch; const int *flevel; int l0; const int *marks;
+    // how a front hands its x to its children inside a multi-level back substitution whose flags carry the step number (backsolve_finish, gather_x):
+    //   X_FLUSH   plain stores, L2 write-back, flag (publish_flag) -- what every other flag of this file does
+    //   X_WT      write-through stores, drained, flag (publish_flag_wt): no write-back
+    //   X_TAGGED  no flag: every x entry travels as a 16-byte granule {lo, tag, hi, tag} in xg, tag = the step number
+    // The host picks the form per launch (x_handover_mode below is the ONE place where a kernel reads it): granules only where every front of the
+    // launch has at most TPB update rows, so that a lane polls one granule (gather_x).
+    int xmode; uint4 *xg; unsigned xg_bytes;
 };
+enum { X_FLUSH = 0, X_WT = 1, X_TAGGED = 2 };
+constexpr int XG_CONST = -1;      // tag of a granule whose value never changes (the zero entries behind phantom rows): valid in every step; no step number reaches it
 
 // ---- work decomposition of the big-front kernels (shared by host launch tables and device decode) ----
 __host__ __device__ inline int asm_chunks(int nbc) { return (nbc + ASM_CB - 1) / ASM_CB; }
@@ -577,7 +589,7 @@ __device__ __forceinline__ void acquire_all() {                 // after the pol
     if (threadIdx.x == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     __syncthreads();
 }
-__device__ __forceinline__ void publish_flag(int *flag, int ev = 0) {       // call by ALL threads of the workgroup after their last store
+__device__ __forceinline__ void publish_flag(int *flag, int ev = 0, long long *pf = nullptr) {       // call by ALL threads of the workgroup after their last store (pf: debug stamps, PROF_X_*)
     // every wave waits until ITS stores are in the L2: the barrier alone does not (a workgroup-scope release on gfx950 waits for no store,
     // the compute unit's vector L1 keeps its waves' stores in order among themselves) and thread 0's write-back below waits only for its own wave
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -590,8 +602,73 @@ __device__ __forceinline__ void publish_flag(int *flag, int ev = 0) {       // c
         // then read what the addresses held BEFORE (the iteration or the context before).  That is the defect behind the rare wrong results
         // of chain-like graphs, whose fronts all take that branch (profiles/r05_flag_soak.txt, listings in profiles/r05_release_isa.txt;
         // tools/check_release_isa.py checks every release of the generated code).
+        const long long t_drained = pf ? wall_clock64() : 0;
         asm volatile("buffer_wbl2 sc1\n\ts_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __hip_atomic_store(flag, ev ? ev : 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (pf) { pf[PROF_X_DRAINED] = t_drained; pf[PROF_X_FLAG] = wall_clock64(); }
+    }
+}
+// The hand-over of x in the multi-level back substitutions, without the write-back.  The payload -- at most a few hundred doubles -- is stored
+// WRITE-THROUGH (st_agent: global_store_dwordx2 sc1, it does not stay dirty in the XCD's L2), every wave waits until its stores have left
+// (s_waitcnt vmcnt(0)), the barrier collects the waves, and ONE lane stores the flag, sc1 as well.  The children poll the flag with sc1 loads
+// from one lane, pass a workgroup barrier and read x with sc1 loads only (ld_agent): no acquire either.  Valid as long as EVERY store and
+// EVERY load of x inside such a launch is sc1 (backsolve_finish, gather_x: there are no others) and a compute unit runs one workgroup of the
+// launch (the host sizes its dynamic LDS accordingly: HANDOVER_LDS_MIN).  publish_flag and every other release of this file keep the write-back:
+// their payloads are update blocks of tens of kilobytes, stored by code that other launches share.
+__device__ __forceinline__ void st_agent(double *p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void publish_flag_wt(int *flag, int ev, long long *pf = nullptr) {      // call by ALL threads of the workgroup after their last st_agent
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const long long t_drained = pf ? wall_clock64() : 0;
+        __hip_atomic_store(flag, ev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (pf) { pf[PROF_X_DRAINED] = t_drained; pf[PROF_X_FLAG] = wall_clock64(); }
+    }
+}
+// the form in which THIS launch hands x over -- asked once per kernel, and both sides (backsolve_finish, the wait and the gather) get the answer:
+// only a launch whose fronts wait for their parent inside it (in_launch) under a step number has a hand-over other than the flag form
+__device__ __forceinline__ int x_handover_mode(const DevPlan &P, const int *xflags, int ev, bool in_launch) { return (xflags && ev != 0 && in_launch) ? P.xmode : X_FLUSH; }
+constexpr size_t HANDOVER_LDS_MIN = 80 * 1024 + 256;      // dynamic LDS of a launch whose workgroups must not share a compute unit (160 KB each)
+// Epoch-tagged granules (DevPlan::xg, X_TAGGED): x entry i travels as ONE 16-byte write-through store {lo32, tag, hi32, tag}, tag = the step
+// number.  Each 8-byte half describes itself, so the halves may land at different times; a reader takes the value once BOTH tags equal the
+// step number it runs in.  The data is its own flag: no ordering between stores, no producer barrier, no write-back, and the value arrives in the
+// memory round trip in which it becomes visible.  Older steps left older tags (the counter only grows, rewind_epoch zeroes xg with the flags),
+// new memory holds zeros, and no step number is 0.  Buffer accesses: the descriptor's byte count drops an access past the end of xg.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t xg_rsrc(const DevPlan &P) { return __builtin_amdgcn_make_buffer_rsrc((void *)P.xg, 0, (int)P.xg_bytes, 0x00020000); }
+typedef unsigned xg_u4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void st_granule(__amdgpu_buffer_rsrc_t r, size_t i, double v, int tag) {
+    const xg_u4 g = { (unsigned)__double2loint(v), (unsigned)tag, (unsigned)__double2hiint(v), (unsigned)tag };
+    __builtin_amdgcn_raw_buffer_store_b128(g, r, (int)(i * 16), 0, 16);       // aux 16: sc1
+}
+// x of the front's update rows (n <= TPB of them, one per lane) into dst (LDS), in the launches that hand x over in granules.  Who spins, and when: while the GRANDPARENT has not
+// finished only lane 0 looks, slowly, at one granule of it; once it has, the parent is the front in flight and every lane polls the granules of
+// its own rows until they carry the step number -- at most one level's workgroups spin hard at any time.  Bounded like wait_flag, same code 9.
+__device__ __forceinline__ void gather_x(const DevPlan &P, const FrontDesc &D_, const int *rows, double *dst, int n, int ev, int *bad, long long *pf) {
+    const int tid = threadIdx.x;
+    const __amdgpu_buffer_rsrc_t r = xg_rsrc(P);
+    auto tagged = [&](const xg_u4 &g) { return ((int)g.y == ev && (int)g.w == ev) || ((int)g.y == XG_CONST && (int)g.w == XG_CONST); };
+    auto give_up = [&]() { if (atomicCAS(bad, 0, 9) == 0) { bad[2] = 9; bad[3] = 0; } };
+    if (tid == 0) {
+        const int g1 = P.fd[D_.parent].parent;
+        if (g1 >= 0 && P.fd[g1].nsb > 0) {
+            const unsigned gi = 3u * (unsigned)P.fd[g1].first * 16u;
+            for (int spins = 0; !tagged(__builtin_amdgcn_raw_buffer_load_b128(r, (int)gi, 0, 16)); ) {
+                __builtin_amdgcn_s_sleep(8); asm volatile("" ::: "memory");       // (the next look is a new load)
+                if (++spins > (1 << 21)) { give_up(); break; }
+            }
+        }
+    }
+    __syncthreads();
+    if (pf && tid == 0) pf[4] = wall_clock64();
+    if (tid < n) {                                       // n <= TPB: the host gives a launch with a taller update block the flag form
+        const int e = tid;
+        const unsigned gi = (3u * (unsigned)rows[e / 3] + (unsigned)(e % 3)) * 16u;
+        xg_u4 g = __builtin_amdgcn_raw_buffer_load_b128(r, (int)gi, 0, 16);
+        for (int spins = 0; !tagged(g); g = __builtin_amdgcn_raw_buffer_load_b128(r, (int)gi, 0, 16)) {
+            __builtin_amdgcn_s_sleep(1); asm volatile("" ::: "memory");
+            if (++spins > (1 << 23)) { give_up(); break; }
+        }
+        dst[e] = __hiloint2double((int)g.z, (int)g.x);
     }
 }
 // reset of a flag on the paths that reuse the values 0 / 1: a device-scope store like every other access to a flag word
@@ -2197,10 +2274,25 @@ __host__ __device__ inline size_t backsolve_lds(int m, int ns, bool pre) { retur
 struct UpdArgs { const int *perm; const double *lp; double *st, *dX, *st_out, *dx_out; int *bad_out; double *lp_next; };      // lp_next (resident loops): the new state is also the next step's linearisation point (aprilsam.c:131-135) -- no copy between two steps
 // common tail of the back-substitution kernels: x of the own columns to HBM, flag for the children, then the state update
 // of the own poses (april_graph_xyt.c:302-314)
-__device__ __forceinline__ void backsolve_finish(const FrontDesc &D_, int t, const double *xw, double *__restrict__ x, int *xflags, int *bad, const UpdArgs &upd, int ev = 0) {
+// xmode (x_handover_mode of the calling kernel), P, pf: the form in which the launch hands x over
+__device__ __forceinline__ void backsolve_finish(const FrontDesc &D_, int t, const double *xw, double *__restrict__ x, int *xflags, int *bad, const UpdArgs &upd, int ev = 0,
+                                                 int xmode = X_FLUSH, const DevPlan *P = nullptr, long long *pf = nullptr) {
     const int tid = threadIdx.x, nsb = D_.nsb, ns = 3 * nsb;
-    for (int e = tid; e < ns; e += TPB) x[(size_t)3 * D_.first + e] = xw[e];
-    if (xflags) publish_flag(xflags + t, ev);       // the children may go; the state update of the own poses follows
+    if (xmode == X_TAGGED) {
+        // the granules first: they are what the children wait for.  x itself, for everything that reads it after a kernel boundary, follows with plain stores
+        const __amdgpu_buffer_rsrc_t r = xg_rsrc(*P);
+        for (int e = tid; e < ns; e += TPB) st_granule(r, (size_t)3 * D_.first + e, xw[e], ev);
+        if (pf && tid == 0) pf[PROF_X_STORED] = pf[PROF_X_FLAG] = wall_clock64();
+        for (int e = tid; e < ns; e += TPB) x[(size_t)3 * D_.first + e] = xw[e];
+    } else if (xmode == X_WT) {
+        for (int e = tid; e < ns; e += TPB) st_agent(x + (size_t)3 * D_.first + e, xw[e]);
+        if (pf && tid == 0) pf[PROF_X_STORED] = wall_clock64();
+        publish_flag_wt(xflags + t, ev, pf);       // the children may go; the state update of the own poses follows
+    } else {
+        for (int e = tid; e < ns; e += TPB) x[(size_t)3 * D_.first + e] = xw[e];
+        if (pf && tid == 0) pf[PROF_X_STORED] = wall_clock64();
+        if (xflags) publish_flag(xflags + t, ev, pf);
+    }
     if (upd.perm) {
         for (int k = tid; k < nsb; k += TPB) {
             const int i = upd.perm[D_.first + k];
@@ -2264,12 +2356,15 @@ __global__ void __launch_bounds__(TPB) k_backsolve_t(DevPlan P, const int *__res
             for (int u = 0; u < 8; u++) { const int e = e0 + u * TPB; if (e < ne) { const int c = e / R; Lp[c * ldp + (e - c * R)] = v[u]; } }
         }
     }
-    if (wait && D_.parent >= 0) {          // multi-level launch, root first: x of every ancestor is final once the parent is done
+    // (granules, DevPlan::xmode: no flag to wait for -- gather_x below polls the data itself)
+    const int xmode = x_handover_mode(P, xflags, ev, PRE && wait);
+    const bool xtag = xmode == X_TAGGED && D_.parent >= 0;
+    if (wait && D_.parent >= 0 && !xtag) {          // multi-level launch, root first: x of every ancestor is final once the parent is done
         if (tid == 0) wait_flag(xflags + D_.parent, bad, ev);
         if constexpr (PRE) { __syncthreads(); asm volatile("" ::: "memory"); }     // no acquire fence: x is gathered with ld_agent below
         else acquire_all();
     }
-    if (pf && tid == 0) pf[4] = wall_clock64();
+    if (pf && tid == 0 && !xtag) pf[4] = wall_clock64();
     // split: the update-row product of this front was computed by k_backsolve_gemv and waits in x at the own positions
     const bool pre_t = split && bs_split_front(nsb, nub);
     const int mprod = pre_t ? ns : m;                  // rows that still enter the products below
@@ -2278,7 +2373,8 @@ __global__ void __launch_bounds__(TPB) k_backsolve_t(DevPlan P, const int *__res
     if (pre_t) { for (int e = tid; e < ns; e += TPB) xw[e] = Fg[(size_t)e * R + m] - x[(size_t)3 * D_.first + e]; }
     else {
         for (int e = tid; e < ns; e += TPB) xw[e] = Fg[(size_t)e * R + m];
-        for (int e = tid; e < 3 * nub; e += TPB) { const double *xp = x + (size_t)3 * rows[e / 3] + e % 3; if constexpr (PRE) xw[ns + e] = ld_agent(xp); else xw[ns + e] = *xp; }
+        if (xtag) gather_x(P, D_, rows, xw + ns, 3 * nub, ev, bad, pf);
+        else for (int e = tid; e < 3 * nub; e += TPB) { const double *xp = x + (size_t)3 * rows[e / 3] + e % 3; if constexpr (PRE) xw[ns + e] = ld_agent(xp); else xw[ns + e] = *xp; }
     }
     __syncthreads();
     if (pf && tid == 0) pf[5] = wall_clock64();
@@ -2411,7 +2507,7 @@ __global__ void __launch_bounds__(TPB) k_backsolve_t(DevPlan P, const int *__res
         if (pf) t_solve += wall_clock64() - ts;
     }
     if (pf && tid == 0) { pf[7] = wall_clock64(); pf[8] = t_prod; pf[9] = t_sum; pf[10] = t_solve; }
-    backsolve_finish(D_, t, xw, x, xflags, bad, upd, ev);
+    backsolve_finish(D_, t, xw, x, xflags, bad, upd, ev, xmode, &P, pf);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -2638,15 +2734,17 @@ __device__ __forceinline__ void backsolve_w_body(const DevPlan &P, const int t, 
             }
         }
     }
-    if (xflags && D_.parent >= 0) {                      // multi-level launch: x of every ancestor is final once the parent is done
+    const int xmode = x_handover_mode(P, xflags, ev, true);
+    const bool xtag = xmode == X_TAGGED && D_.parent >= 0;      // granules: no flag to wait for, gather_x polls the data itself
+    if (xflags && D_.parent >= 0 && !xtag) {             // multi-level launch: x of every ancestor is final once the parent is done
         if (tid == 0) wait_flag(xflags + D_.parent, bad, ev);
         __syncthreads();                                 // no acquire fence: x is gathered with ld_agent
         asm volatile("" ::: "memory");
-       
     }
-    if (pf && tid == 0) pf[4] = wall_clock64();
+    if (pf && tid == 0 && !xtag) pf[4] = wall_clock64();
     for (int e = tid; e < ns; e += TPB) xw[e] = Fg[(size_t)e * R + m];
-    for (int e = tid; e < 3 * nub; e += TPB) xw[ns + e] = ld_agent(x + (size_t)3 * rows[e / 3] + e % 3);
+    if (xtag) gather_x(P, D_, rows, xw + ns, 3 * nub, ev, bad, pf);
+    else for (int e = tid; e < 3 * nub; e += TPB) xw[ns + e] = ld_agent(x + (size_t)3 * rows[e / 3] + e % 3);
     __syncthreads();
     if (pf && tid == 0) pf[5] = wall_clock64();
     for (int k1 = ns; k1 > 0; k1 -= BSWT) {
@@ -2689,7 +2787,7 @@ __device__ __forceinline__ void backsolve_w_body(const DevPlan &P, const int t, 
         __syncthreads();
     }
     if (pf && tid == 0) pf[7] = wall_clock64();
-    backsolve_finish(D_, t, xw, x, xflags, bad, upd, ev);
+    backsolve_finish(D_, t, xw, x, xflags, bad, upd, ev, xmode, &P, pf);
 }
 __global__ void __launch_bounds__(TPB) k_backsolve_w(DevPlan P, const int *__restrict__ fronts, const double *__restrict__ pool,
                                                      double *__restrict__ x, int *xflags, int *bad, UpdArgs upd) {

@@ -44,6 +44,7 @@ struct Options {
     int tail_poses = 28;          // incremental path: own poses per tail front (>= 8; measured on the M3500 demo: 24 / 28 / 32 -> 546 / 530 / 528 ms total, median 0.038 / 0.0385 / 0.040 ms)
     int blk_backsolve = 1;        // wide multi-workgroup fronts: back substitution 128 columns at a time by a chain workgroup + helpers (0: k_backsolve_gemv + k_backsolve_t)
     int wave_backsolve = 1;       // multi-level back substitution: column-per-lane kernel (0: the per-32-column-block kernel)
+    int tagged_x = 1;             // multi-level back substitutions: how a front hands its x to its children.  1 = as epoch-tagged 16-byte granules, no flag (kernels.hip.h: gather_x; a launch holding a front of more than 256 update rows takes form 2: launch_xmode); 0 = write-through x, drained, then the flag -- no L2 write-back (publish_flag_wt); 2 = plain x, L2 write-back, flag (publish_flag: the form before, kept for measurements).  Measured on M3500, resident step: 0.2092 (2 and the commit before) / 0.2093 (0) / 0.2028 ms (1), profiles/r08_downsweep_handover.txt
     int linearize_staged_min = 32768; // factors per launch from which k_linearize writes its results out through LDS (coalesced stores)
     int mem_cap_mb = 0;           // > 0: refuse any single device buffer above this size with ERR_OOM (tests: the out-of-memory path)
     int pool_guard = 0;           // debug: > 0 = every frontal array of a plan is followed by a guard band of this many doubles, NaN-filled at plan upload and checked after every synchronised step (ERR_GUARD); a stray read that is used poisons the result

@@ -137,10 +137,11 @@ struct Context {
     // of fronts, run as ONE launch for the factorisation and ONE for the back substitution, fronts waiting on per-front
     // dependency flags instead of on kernel boundaries (kernels.hip.h: wait_flag / publish_flag)
     int persist_l0 = -1;                  // first level of the multi-level launch, -1: none
-    int p_up_off = 0, p_up_n = 0, p_dn_off = 0, p_dn_n = 0, p_nt = 1024; size_t p_up_lds = 0, p_dn_lds = 0; long long p_up_full = 0; int p_dn_maxns = 0;
+    int p_up_off = 0, p_up_n = 0, p_dn_off = 0, p_dn_n = 0, p_nt = 1024; size_t p_up_lds = 0, p_dn_lds = 0; long long p_up_full = 0; int p_dn_maxns = 0, p_dn_maxnu = 0;      // (p_dn_maxnu: tallest update block, rows, of the back substitution's list)
     int x_up_off = 0, x_up_n = 0, x_dn_off = 0, x_dn_n = 0;      // the same two lists in XCD-placed order (option xcd_place; x_up_n = 0: not placed)
     int x_leaf_off = 0, x_leaf_n = 0;                           // ... and level 0's fronts for its two launches (x_leaf_n = 0: level 0 keeps its own list)
     DBuf<int> d_flags, d_flevel, d_perm, d_epoch, d_marks;   // d_epoch: the step counter every dependency flag carries (kernels.hip.h wait_flag); d_marks: fronts regenerated by an incremental step
+    DBuf<uint4> d_xg;                     // x as epoch-tagged granules, one per entry of d_x: the hand-over inside the multi-level back substitutions (kernels.hip.h: gather_x; option tagged_x)
     int flag_stride = 0;                  // d_flags = three arrays of this many words: "factor done", "x done", "vectors ready" per front
     long long epoch_steps = 0;            // numeric phases enqueued since the counter was (re)started (rewind_epoch)
     DBuf<double> d_dinv, d_bsb_far; DBuf<int> d_bsb_flags;   // inverse diagonal blocks of the big fronts; scratch of k_backsolve_blk
@@ -301,6 +302,7 @@ template <class Fn> static int guarded_rc(const april_graph_cholesky_param_t *pa
 static const int FIRST_EPOCH = 1 << 20;
 struct Context;
 static void rewind_epoch(Context &c, hipStream_t s, long long phases);
+static void set_const_granules(Context &c, hipStream_t s);
 // marginal covariances (solver_marginals.inc.h): what a successful solver call left in the front pool
 enum { FACT_NONE = 0, FACT_PLAN = 1, FACT_EXTENDED = 2 };      // no factor / the factor of c.plan / tail fronts appended by the incremental path
 static void record_factor(Context &c, int kind, const GraphPack &gp);
@@ -594,13 +596,13 @@ static void upload_plan(Context &c, hipStream_t s, const ShardLayout *lay = null
             cnt += L.n_small; l0 = l;
         }
         if (P.nLevels - l0 >= 2) {
-            c.persist_l0 = l0; c.p_nt = nt_top; c.p_up_lds = 0; c.p_dn_lds = 0; c.p_up_full = 0; c.p_dn_maxns = 0;
+            c.persist_l0 = l0; c.p_nt = nt_top; c.p_up_lds = 0; c.p_dn_lds = 0; c.p_up_full = 0; c.p_dn_maxns = 0; c.p_dn_maxnu = 0;
             c.p_up_off = (int)tab.size(); c.p_up_n = cnt;
             for (int l = l0; l < P.nLevels; l++) {                     // children before parents: dependencies have lower workgroup ids
                 const LevelPlan &L = c.levels[l];
                 for (int k = 0; k < L.n_small; k++) tab.push_back(tab[L.small_off + k]);
                 c.p_up_lds = std::max(c.p_up_lds, L.small_lds); c.p_up_full = std::max(c.p_up_full, L.full_limit);
-                for (int k = 0; k < L.n_all; k++) { const int t = tab[L.all_off + k]; c.p_dn_lds = std::max(c.p_dn_lds, backsolve_lds(P.cols(t), 3 * P.f_nsb[t], true)); c.p_dn_maxns = std::max(c.p_dn_maxns, 3 * P.f_nsb[t]); }
+                for (int k = 0; k < L.n_all; k++) { const int t = tab[L.all_off + k]; c.p_dn_lds = std::max(c.p_dn_lds, backsolve_lds(P.cols(t), 3 * P.f_nsb[t], true)); c.p_dn_maxns = std::max(c.p_dn_maxns, 3 * P.f_nsb[t]); c.p_dn_maxnu = std::max(c.p_dn_maxnu, P.cols(t) - 3 * P.f_nsb[t]); }
             }
             c.p_dn_off = (int)tab.size(); c.p_dn_n = cnt;
             for (int l = P.nLevels - 1; l >= l0; l--) { const LevelPlan &L = c.levels[l]; for (int k = 0; k < L.n_all; k++) tab.push_back(tab[L.all_off + k]); }
@@ -671,6 +673,24 @@ static void upload_plan(Context &c, hipStream_t s, const ShardLayout *lay = null
     c.d_H.need((size_t)9 * ((size_t)std::max(1, P.n_slots) + (size_t)5 * INC_FACT_)); c.d_x.need((size_t)3 * ((size_t)P.N + INC_NODES_ + 1));
     c.inc.zpos = P.N + INC_NODES_;
     HIPCHECK(hipMemsetAsync(c.d_x.p + (size_t)3 * c.inc.zpos, 0, 24, s));
+    {   // The form in which the multi-level back substitutions of this plan hand x over (option tagged_x: 1 granules, 0 write-through x and a
+        // flag, 2 the write-back hand-over of every other flag); launch_xmode has the last word per launch.  The granule mirror of x exists only
+        // where the option asks for it and such a launch can exist (the batch step's, or an incremental step's later on), and is zeroed with
+        // every plan: step numbers of THIS context's counter only grow, so the tags an earlier plan left behind would be older than any step to
+        // come -- but its CONSTANT granules (tag XG_CONST at ITS zpos) are not: in a larger plan that position belongs to a pose, and a child
+        // would take the zero for its value.  The granules are addressed with 32-bit byte offsets: a system too large for them takes the
+        // form every other flag uses.
+        const size_t nx = (size_t)3 * ((size_t)P.N + INC_NODES_ + 1);
+        const bool mirror = g_opt.tagged_x == 1 && (c.persist_l0 >= 0 || inc) && nx * sizeof(uint4) < ((size_t)1 << 32);
+        c.dp.xmode = mirror ? X_TAGGED : g_opt.tagged_x == 0 ? X_WT : X_FLUSH;
+        c.dp.xg = nullptr; c.dp.xg_bytes = 0;
+        if (mirror) {
+            c.d_xg.need(nx);
+            HIPCHECK(hipMemsetAsync(c.d_xg.p, 0, c.d_xg.cap * sizeof(uint4), s));
+            set_const_granules(c, s);
+            c.dp.xg = c.d_xg.p; c.dp.xg_bytes = (unsigned)(nx * sizeof(uint4));
+        }
+    }
     c.inc.slots_used = P.n_slots;
     c.inc.ready = false; c.inc.t_first.clear(); c.same_topo_batches = 0;
     c.d_bad.need(4); c.h_bad.need(4);
@@ -683,6 +703,7 @@ static void upload_plan(Context &c, hipStream_t s, const ShardLayout *lay = null
     }
     if (uprof) fprintf(stderr, "aprilsam_amd upload: graphs destroyed + descriptors %.3f, index arrays + copies %.3f, launch tables %.3f, last copies + sync %.3f, pools %.3f ms\n", u1 - u0, u2 - u1, u3 - u2, u4 - u3, now_ms() - u4);
     c.st.n_fronts = P.nF; c.st.n_levels = P.nLevels; c.st.max_front_rows = P.max_rows;
+    c.st.dn_launch_fronts = c.persist_l0 >= 0 ? c.p_dn_n : 0;       // fronts of the batch step's multi-level back substitution (an incremental step overwrites it with its own)
     c.st.nnz_L = P.nnzL; c.st.flops_factor = P.flops; c.st.bytes_fronts = 8.0 * (double)pool_doubles;
 }
 
@@ -737,7 +758,32 @@ static void launch_backsolve(Context &c, const LevelPlan &L, hipStream_t s, Tic 
 // k_front_small with the configured workgroup size (option small_threads: 256 / 512 / 1024)
 // the multi-level launch of the factorisation: every small front of levels >= persist_l0
 // the plan as the batch path's two multi-level launches see it: flags carry the iteration number
-static DevPlan persist_plan(const Context &c) { DevPlan d = c.dp; d.flevel = c.d_flevel.p; d.l0 = c.persist_l0; return d; }
+// the x entries that stay zero for good (inc.zpos: what phantom rows point at) are valid in every step
+static void set_const_granules(Context &c, hipStream_t s) {
+    static const unsigned G[12] = { 0u, (unsigned)XG_CONST, 0u, (unsigned)XG_CONST, 0u, (unsigned)XG_CONST, 0u, (unsigned)XG_CONST, 0u, (unsigned)XG_CONST, 0u, (unsigned)XG_CONST };
+    HIPCHECK(hipMemcpyAsync(c.d_xg.p + (size_t)3 * c.inc.zpos, G, sizeof(G), hipMemcpyHostToDevice, s));
+}
+// The hand-over form of ONE multi-level back substitution whose tallest update block has max_upd_rows rows: granules are gathered one per lane
+// (kernels.hip.h gather_x), so a launch with a taller block takes the form every other flag uses.  (No plan met so far puts such a front into a
+// multi-level launch -- a front of 86 update blocks that still fits a workgroup's LDS needs four or more ancestors of at most 24-33 poses each
+// -- but an incremental step's fronts near the root collect rows without such a bound.)
+static int launch_xmode(const Context &c, int max_upd_rows) { return c.dp.xmode == X_TAGGED && max_upd_rows > TPB ? (int)X_FLUSH : c.dp.xmode; }
+static int device_cus() {
+    int cus = 0;
+    HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, physical_device(t_slot)));
+    return cus;
+}
+// Dynamic LDS of a multi-level back substitution of `grid` workgroups: two workgroups of more than 80 KB each cannot share a compute unit's 160 KB.
+// The write-through form NEEDS one workgroup of the launch per unit (kernels.hip.h publish_flag_wt): it always gets the larger request, and a
+// grid of more workgroups than units (persist_max_fronts above its default, the empty slots of a placed list) then runs in rounds of one per
+// unit -- deadlock-free as ever by the order of the ids, slower than two per unit.  The granules need no such thing; they get it where it is
+// free, on a grid that fits the device (M3500: 216 slots), so that a spinning workgroup does not sit beside a working one.
+static size_t handover_lds(int xmode, size_t lds, int grid) {
+    if (xmode == X_WT || (xmode == X_TAGGED && grid <= device_cus())) return std::max(lds, HANDOVER_LDS_MIN);
+    return lds;
+}
+static DevPlan launch_plan(const Context &c, DevPlan d, int max_upd_rows) { d.xmode = launch_xmode(c, max_upd_rows); return d; }
+static DevPlan persist_plan(const Context &c) { DevPlan d = c.dp; d.flevel = c.d_flevel.p; d.l0 = c.persist_l0; d.xmode = launch_xmode(c, c.p_dn_maxnu); return d; }
 static void rewind_epoch(Context &c, hipStream_t s, long long phases) {
     c.epoch_steps += phases;
     if (c.epoch_steps < (1ll << 30) || !c.d_epoch.p) return;
@@ -745,6 +791,7 @@ static void rewind_epoch(Context &c, hipStream_t s, long long phases) {
     HIPCHECK(hipStreamSynchronize(s));                      // nothing in flight reads a flag
     HIPCHECK(hipMemsetAsync(c.d_flags.p, 0, c.d_flags.cap * 4, s));
     HIPCHECK(hipMemsetAsync(c.d_marks.p, 0, c.d_marks.cap * 4, s));
+    if (c.d_xg.p) { HIPCHECK(hipMemsetAsync(c.d_xg.p, 0, c.d_xg.cap * sizeof(uint4), s)); set_const_granules(c, s); }      // (tags are step numbers too)
     HIPCHECK(hipMemcpyAsync(c.d_epoch.p, &FIRST_EPOCH, 4, hipMemcpyHostToDevice, s));
     c.epoch_steps = phases;
 }
@@ -883,9 +930,9 @@ static void enqueue_numeric(Context &c, GraphPack &gp, hipStream_t s, hipEvent_t
         const bool xp = c.x_dn_n > 0;                            // the XCD-placed list (empty slots included)
         const int *dn = c.d_tab.p + (xp ? c.x_dn_off : c.p_dn_off), n_dn = xp ? c.x_dn_n : c.p_dn_n;
         if (g_opt.wave_backsolve && c.p_dn_maxns <= BSW_MAX_NS)
-            hipLaunchKernelGGL(k_backsolve_w, dim3(n_dn), dim3(TPB), c.p_dn_lds, s, persist_plan(c), dn, c.d_pool.p, c.d_x.p, c.d_flags.p + c.flag_stride, c.d_bad.p, u);
+            hipLaunchKernelGGL(k_backsolve_w, dim3(n_dn), dim3(TPB), handover_lds(launch_xmode(c, c.p_dn_maxnu), c.p_dn_lds, n_dn), s, persist_plan(c), dn, c.d_pool.p, c.d_x.p, c.d_flags.p + c.flag_stride, c.d_bad.p, u);
         else
-            hipLaunchKernelGGL((k_backsolve_t<true>), dim3(n_dn), dim3(TPB), c.p_dn_lds, s, persist_plan(c), dn, c.d_pool.p, c.d_x.p, 0, c.d_flags.p + c.flag_stride, 1, c.d_bad.p, u);
+            hipLaunchKernelGGL((k_backsolve_t<true>), dim3(n_dn), dim3(TPB), handover_lds(launch_xmode(c, c.p_dn_maxnu), c.p_dn_lds, n_dn), s, persist_plan(c), dn, c.d_pool.p, c.d_x.p, 0, c.d_flags.p + c.flag_stride, 1, c.d_bad.p, u);
         toc();
     }
     for (int l = l0 - 1; l >= 0; l--) {

@@ -371,6 +371,7 @@ static bool inc_fast_step(Context &c, GraphPack &gp, int N, int F, int Fold, int
         const int nph = (tail && t == nFr - 1 && g_opt.inc_tail && E.empty()) ? std::max(0, TAIL_POSES - nsb) : 0;
         const int nub = nub0 + (int)E.size() + nph, nbc = nsb + nub;
         const long long need = (long long)(3 * (nbc + 1)) * (3 * nbc);
+        c.st.max_front_rows = std::max<decltype(c.st.max_front_rows)>(c.st.max_front_rows, 3 * nbc);      // (stats: fronts grow under incremental steps)
         FrontDesc &D = I.fd[t];
         if (tail_fast && t == tstep.t) {               // only the descriptor changes: records, children and array stay
             D.nsb = nsb; D.nub = nub; I.cur_nub[t] = nub;
@@ -654,6 +655,7 @@ static bool inc_fast_step(Context &c, GraphPack &gp, int N, int F, int Fold, int
     if (tail_fast && !one && tail_refactor_lds() > 64 * 1024) return inc_fail(14);       // (never: the refactorisation alone runs as k_inc_one without lists)
     if (I.tab_used + (long long)tab.size() > (long long)c.d_tab.cap) return inc_fail(15);
     c.st.reserved0 = (int)fd_dirty.size();              // fronts regenerated by this step (tools/inc_hist.py)
+    c.st.dn_launch_fronts = one ? 0 : id ? id_n : mp ? mp_n : 0;      // workgroups of this step's multi-level back substitution (0: k_inc_one, or level by level)
     if (!batch) {
         int nu_ = 0; for (int t : fd_dirty) nu_ += (any_upd && mode[t]) ? 1 : 0;
         c.st.inc_fronts_updated = nu_;
@@ -718,6 +720,9 @@ static bool inc_fast_step(Context &c, GraphPack &gp, int N, int F, int Fold, int
     DevPlan dpi = c.dp; dpi.marks = c.d_marks.p;
     DevPlan dpm = c.dp; dpm.flevel = c.d_flevel.p; dpm.l0 = 1;
     int *const xfl = c.d_flags.p + c.flag_stride;
+    // the step's multi-level back substitutions hand x over in the plan's form unless ANY front holds more update rows than a workgroup has lanes by now
+    // (fronts near the root collect the rows of the loop closures): launch_xmode
+    const DevPlan dpx = launch_plan(c, c.dp, I.cur_nub.empty() ? 0 : 3 * *std::max_element(I.cur_nub.begin(), I.cur_nub.end()));
     const UpdCtx uctx = any_upd ? UpdCtx{ c.d_upd.p, c.d_wbuf.p, c.d_flags.p + (size_t)2 * c.flag_stride, gp.d_fa.p, gp.d_fb.p, gp.d_z.p, gp.d_W.p, gp.d_lp.p, gp.d_state.p } : UpdCtx{};
     if (batch) {
         PL.launch(s);
@@ -794,8 +799,8 @@ static bool inc_fast_step(Context &c, GraphPack &gp, int N, int F, int Fold, int
             enqueue_big_steps(c, L, s, [](int) {}, []() {});
         }
     }
-    if (mp && g_opt.wave_backsolve && mp_dn_maxns <= BSW_MAX_NS) hipLaunchKernelGGL(k_backsolve_w, dim3(mp_n), dim3(TPB), mp_dn_lds, s, c.dp, c.d_tab.p + mp_dn_off, c.d_pool.p, c.d_x.p, xfl, c.d_bad.p, UpdArgs{});
-    else if (mp) hipLaunchKernelGGL((k_backsolve_t<true>), dim3(mp_n), dim3(TPB), mp_dn_lds, s, c.dp, c.d_tab.p + mp_dn_off, c.d_pool.p, c.d_x.p, 0, xfl, 1, c.d_bad.p, UpdArgs{});
+    if (mp && g_opt.wave_backsolve && mp_dn_maxns <= BSW_MAX_NS) hipLaunchKernelGGL(k_backsolve_w, dim3(mp_n), dim3(TPB), handover_lds(dpx.xmode, mp_dn_lds, mp_n), s, dpx, c.d_tab.p + mp_dn_off, c.d_pool.p, c.d_x.p, xfl, c.d_bad.p, UpdArgs{});
+    else if (mp) hipLaunchKernelGGL((k_backsolve_t<true>), dim3(mp_n), dim3(TPB), handover_lds(dpx.xmode, mp_dn_lds, mp_n), s, dpx, c.d_tab.p + mp_dn_off, c.d_pool.p, c.d_x.p, 0, xfl, 1, c.d_bad.p, UpdArgs{});
     // incremental steps: the state update (state = l_point + dx, pinned mirrors of state / dx / failure record) rides on the
     // back substitution of the front that owns the pose -- every visited pose lives in a front of this sweep -- instead of
     // a launch of its own over all poses
@@ -805,8 +810,8 @@ static bool inc_fast_step(Context &c, GraphPack &gp, int N, int F, int Fold, int
     const UpdArgs upd = batch ? UpdArgs{} : UpdArgs{ c.d_perm.p, gp.d_lp.p, nullptr, gp.d_dx.p, gp.h_out.p, gp.h_dx.p, c.h_bad.p };
     bool rode = one;
     if (id && !one) {
-        if (g_opt.wave_backsolve && id_maxns <= BSW_MAX_NS) hipLaunchKernelGGL(k_backsolve_w, dim3(id_n), dim3(TPB), id_lds, s, c.dp, c.d_tab.p + id_off, c.d_pool.p, c.d_x.p, xfl, c.d_bad.p, upd);
-        else hipLaunchKernelGGL((k_backsolve_t<true>), dim3(id_n), dim3(TPB), id_lds, s, c.dp, c.d_tab.p + id_off, c.d_pool.p, c.d_x.p, 0, xfl, 1, c.d_bad.p, upd);
+        if (g_opt.wave_backsolve && id_maxns <= BSW_MAX_NS) hipLaunchKernelGGL(k_backsolve_w, dim3(id_n), dim3(TPB), handover_lds(dpx.xmode, id_lds, id_n), s, dpx, c.d_tab.p + id_off, c.d_pool.p, c.d_x.p, xfl, c.d_bad.p, upd);
+        else hipLaunchKernelGGL((k_backsolve_t<true>), dim3(id_n), dim3(TPB), handover_lds(dpx.xmode, id_lds, id_n), s, dpx, c.d_tab.p + id_off, c.d_pool.p, c.d_x.p, 0, xfl, 1, c.d_bad.p, upd);
         rode = true;
     }
     for (int l = (one ? -1 : id ? (needed ? -1 : id_rest) : nLev - 1); l >= 0; l--) {

@@ -242,7 +242,7 @@ typedef struct aprilsam_amd_stats {
                                   (INTEGRATION.md section 4).  > 0 therefore means: this step's states deviate from the reference's by design */
     int    inc_fronts_updated; /* fronts whose factor took a low-rank update in this step (option "inc_update") instead of being re-assembled and
                                   re-factorised; reserved0 counts all fronts the step regenerated */
-    int    reserved2;
+    int    dn_launch_fronts;   /* fronts in the step's multi-level back substitution launch (one workgroup each, x handed from parent to child inside the launch), 0: none */
 } aprilsam_amd_stats_t;
 int aprilsam_amd_get_stats(const april_graph_cholesky_param_t *param, aprilsam_amd_stats_t *out);
 
@@ -351,6 +351,10 @@ void aprilsam_amd_clear_error(void);
  *   "wave_backsolve"    1 (default): fronts whose L panel fits LDS (multi-level launch, latency-bound levels, incremental
  *                       steps) are back-substituted column-per-lane -- one in-register chain per 64 columns; 0 = the
  *                       per-32-column-block kernel everywhere
+ *   "tagged_x"          how a front of a multi-level back substitution hands its x to its children (APRILSAM_AMD_TAGGED_X).  1 (default):
+ *                       as epoch-tagged 16-byte granules that the children's lanes poll, no flag; a launch that holds a front of more
+ *                       than 256 update rows takes form 2.  0 = x stored write-through, then a flag, no L2 write-back.  2 = plain x,
+ *                       L2 write-back, flag: the form of every other hand-over.  Speed only, results bitwise the same
  *   "linearize_staged_min"  graphs with at least this many factors (default 32768) write the J^T W J blocks out through
  *                       LDS with coalesced stores; smaller ones store directly (one latency chain less)
  *   "mem_cap_mb"        > 0: any single device buffer above this size is refused as if the device were out of memory
