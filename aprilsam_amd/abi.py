@@ -104,6 +104,22 @@ class LmReport(C.Structure):
 
 
 LM_CONVERGED_F, LM_CONVERGED_X, LM_STALLED, LM_MAX_ITERS = 1, 2, 3, 4
+
+
+class ChordalOpts(C.Structure):
+    """aprilsam_amd_chordal_opts_t (include/aprilsam_amd.h)"""
+    _fields_ = [("stages", C.c_int)]
+
+
+class ChordalReport(C.Structure):
+    """aprilsam_amd_chordal_report_t"""
+    _fields_ = [("status", C.c_int), ("n_degenerate", C.c_int), ("not_spd_stage", C.c_int), ("min_norm", C.c_double),
+                ("F_initial", C.c_double), ("F_final", C.c_double)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # robust loss kinds of xyt / xytpos factors (include/aprilsam_amd.h: aprilsam_amd_factor_set_robust; DESIGN.md section 15)
 ROBUST_NONE, ROBUST_HUBER, ROBUST_CAUCHY, ROBUST_DCS = 0, 1, 2, 3
 

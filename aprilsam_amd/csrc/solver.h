@@ -102,6 +102,9 @@ long long path_solve_bytes(const april_graph_cholesky_param_t *param);
 int max_selected(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *factors, int *out);   // solver_pack.inc.h
 void lm_opts_init(aprilsam_amd_lm_opts_t *opts);                                                                    // solver_lm.inc.h
 int optimize_lm(april_graph_t *g, april_graph_cholesky_param_t *param, const aprilsam_amd_lm_opts_t *opts, aprilsam_amd_lm_report_t *report, double *trace);
+void chordal_opts_init(aprilsam_amd_chordal_opts_t *opts);                                                         // solver_chordal.inc.h
+int initialize_chordal(april_graph_t *g, april_graph_cholesky_param_t *param, const aprilsam_amd_chordal_opts_t *opts, aprilsam_amd_chordal_report_t *report,
+                       double *rot_out, double *raw_out);
 // max-mixture factors (host_objects.cpp)
 constexpr int MAX_MIX_K = 8;
 bool is_native_max(const april_graph_factor_t *f);                 // type 3 with this library's eval

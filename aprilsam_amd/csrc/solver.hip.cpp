@@ -16,6 +16,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <atomic>
@@ -30,6 +31,7 @@
 #include "maxmix.hip.h"
 #include "robust.hip.h"
 #include "lm.hip.h"
+#include "chordal.hip.h"
 #include "selinv.hip.h"
 #include "pathsolve.hip.h"
 #include "plan.h"
@@ -246,6 +248,7 @@ struct PatchList {
 #include "solver_marginals.inc.h"
 #include "solver_gating.inc.h"
 #include "solver_lm.inc.h"
+#include "solver_chordal.inc.h"
 
 // ------------------------------------------------------------------------------------------------------
 // Runtime warm-up, once per process, from april_graph_cholesky_param_init (the API's set-up call; aprilsam.c:45-64 has nothing to set up).
@@ -504,4 +507,13 @@ extern "C" void aprilsam_amd_lm_opts_init(aprilsam_amd_lm_opts_t *opts) { asam::
 extern "C" int aprilsam_amd_optimize_lm(april_graph_t *graph, april_graph_cholesky_param_t *param, const aprilsam_amd_lm_opts_t *opts,
                                         aprilsam_amd_lm_report_t *report, double *trace) {
     return asam::optimize_lm(graph, param, opts, report, trace);
+}
+extern "C" void aprilsam_amd_chordal_opts_init(aprilsam_amd_chordal_opts_t *opts) { asam::chordal_opts_init(opts); }
+extern "C" int aprilsam_amd_initialize_chordal(april_graph_t *graph, april_graph_cholesky_param_t *param, const aprilsam_amd_chordal_opts_t *opts,
+                                               aprilsam_amd_chordal_report_t *report, double *rot_out) {
+    return asam::initialize_chordal(graph, param, opts, report, rot_out, nullptr);
+}
+extern "C" int aprilsam_amd_debug_chordal_raw(april_graph_t *graph, april_graph_cholesky_param_t *param, const aprilsam_amd_chordal_opts_t *opts,
+                                              aprilsam_amd_chordal_report_t *report, double *raw) {
+    return asam::initialize_chordal(graph, param, opts, report, nullptr, raw);
 }

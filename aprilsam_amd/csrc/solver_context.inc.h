@@ -160,6 +160,8 @@ struct Context {
     hipGraphExec_t gexec_lm = nullptr;
     const void *lm_key[9] = {};
     DBuf<double> d_lm_trial, d_lm_hacc, d_lm_terms, d_lm_trace; DBuf<LmScalars> d_lm; HBuf<LmScalars> h_lm;
+    // chordal initialisation (solver_chordal.inc.h): [scratch of the state update 3N][theta N][4 scalars]; the components chosen for the max factors
+    DBuf<double> d_ch; HBuf<double> h_ch; DBuf<int> d_ch_sel;
     int api_key_runs = 0;                          // calls seen with this key: the first one runs without a graph (below)
     // captured graphs that are no longer current: hipGraphExecDestroy takes 0.24 ms on this stack, so they are destroyed while the
     // GPU works on a step (reap_retired), not on the way to the next plan
@@ -210,6 +212,7 @@ struct Context {
         d_pool.release(); d_H.release(); d_x.release(); d_diag.release(); d_bad.release(); h_bad.release(); patches.release();
         h_done.release(); h_kstamp.release(); d_prof.release(); d_upd.release(); d_wbuf.release(); d_flags.release(); d_flevel.release(); d_epoch.release(); d_marks.release(); d_perm.release(); d_solve_tab.release(); d_dinv.release(); d_bsb_far.release(); d_bsb_flags.release(); d_guard.release(); d_guard_cnt.release(); n_guard = 0;
         d_lm_trial.release(); d_lm_hacc.release(); d_lm_terms.release(); d_lm_trace.release(); d_lm.release(); h_lm.release();
+        d_ch.release(); h_ch.release(); d_ch_sel.release();
         retire(gexec); retire(gexec_api); retire(gexec_lm); reap_retired(true);
         if (have_events) for (auto &e : ev) (void)hipEventDestroy(e);
         have_events = false;
@@ -871,29 +874,9 @@ static void enqueue_factor_level(Context &c, const LevelPlan &L, hipStream_t s, 
     }
 }
 
-// enqueue: linearise -> per level {assemble+factor} -> back substitution -> state update
-// ev != null: record stage events (0 start, 1 after linearise, 2 after factor, 3 after solve+update)
-// ktime: bracket EVERY kernel launch with its own HIP event pair on this stream (c.k_ev / c.k_ids)
-// st_dest (LM iterations, solver_lm.inc.h): where the state update writes x (+) h instead of d_state -- the trial buffer
-static void enqueue_numeric(Context &c, GraphPack &gp, hipStream_t s, hipEvent_t *ev, bool unary_at_lp = false, bool ktime = false, bool io_host = false, bool relin = false,
-                            double *st_dest = nullptr) {
-    const Plan &P = c.plan;
-    const int F = P.F, N = P.N;
-    size_t nev = 0;
-    if (ktime) { c.k_ids.clear(); c.k_lev.clear(); }
-    int cur_level = -1;                              // (profile: the level the launches that follow belong to; multi-level launches: their first level)
-    auto tic = [&](int id) {
-        if (!ktime) return;
-        if (c.k_ev.size() < nev + 2) { c.k_ev.resize(nev + 2); HIPCHECK(hipEventCreate(&c.k_ev[nev])); HIPCHECK(hipEventCreate(&c.k_ev[nev + 1])); }
-        HIPCHECK(hipEventRecord(c.k_ev[nev], s));
-        c.k_ids.push_back(id); c.k_lev.push_back(cur_level);
-    };
-    auto toc = [&]() { if (ktime) { HIPCHECK(hipEventRecord(c.k_ev[nev + 1], s)); nev += 2; } };
-    if (ev) HIPCHECK(hipEventRecord(ev[0], s));
-    if (c.dp.prof) HIPCHECK(hipMemsetAsync(c.d_prof.p, 0, (size_t)8 * PROF_SLOTS * P.nF, s));
-    if (io_host) hipLaunchKernelGGL(k_load_states, dim3((3 * N + TPB - 1) / TPB), dim3(TPB), 0, s, 3 * N, gp.h_state.p, gp.d_state.p, gp.d_lp.p);
-    enqueue_poison(c, s, nullptr, P.nF);
-    tic(K_LINEARIZE);
+// what fills the contribution slots of a Gauss-Newton step: selection, robust weights, linearisation (+ the host-evaluated factors' blocks)
+static void enqueue_linearise(Context &c, GraphPack &gp, hipStream_t s, bool unary_at_lp) {
+    const int F = c.plan.F;
     enqueue_select(gp, s);                           // max-mixture factors: the component selected at l_point goes into the factor's slot
     enqueue_robust(gp, s, unary_at_lp ? gp.d_upt.p : (const double *)nullptr);      // robust factors: W_eff = w(s) W0 into the factor's slot
     {   // (a variant of the kernel without the asymmetric-W orientation branch, for graphs that have no such factor, was measured in round 6: no
@@ -910,6 +893,34 @@ static void enqueue_numeric(Context &c, GraphPack &gp, hipStream_t s, hipEvent_t
         hipLaunchKernelGGL(k_scatter_host, dim3((nh + TPB - 1) / TPB), dim3(TPB), 0, s, nh, gp.d_host_idx.p, gp.d_hostH.p, gp.d_fb.p, c.d_swap.p,
                            c.dp.slot_blk, c.dp.slot_rhs, c.d_H.p);
     }
+}
+
+// enqueue: linearise -> per level {assemble+factor} -> back substitution -> state update
+// ev != null: record stage events (0 start, 1 after linearise, 2 after factor, 3 after solve+update)
+// ktime: bracket EVERY kernel launch with its own HIP event pair on this stream (c.k_ev / c.k_ids)
+// st_dest (LM iterations, solver_lm.inc.h): where the state update writes x (+) h instead of d_state -- the trial buffer
+// fill (chordal initialisation, solver_chordal.inc.h): what writes the contribution slots, clears the failure record and advances the step
+// counter in place of the selection, the weights and the linearisation
+static void enqueue_numeric(Context &c, GraphPack &gp, hipStream_t s, hipEvent_t *ev, bool unary_at_lp = false, bool ktime = false, bool io_host = false, bool relin = false,
+                            double *st_dest = nullptr, const std::function<void()> *fill = nullptr) {
+    const Plan &P = c.plan;
+    const int N = P.N;
+    size_t nev = 0;
+    if (ktime) { c.k_ids.clear(); c.k_lev.clear(); }
+    int cur_level = -1;                              // (profile: the level the launches that follow belong to; multi-level launches: their first level)
+    auto tic = [&](int id) {
+        if (!ktime) return;
+        if (c.k_ev.size() < nev + 2) { c.k_ev.resize(nev + 2); HIPCHECK(hipEventCreate(&c.k_ev[nev])); HIPCHECK(hipEventCreate(&c.k_ev[nev + 1])); }
+        HIPCHECK(hipEventRecord(c.k_ev[nev], s));
+        c.k_ids.push_back(id); c.k_lev.push_back(cur_level);
+    };
+    auto toc = [&]() { if (ktime) { HIPCHECK(hipEventRecord(c.k_ev[nev + 1], s)); nev += 2; } };
+    if (ev) HIPCHECK(hipEventRecord(ev[0], s));
+    if (c.dp.prof) HIPCHECK(hipMemsetAsync(c.d_prof.p, 0, (size_t)8 * PROF_SLOTS * P.nF, s));
+    if (io_host) hipLaunchKernelGGL(k_load_states, dim3((3 * N + TPB - 1) / TPB), dim3(TPB), 0, s, 3 * N, gp.h_state.p, gp.d_state.p, gp.d_lp.p);
+    enqueue_poison(c, s, nullptr, P.nF);
+    tic(K_LINEARIZE);
+    if (fill) (*fill)(); else enqueue_linearise(c, gp, s, unary_at_lp);
     toc();
     if (ev) HIPCHECK(hipEventRecord(ev[1], s));
     const int l0 = c.persist_l0 >= 0 ? c.persist_l0 : P.nLevels;        // levels >= l0: one multi-level launch each way
@@ -1060,7 +1071,8 @@ static void flush_orientation(Context &c, hipStream_t s) {
     c.wt_dirty = false;
 }
 // make sure plan / device buffers match the packed graph; returns true if the plan was reused
-static bool prepare_plan(Context &c, GraphPack &gp, const april_graph_t *g, bool upload = true) {
+// xy_hint = false (chordal initialisation: its result must not depend on the incoming states): a new plan is made from the graph alone
+static bool prepare_plan(Context &c, GraphPack &gp, const april_graph_t *g, bool upload = true, bool xy_hint = true) {
     const int N = gp.N, F = gp.F;
     bool same = c.have_plan && c.patN == N && (int)c.pat.size() == 2 * F && c.plan.leaf_nodes == g_opt.leaf_nodes && c.plan_pin == g_opt.pin_last &&
                 c.plan_persist == launch_table_key() && c.inc.t_first.empty();        // (a plan extended by tail fronts is only driven by inc_fast_step)
@@ -1075,7 +1087,7 @@ static bool prepare_plan(Context &c, GraphPack &gp, const april_graph_t *g, bool
     std::vector<double> xy((size_t)2 * N);
     for (int i = 0; i < N; i++) { xy[2 * i] = gp.h_state.p[3 * i]; xy[2 * i + 1] = gp.h_state.p[3 * i + 1]; }
     const double tb0 = now_ms();
-    build_plan(c.plan, N, F, c.pat.data(), xy.data(), g_opt.leaf_nodes);
+    build_plan(c.plan, N, F, c.pat.data(), xy_hint ? xy.data() : nullptr, g_opt.leaf_nodes);
     if (g_opt.pool_guard > 0) {              // debug: a guard band behind every frontal array (upload_plan fills them, check_guard reads them)
         Plan &P = c.plan;
         const long long G = ((long long)g_opt.pool_guard + 31) & ~31ll;

@@ -50,6 +50,15 @@ class LMError(RuntimeError):
         self.code = code
 
 
+class ChordalError(RuntimeError):
+    """a negative return of aprilsam_amd_initialize_chordal: .code is the return value, .report the report's fields (written on -2 only)"""
+
+    def __init__(self, code, msg=None, report=None):
+        super().__init__(f"initialize_chordal failed: {code} {msg or ''}".strip())
+        self.code = code
+        self.report = report
+
+
 class SolverLib:
     """A loaded shared library exporting the reference API names."""
 
@@ -126,6 +135,12 @@ class SolverLib:
                 d.aprilsam_amd_lm_opts_init.restype = None
                 d.aprilsam_amd_optimize_lm.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.POINTER(abi.LmOpts),
                                                        C.POINTER(abi.LmReport), _dp]
+            if hasattr(d, "aprilsam_amd_initialize_chordal"):    # (defined in the HIP translation unit)
+                d.aprilsam_amd_chordal_opts_init.argtypes = [C.POINTER(abi.ChordalOpts)]
+                d.aprilsam_amd_chordal_opts_init.restype = None
+                for nm in ("aprilsam_amd_initialize_chordal", "aprilsam_amd_debug_chordal_raw"):
+                    getattr(d, nm).argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.POINTER(abi.ChordalOpts),
+                                               C.POINTER(abi.ChordalReport), _dp]
             if hasattr(d, "aprilsam_amd_factor_max_create"):
                 d.aprilsam_amd_factor_max_create.restype = C.POINTER(abi.Factor)
                 d.aprilsam_amd_factor_max_create.argtypes = [C.POINTER(C.POINTER(abi.Factor)), _dp, C.c_int]
@@ -548,6 +563,35 @@ class Graph:
         out = rep.asdict()
         if trace:
             out["trace"] = tr[:rep.iterations].copy()
+        return out
+
+    def initialize_chordal(self, param, rot=False, raw=False, **opts):
+        """Chordal initialisation on the GPU (include/aprilsam_amd.h: aprilsam_amd_initialize_chordal).
+        opts: fields of aprilsam_amd_chordal_opts_t (stages).  Returns the report's fields as a dict, plus "rot": the (N, 2) array
+        (c_i, s_i) of stage 1 when rot is true, or -- through the debug entry point -- "raw": the (2, N, 3) padded solutions of both
+        stages when raw is true.  Raises ChordalError(rc) on a negative return."""
+        o = abi.ChordalOpts()
+        self.lib.dll.aprilsam_amd_chordal_opts_init(C.byref(o))
+        for k, v in opts.items():
+            if k not in dict(abi.ChordalOpts._fields_):
+                raise TypeError(f"unknown chordal option {k}")
+            setattr(o, k, v)
+        rep = abi.ChordalReport()
+        n = self.n_nodes
+        pp = param.ptr if param is not None else None
+        if raw:
+            buf = np.full((2, n, 3), np.nan)
+            rc = self.lib.dll.aprilsam_amd_debug_chordal_raw(self.ptr, pp, C.byref(o), C.byref(rep), _np_d(buf))
+        else:
+            buf = np.full((n, 2), np.nan) if rot else None
+            rc = self.lib.dll.aprilsam_amd_initialize_chordal(self.ptr, pp, C.byref(o), C.byref(rep), _np_d(buf) if rot else None)
+        if rc < 0:
+            raise ChordalError(rc, self.lib.last_error(), rep.asdict() if rc == -2 else None)
+        out = rep.asdict()
+        if raw:
+            out["raw"] = buf
+        elif rot:
+            out["rot"] = buf
         return out
 
     def batch_resident(self, param, iters):

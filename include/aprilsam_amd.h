@@ -516,6 +516,45 @@ typedef struct {
 int aprilsam_amd_optimize_lm(april_graph_t *graph, april_graph_cholesky_param_t *param, const aprilsam_amd_lm_opts_t *opts,
                              aprilsam_amd_lm_report_t *report, double *trace);
 
+/* ---- chordal initialisation (Carlone et al., ICRA 2015) -----------------------------------------------------
+ * Every optimiser above starts from the states the caller supplies; from a poor start LM does not reach the optimum.
+ * aprilsam_amd_initialize_chordal computes a start from the factors alone -- it reads no state -- as two linear least-squares problems on
+ * the graph's own sparsity pattern, each solved by the plan, assembly, factorisation and back substitution of a batch step, damping 0.
+ *   Stage 1    headings.  Unknown u_i = (c_i, s_i) per pose.  An xyt factor (a, b, z, W) with w = W[2][2] > 0 contributes
+ *              w |R(z_theta) u_a - u_b|^2, an xytpos prior with w > 0 contributes w |u_a - (cos z_theta, sin z_theta)|^2.  Then
+ *              theta_i = atan2(s_i, c_i); a pose with c^2 + s^2 == 0 or a non-finite value keeps its incoming heading (n_degenerate).
+ *   Stage 2    positions, headings held fixed.  Unknown t_i per pose, Wxy = W[0:2, 0:2].  An xyt factor with W[0][0] > 0 and
+ *              det Wxy > 0 contributes |R(theta_a)' (t_b - t_a) - z_xy|^2_Wxy, a prior under the same condition |t_a - z_xy|^2_Wxy.
+ *   A factor that fails a stage's condition contributes nothing to that stage (an xy-only prior enters stage 2 only); the xy-theta cross
+ *   terms of W are ignored.  A robust loss is ignored (the plain W is used); a max factor enters as the component with the largest log
+ *   weight, lowest index on a tie.
+ * What the call leaves: state = l_point = the initial guess; delta_X and param->tikhanov untouched; the param's plan kept; the retained
+ * factor DROPPED as after aprilsam_amd_optimize_lm (marginals and gating return -1 until the next april_graph_cholesky).  Two calls give
+ * identical bits, and the result does not depend on the incoming states (degenerate poses and stages = 1 apart).
+ * Typical use: aprilsam_amd_initialize_chordal, then aprilsam_amd_optimize_lm.
+ * Returns 0, or: -1 empty graph; -4 host-evaluated (foreign) factors; -12 sharded param, or an information matrix that is not symmetric;
+ * -13 a null argument or bad stages; -14 no HIP device; -2 the system of a stage is not positive definite (a graph without a heading
+ * prior, a part of the graph that no prior reaches): report->not_spd_stage says which.  On a refusal the graph is untouched and nothing
+ * is written -- except the report on -2; aprilsam_amd_last_error says why.  A failure during the run (-9 / -10 / -11) behaves as on
+ * every solver entry point. */
+typedef struct {
+    int    stages;        /* 3 = both (default), 1 = headings only: positions keep their incoming values */
+} aprilsam_amd_chordal_opts_t;
+void aprilsam_amd_chordal_opts_init(aprilsam_amd_chordal_opts_t *opts);
+typedef struct {
+    int    status;                 /* 0 ok (-2 on that refusal) */
+    int    n_degenerate;           /* poses that kept their incoming heading */
+    int    not_spd_stage;          /* 0, 1 or 2 */
+    double min_norm;               /* min_i |u_i| (0 when a pose is degenerate) */
+    double F_initial, F_final;     /* LM's objective at the incoming / returned states */
+} aprilsam_amd_chordal_report_t;
+/* rot_out: NULL or 2*N doubles, (c_i, s_i) of stage 1 in node order, before normalisation */
+int aprilsam_amd_initialize_chordal(april_graph_t *graph, april_graph_cholesky_param_t *param, const aprilsam_amd_chordal_opts_t *opts,
+                                    aprilsam_amd_chordal_report_t *report, double *rot_out);
+/* debug: the same call; raw: 6*N doubles, the solution of stage 1 then of stage 2 (3 per pose, node order) with the padded third unknown */
+int aprilsam_amd_debug_chordal_raw(april_graph_t *graph, april_graph_cholesky_param_t *param, const aprilsam_amd_chordal_opts_t *opts,
+                                   aprilsam_amd_chordal_report_t *report, double *raw);
+
 /* ---- max-mixture factors (Olson & Agarwal, RSS 2012) ---------------------------------------------------
  * A max factor on the ordered pair (a, b) holds K = 1..8 components, each an xyt factor made by april_graph_factor_xyt_create on
  * the same (a, b) with a symmetric W of det W > 0, and a log weight per component.  At a point p component i scores
