@@ -241,6 +241,7 @@ struct PatchList {
 // split by topic):
 #include "solver_pack.inc.h"
 #include "solver_context.inc.h"
+#include "solver_launch.inc.h"
 #include "solver_inc.inc.h"
 #include "solver_calls.inc.h"
 #include "solver_resident.inc.h"

@@ -77,7 +77,8 @@ static void batch_impl(april_graph_t *g, april_graph_cholesky_param_t *param) {
             set_lambda(c, gp, param->tikhanov);
             t2 = t3 = now_ms();                         // (stats: the pass over the factor objects below counts as device time -- it runs under it)
             c.h_bad.p[0] = c.h_bad.p[1] = c.h_bad.p[2] = c.h_bad.p[3] = 0;
-            run_numeric(c, gp, false, false, true);
+            RunArgs r; r.io_host = true;
+            run_numeric(c, gp, r);
             const long long v0 = gp.content_version; const int dev0 = gp.F_on_device;
             pack_factors(gp, g);                        // ... the pass over the factor objects, under the GPU's work
             if (gp.content_version != v0 || gp.F_on_device != dev0 || gp.dirty_hi > gp.dirty_lo || !gp.host_idx.empty()) {
@@ -101,7 +102,8 @@ static void batch_impl(april_graph_t *g, april_graph_cholesky_param_t *param) {
         // re-linearised first, aprilsam.c:131-135, l_point), ..., k_update_states leaves new states (h_lp), dx and the pivot
         // flag in pinned mirrors.  No copy-engine call on the path.
         c.h_bad.p[0] = c.h_bad.p[1] = c.h_bad.p[2] = c.h_bad.p[3] = 0;          // (the kernels only ever write a SET failure record)
-        run_numeric(c, gp, timing, false, true);
+        RunArgs r; r.timing = timing; r.io_host = true;
+        run_numeric(c, gp, r);
     }
     const bool fbp = g_fbprof_on && !hybrid && !speculate && !reused;
     const double f0 = fbp ? now_ms() : 0;
@@ -330,7 +332,8 @@ static void inc_impl(april_graph_t *g, april_graph_cholesky_param_t *param) {
         for (int i = 0; i < N; i++) if (c.plan.perm[i] < c.batch_nodes && param->tikhanov > 0) c.h_lambda[i] = param->tikhanov;
         HIPCHECK(hipMemcpyAsync(c.d_lambda.p, c.h_lambda.data(), (size_t)8 * N, hipMemcpyHostToDevice, gp.stream));
         c.lambda_N = -1;                                  // (not the uniform batch value)
-        run_numeric(c, gp, false, true);
+        RunArgs r; r.unary_at_lp = true;
+        run_numeric(c, gp, r);
         inc_prepare(c);
     }
     c.inc_F = F; c.inc_N = N; c.same_topo_batches = 0;
@@ -446,10 +449,8 @@ static void enqueue_backsolve_current(Context &c, GraphPack &gp, const std::vect
             maxns = std::max(maxns, ns); wlds = std::max(wlds, backsolve_lds(m, ns, true));
             tlds = std::max(tlds, (size_t)(m + NB + 8 + NB * (NB + 1)) * 8);
         }
-        if (g_opt.wave_backsolve && maxns <= BSW_MAX_NS && wlds <= 160 * 1024)
-            hipLaunchKernelGGL(k_backsolve_w, dim3((unsigned)n), dim3(TPB), wlds, s, c.dp, c.d_solve_tab.p + off[l], c.d_pool.p, c.d_x.p, (int *)nullptr, (int *)nullptr, UpdArgs{});
-        else
-            hipLaunchKernelGGL((k_backsolve_t<false>), dim3((unsigned)n), dim3(TPB), tlds, s, c.dp, c.d_solve_tab.p + off[l], c.d_pool.p, c.d_x.p, 0, (int *)nullptr, 0, (int *)nullptr, UpdArgs{});
+        const bool wave = g_opt.wave_backsolve && maxns <= BSW_MAX_NS && wlds <= 160 * 1024;
+        launch_backsolve_list(c, s, wave ? BS_WAVE : BS_THREAD, c.d_solve_tab.p + off[l], n, wave ? wlds : tlds, 0, nullptr, UpdArgs{});
     }
 }
 

@@ -61,7 +61,8 @@ static int chordal_unanchored_stage(const GraphPack &gp, const std::vector<int> 
 static bool chordal_run_stage(Context &c, GraphPack &gp, hipStream_t s, int stage, double *scratch, const double *theta) {
     rewind_epoch(c, s, 1);
     const std::function<void()> fill = [&] { chordal_enqueue_fill(c, gp, s, stage, theta); };
-    enqueue_numeric(c, gp, s, nullptr, false, false, false, false, scratch, &fill);
+    NumericArgs a; a.st_dest = scratch; a.fill = &fill;
+    enqueue_numeric(c, gp, s, a);
     HIPCHECK(hipMemcpyAsync(c.h_bad.p, c.d_bad.p, 16, hipMemcpyDeviceToHost, s));
     HIPCHECK(hipStreamSynchronize(s));
     const bool not_spd = check_bad(c);             // (a dependency time-out fails the call: ERR_DEP_TIMEOUT)

@@ -1,5 +1,5 @@
 // solver_context.inc.h -- part of solver.hip.cpp (ONE translation unit: the kernels of kernels.hip.h are compiled once); included from there,
-// inside namespace asam.  Contents: the solver context of a param (plan, device tables, fronts, captured graphs), the failure path, plan upload, launch tables and the numeric phase of a batch step.
+// inside namespace asam.  Contents: the solver context of a param (plan, device tables, fronts, captured graphs), the failure path, plan upload with its launch tables, the step counter, plan reuse and the orientation of asymmetric factors (the launches themselves: solver_launch.inc.h).
 // ------------------------------------------------------------------------------------------------------
 // solver context — one per april_graph_cholesky_param_t pointer
 // ------------------------------------------------------------------------------------------------------
@@ -162,7 +162,7 @@ struct Context {
     DBuf<double> d_lm_trial, d_lm_hacc, d_lm_terms, d_lm_trace; DBuf<LmScalars> d_lm; HBuf<LmScalars> h_lm;
     // chordal initialisation (solver_chordal.inc.h): [scratch of the state update 3N][theta N][4 scalars]; the components chosen for the max factors
     DBuf<double> d_ch; HBuf<double> h_ch; DBuf<int> d_ch_sel;
-    int api_key_runs = 0;                          // calls seen with this key: the first one runs without a graph (below)
+    int api_key_runs = 0;                          // calls seen with this key: the first one runs without a graph (run_numeric)
     // captured graphs that are no longer current: hipGraphExecDestroy takes 0.24 ms on this stack, so they are destroyed while the
     // GPU works on a step (reap_retired), not on the way to the next plan
     // A retired graph may still have launches in flight (resident / sharded loops enqueue steps without a sync in between): it carries an
@@ -710,83 +710,11 @@ static void upload_plan(Context &c, hipStream_t s, const ShardLayout *lay = null
     c.st.nnz_L = P.nnzL; c.st.flops_factor = P.flops; c.st.bytes_fronts = 8.0 * (double)pool_doubles;
 }
 
-static void set_small_attr() {
-    static std::once_flag once[MAX_SLOTS];          // (function attributes are kept per device)
-    std::call_once(once[physical_device(t_slot) % MAX_SLOTS], [] {
-        HIPCHECK(hipFuncSetAttribute((const void *)k_front_small<256>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHECK(hipFuncSetAttribute((const void *)k_front_small<512>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHECK(hipFuncSetAttribute((const void *)k_front_small<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHECK(hipFuncSetAttribute((const void *)k_backsolve_t<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHECK(hipFuncSetAttribute((const void *)k_backsolve_t<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHECK(hipFuncSetAttribute((const void *)k_backsolve_w, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHECK(hipFuncSetAttribute((const void *)k_backsolve_t<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHECK(hipFuncSetAttribute((const void *)k_block_chain, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHECK(hipFuncSetAttribute((const void *)k_backsolve_blk, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHECK(hipFuncSetAttribute((const void *)k_block_solve<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHECK(hipFuncSetAttribute((const void *)k_block_solve<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHECK(hipFuncSetAttribute((const void *)k_inc_one<256>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHECK(hipFuncSetAttribute((const void *)k_inc_one<512>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHECK(hipFuncSetAttribute((const void *)k_inc_one<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    });
-}
-
-// back substitution of one level: update-row products of the large fronts on many workgroups, then one workgroup per front
-// (list_off >= 0: the level's list of every front replaced by the list_n entries there -- an XCD-placed list of a level of small fronts only)
-template <class Tic, class Toc>
-static void launch_backsolve(Context &c, const LevelPlan &L, hipStream_t s, Tic tic, Toc toc, const int *tab = nullptr, UpdArgs upd = UpdArgs{}, int list_off = -1, int list_n = 0) {
-    if (!tab) tab = c.d_tab.p;
-    if (!L.n_all) return;
-    tic(K_BACKSOLVE);
-    if (L.bs_gemv.grid > 0)
-        hipLaunchKernelGGL(k_backsolve_gemv, dim3(L.bs_gemv.grid), dim3(TPB), 0, s, c.dp, tab + L.bs_gemv.list_off, tab + L.bs_gemv.pre_off,
-                           L.bs_gemv.n, c.d_pool.p, c.d_x.p);
-    // wide fronts: chain + helper workgroups (k_backsolve_blk); the level's other fronts below
-    int n_all = list_off >= 0 ? list_n : L.n_all, all_off = list_off >= 0 ? list_off : L.all_off; size_t solve_lds = L.solve_lds;
-    if (L.bs_blk.grid > 0) {
-        hipLaunchKernelGGL(k_backsolve_blk, dim3(L.bs_blk.grid), dim3(TPB), L.bs_blk_lds, s, c.dp, tab + L.bs_blk.list_off, tab + L.bs_blk.pre_off, L.bs_blk.n,
-                           c.d_pool.p, c.d_x.p, c.d_dinv.p, c.d_bsb_flags.p, c.d_bsb_far.p, L.bs_gemv.grid > 0 ? 1 : 0, c.d_bad.p, upd);
-        n_all = L.n_rest; all_off = L.rest_off; solve_lds = L.rest_lds;
-        if (!n_all) { toc(); return; }
-    }
-    // latency-bound levels of small fronts: column-per-lane form with the L panel in LDS (at least two workgroups per CU)
-    if (g_opt.wave_backsolve && L.bs_gemv.grid == 0 && L.n_all < g_opt.tp_fronts && L.maxns <= BSW_MAX_NS && L.solve_w_lds <= 80 * 1024)
-        hipLaunchKernelGGL(k_backsolve_w, dim3(n_all), dim3(TPB), L.solve_w_lds, s, c.dp, tab + all_off, c.d_pool.p, c.d_x.p, (int *)nullptr, c.d_bad.p, upd);
-    else if (solve_lds >= (size_t)(BS_TALL_ROWS + NB + 8 + NB * (NB + 1)) * 8)
-        hipLaunchKernelGGL((k_backsolve_t<false, true>), dim3(n_all), dim3(TPB), solve_lds, s, c.dp, tab + all_off, c.d_pool.p, c.d_x.p, L.bs_gemv.grid > 0 ? 1 : 0, (int *)nullptr, 0, c.d_bad.p, upd);
-    else
-        hipLaunchKernelGGL((k_backsolve_t<false>), dim3(n_all), dim3(TPB), solve_lds, s, c.dp, tab + all_off, c.d_pool.p, c.d_x.p, L.bs_gemv.grid > 0 ? 1 : 0, (int *)nullptr, 0, c.d_bad.p, upd);
-    toc();
-}
-
-// k_front_small with the configured workgroup size (option small_threads: 256 / 512 / 1024)
-// the multi-level launch of the factorisation: every small front of levels >= persist_l0
-// the plan as the batch path's two multi-level launches see it: flags carry the iteration number
 // the x entries that stay zero for good (inc.zpos: what phantom rows point at) are valid in every step
 static void set_const_granules(Context &c, hipStream_t s) {
     static const unsigned G[12] = { 0u, (unsigned)XG_CONST, 0u, (unsigned)XG_CONST, 0u, (unsigned)XG_CONST, 0u, (unsigned)XG_CONST, 0u, (unsigned)XG_CONST, 0u, (unsigned)XG_CONST };
     HIPCHECK(hipMemcpyAsync(c.d_xg.p + (size_t)3 * c.inc.zpos, G, sizeof(G), hipMemcpyHostToDevice, s));
 }
-// The hand-over form of ONE multi-level back substitution whose tallest update block has max_upd_rows rows: granules are gathered one per lane
-// (kernels.hip.h gather_x), so a launch with a taller block takes the form every other flag uses.  (No plan met so far puts such a front into a
-// multi-level launch -- a front of 86 update blocks that still fits a workgroup's LDS needs four or more ancestors of at most 24-33 poses each
-// -- but an incremental step's fronts near the root collect rows without such a bound.)
-static int launch_xmode(const Context &c, int max_upd_rows) { return c.dp.xmode == X_TAGGED && max_upd_rows > TPB ? (int)X_FLUSH : c.dp.xmode; }
-static int device_cus() {
-    int cus = 0;
-    HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, physical_device(t_slot)));
-    return cus;
-}
-// Dynamic LDS of a multi-level back substitution of `grid` workgroups: two workgroups of more than 80 KB each cannot share a compute unit's 160 KB.
-// The write-through form NEEDS one workgroup of the launch per unit (kernels.hip.h publish_flag_wt): it always gets the larger request, and a
-// grid of more workgroups than units (persist_max_fronts above its default, the empty slots of a placed list) then runs in rounds of one per
-// unit -- deadlock-free as ever by the order of the ids, slower than two per unit.  The granules need no such thing; they get it where it is
-// free, on a grid that fits the device (M3500: 216 slots), so that a spinning workgroup does not sit beside a working one.
-static size_t handover_lds(int xmode, size_t lds, int grid) {
-    if (xmode == X_WT || (xmode == X_TAGGED && grid <= device_cus())) return std::max(lds, HANDOVER_LDS_MIN);
-    return lds;
-}
-static DevPlan launch_plan(const Context &c, DevPlan d, int max_upd_rows) { d.xmode = launch_xmode(c, max_upd_rows); return d; }
-static DevPlan persist_plan(const Context &c) { DevPlan d = c.dp; d.flevel = c.d_flevel.p; d.l0 = c.persist_l0; d.xmode = launch_xmode(c, c.p_dn_maxnu); return d; }
 static void rewind_epoch(Context &c, hipStream_t s, long long phases) {
     c.epoch_steps += phases;
     if (c.epoch_steps < (1ll << 30) || !c.d_epoch.p) return;
@@ -797,224 +725,6 @@ static void rewind_epoch(Context &c, hipStream_t s, long long phases) {
     if (c.d_xg.p) { HIPCHECK(hipMemsetAsync(c.d_xg.p, 0, c.d_xg.cap * sizeof(uint4), s)); set_const_granules(c, s); }      // (tags are step numbers too)
     HIPCHECK(hipMemcpyAsync(c.d_epoch.p, &FIRST_EPOCH, 4, hipMemcpyHostToDevice, s));
     c.epoch_steps = phases;
-}
-// debug option pool_poison (kernels.hip.h k_poison): NaN into everything the step's launches hand from one workgroup to another
-static void enqueue_poison(Context &c, hipStream_t s, const int *list, int n, int what = 3, const UpdRec *recs = nullptr) {
-    if (g_opt.pool_poison <= 0 || n <= 0) return;
-    static_assert(offsetof(UpdRec, mode) % 4 == 0 && sizeof(UpdRec) % 4 == 0, "UpdRec::mode as a strided int");
-    hipLaunchKernelGGL(k_poison, dim3(n), dim3(TPB), 0, s, c.dp, list, n, recs ? (const int *)((const char *)recs + offsetof(UpdRec, mode)) : (const int *)nullptr,
-                       (int)(sizeof(UpdRec) / 4), what, c.d_pool.p, c.d_x.p);
-}
-static void launch_front_persist(Context &c, hipStream_t s) {
-    const bool xp = c.x_up_n > 0;                          // the XCD-placed list (empty slots included)
-    const int *list = c.d_tab.p + (xp ? c.x_up_off : c.p_up_off), n = xp ? c.x_up_n : c.p_up_n;
-    int *fl = c.d_flags.p;
-    DevPlan dpe = persist_plan(c);
-    if (g_opt.skip_flag_waits > 0) dpe.l0 = 1 << 30;       // debug (negative control of pool_poison): no front of this launch waits for its children
-    if (c.p_nt >= 1024) hipLaunchKernelGGL(k_front_small<1024>, dim3(n), dim3(1024), c.p_up_lds, s, dpe, list, c.d_pool.p, c.d_H.p, c.d_bad.p, c.p_up_full, fl, 1);
-    else if (c.p_nt >= 512) hipLaunchKernelGGL(k_front_small<512>, dim3(n), dim3(512), c.p_up_lds, s, dpe, list, c.d_pool.p, c.d_H.p, c.d_bad.p, c.p_up_full, fl, 1);
-    else hipLaunchKernelGGL(k_front_small<256>, dim3(n), dim3(256), c.p_up_lds, s, dpe, list, c.d_pool.p, c.d_H.p, c.d_bad.p, c.p_up_full, fl, 1);
-}
-
-// (list_off >= 0: the list_n entries there instead of the level's own list -- an XCD-placed list)
-static void launch_front_small(Context &c, const LevelPlan &L, hipStream_t s, const int *tab = nullptr, int list_off = -1, int list_n = 0) {
-    if (!tab) tab = c.d_tab.p;
-    const int nt = L.small_nt, off = list_off >= 0 ? list_off : L.small_off, n = list_off >= 0 ? list_n : L.n_small;
-    if (nt >= 1024) hipLaunchKernelGGL(k_front_small<1024>, dim3(n), dim3(1024), L.small_lds, s, c.dp, tab + off, c.d_pool.p, c.d_H.p, c.d_bad.p, L.full_limit, (int *)nullptr, 0);
-    else if (nt >= 512) hipLaunchKernelGGL(k_front_small<512>, dim3(n), dim3(512), L.small_lds, s, c.dp, tab + off, c.d_pool.p, c.d_H.p, c.d_bad.p, L.full_limit, (int *)nullptr, 0);
-    else hipLaunchKernelGGL(k_front_small<256>, dim3(n), dim3(256), L.small_lds, s, c.dp, tab + off, c.d_pool.p, c.d_H.p, c.d_bad.p, L.full_limit, (int *)nullptr, 0);
-}
-
-// The big fronts of one level, 128 columns (an outer block of OBP panels) at a time: diagonal block in LDS with the inverses of its four
-// 32 x 32 diagonal blocks as a by-product (k_block_chain), row solves on the matrix cores (k_block_solve), then ONE wide update of
-// everything to the right with K = the block's columns (k_syrk_big / k_syrk_big32).
-template <class Tic, class Toc>
-static void enqueue_big_steps(Context &c, const LevelPlan &L, hipStream_t s, Tic tic, Toc toc, const int *tab = nullptr) {
-    if (!tab) tab = c.d_tab.p;
-    const int xcd = std::max(0, g_opt.syrk_xcd_order) << SYRK_MODE_XCD_SHIFT;
-    for (size_t o = 0; o < L.bchain.size(); o++) {
-        const Launch &bc = L.bchain[o], &bt = L.btile[o], &sw = L.syrkw[o];
-        tic(K_PANEL_BIG);
-        hipLaunchKernelGGL(k_block_chain, dim3(bc.n), dim3(BCH_THREADS), block_chain_lds(), s, c.dp, tab + bc.list_off, (int)o, c.d_pool.p, c.d_diag.p, c.d_dinv.p, c.d_bad.p);
-        if (bt.grid > 0) {
-            if (bt.tile == 2) hipLaunchKernelGGL(k_block_solve<2>, dim3(bt.grid), dim3(TPB), block_solve_lds(), s, c.dp, tab + bt.list_off, tab + bt.pre_off, bt.n, (int)o, c.d_pool.p, c.d_diag.p, c.d_dinv.p);
-            else hipLaunchKernelGGL(k_block_solve<1>, dim3(bt.grid), dim3(TPB), block_solve_lds(), s, c.dp, tab + bt.list_off, tab + bt.pre_off, bt.n, (int)o, c.d_pool.p, c.d_diag.p, c.d_dinv.p);
-        }
-        toc();
-        auto wide = [&](const Launch &w, int s_lo, int s_hi, int mode) {
-            if (w.grid <= 0) return;
-            tic(K_SYRK_BIG);
-            // (s_lo, s_hi) in panel steps: the kernel clips s_hi * NB to the front's own columns
-            if (w.tile == TILE / 2) hipLaunchKernelGGL(k_syrk_big32, dim3(w.grid), dim3(TPB), 0, s, c.dp, tab + w.list_off, tab + w.pre_off, w.n, s_lo, s_hi, mode | xcd, c.d_pool.p);
-            else hipLaunchKernelGGL(k_syrk_big, dim3(w.grid), dim3(TPB), 0, s, c.dp, tab + w.list_off, tab + w.pre_off, w.n, s_lo, s_hi, mode | xcd, c.d_pool.p);
-            toc();
-        };
-        const int G = std::max(2, g_opt.syrk_group), g0 = (int)(o - o % G) * OBP;
-        if (!L.paired) wide(sw, (int)o * OBP, (int)(o + 1) * OBP, 1);
-        else if ((int)(o % G) != G - 1) { wide(L.syrka[o], g0, (int)(o + 1) * OBP, 2); wide(L.syrk1[o], g0, (int)(o + 1) * OBP, 1); }
-        else wide(sw, g0, (int)(o + 1) * OBP, 1);
-    }
-}
-
-// kernels of one level of the factorisation (small LDS fronts, big multi-workgroup path)
-template <class Tic, class Toc>
-static void enqueue_factor_level(Context &c, const LevelPlan &L, hipStream_t s, Tic tic, Toc toc, const int *tab = nullptr) {
-    if (!tab) tab = c.d_tab.p;
-    if (L.n_small) {
-        tic(K_FRONT_SMALL);
-        launch_front_small(c, L, s, tab);
-        toc();
-    }
-    if (L.n_big) {
-        tic(K_ASSEMBLE_BIG);
-        hipLaunchKernelGGL(k_assemble_big, dim3(L.asm_big.grid), dim3(TPB), L.asm_lds, s, c.dp, tab + L.asm_big.list_off,
-                           tab + L.asm_big.pre_off, L.asm_big.n, c.d_pool.p, c.d_H.p);
-        toc();
-        enqueue_big_steps(c, L, s, tic, toc, tab);
-    }
-}
-
-// what fills the contribution slots of a Gauss-Newton step: selection, robust weights, linearisation (+ the host-evaluated factors' blocks)
-static void enqueue_linearise(Context &c, GraphPack &gp, hipStream_t s, bool unary_at_lp) {
-    const int F = c.plan.F;
-    enqueue_select(gp, s);                           // max-mixture factors: the component selected at l_point goes into the factor's slot
-    enqueue_robust(gp, s, unary_at_lp ? gp.d_upt.p : (const double *)nullptr);      // robust factors: W_eff = w(s) W0 into the factor's slot
-    {   // (a variant of the kernel without the asymmetric-W orientation branch, for graphs that have no such factor, was measured in round 6: no
-        // difference -- 0.79 ms on the 1 M lattice either way)
-        auto launch = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3((F + TPB - 1) / TPB), dim3(TPB), 0, s, 0, F, (const int *)nullptr, gp.d_fa.p, gp.d_fb.p, gp.d_z.p, gp.d_W.p,
-                               gp.d_lp.p, gp.d_state.p, c.d_swap.p, c.dp.slot_blk, c.dp.slot_rhs, c.d_H.p, c.d_bad.p, unary_at_lp ? gp.d_upt.p : (const double *)nullptr, c.d_epoch.p);
-        };
-        if (F >= g_opt.linearize_staged_min) launch(k_linearize_t<true>); else launch(k_linearize_t<false>);
-    }
-    if (!gp.host_idx.empty()) {         // host-evaluated factors: their blocks replace the null contributions written above
-        const int nh = (int)gp.host_idx.size();
-        HIPCHECK(hipMemcpyAsync(gp.d_hostH.p, gp.h_hostH.p, (size_t)33 * 8 * nh, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_scatter_host, dim3((nh + TPB - 1) / TPB), dim3(TPB), 0, s, nh, gp.d_host_idx.p, gp.d_hostH.p, gp.d_fb.p, c.d_swap.p,
-                           c.dp.slot_blk, c.dp.slot_rhs, c.d_H.p);
-    }
-}
-
-// enqueue: linearise -> per level {assemble+factor} -> back substitution -> state update
-// ev != null: record stage events (0 start, 1 after linearise, 2 after factor, 3 after solve+update)
-// ktime: bracket EVERY kernel launch with its own HIP event pair on this stream (c.k_ev / c.k_ids)
-// st_dest (LM iterations, solver_lm.inc.h): where the state update writes x (+) h instead of d_state -- the trial buffer
-// fill (chordal initialisation, solver_chordal.inc.h): what writes the contribution slots, clears the failure record and advances the step
-// counter in place of the selection, the weights and the linearisation
-static void enqueue_numeric(Context &c, GraphPack &gp, hipStream_t s, hipEvent_t *ev, bool unary_at_lp = false, bool ktime = false, bool io_host = false, bool relin = false,
-                            double *st_dest = nullptr, const std::function<void()> *fill = nullptr) {
-    const Plan &P = c.plan;
-    const int N = P.N;
-    size_t nev = 0;
-    if (ktime) { c.k_ids.clear(); c.k_lev.clear(); }
-    int cur_level = -1;                              // (profile: the level the launches that follow belong to; multi-level launches: their first level)
-    auto tic = [&](int id) {
-        if (!ktime) return;
-        if (c.k_ev.size() < nev + 2) { c.k_ev.resize(nev + 2); HIPCHECK(hipEventCreate(&c.k_ev[nev])); HIPCHECK(hipEventCreate(&c.k_ev[nev + 1])); }
-        HIPCHECK(hipEventRecord(c.k_ev[nev], s));
-        c.k_ids.push_back(id); c.k_lev.push_back(cur_level);
-    };
-    auto toc = [&]() { if (ktime) { HIPCHECK(hipEventRecord(c.k_ev[nev + 1], s)); nev += 2; } };
-    if (ev) HIPCHECK(hipEventRecord(ev[0], s));
-    if (c.dp.prof) HIPCHECK(hipMemsetAsync(c.d_prof.p, 0, (size_t)8 * PROF_SLOTS * P.nF, s));
-    if (io_host) hipLaunchKernelGGL(k_load_states, dim3((3 * N + TPB - 1) / TPB), dim3(TPB), 0, s, 3 * N, gp.h_state.p, gp.d_state.p, gp.d_lp.p);
-    enqueue_poison(c, s, nullptr, P.nF);
-    tic(K_LINEARIZE);
-    if (fill) (*fill)(); else enqueue_linearise(c, gp, s, unary_at_lp);
-    toc();
-    if (ev) HIPCHECK(hipEventRecord(ev[1], s));
-    const int l0 = c.persist_l0 >= 0 ? c.persist_l0 : P.nLevels;        // levels >= l0: one multi-level launch each way
-    for (int l = 0; l < l0; l++) {
-        cur_level = l;
-        if (l == 0 && c.x_leaf_n > 0) { tic(K_FRONT_SMALL); launch_front_small(c, c.levels[0], s, nullptr, c.x_leaf_off, c.x_leaf_n); toc(); }      // (small fronts only)
-        else enqueue_factor_level(c, c.levels[l], s, tic, toc);
-    }
-    cur_level = l0;
-    if (l0 < P.nLevels) { tic(K_FRONT_SMALL); launch_front_persist(c, s); toc(); }
-    if (ev) HIPCHECK(hipEventRecord(ev[2], s));
-    // the state update of a front's own poses rides on its back substitution (no kernel of its own); the last launch also
-    // mirrors the pivot flag for the API call
-    UpdArgs upd{ c.d_perm.p, gp.d_lp.p, st_dest ? st_dest : gp.d_state.p, gp.d_dx.p, io_host ? gp.h_lp.p : nullptr, io_host ? gp.h_dx.p : nullptr, nullptr, relin ? gp.d_lp.p : nullptr };
-    if (l0 < P.nLevels) {
-        UpdArgs u = upd; if (l0 == 0) u.bad_out = io_host ? c.h_bad.p : nullptr;
-        tic(K_BACKSOLVE);
-        const bool xp = c.x_dn_n > 0;                            // the XCD-placed list (empty slots included)
-        const int *dn = c.d_tab.p + (xp ? c.x_dn_off : c.p_dn_off), n_dn = xp ? c.x_dn_n : c.p_dn_n;
-        if (g_opt.wave_backsolve && c.p_dn_maxns <= BSW_MAX_NS)
-            hipLaunchKernelGGL(k_backsolve_w, dim3(n_dn), dim3(TPB), handover_lds(launch_xmode(c, c.p_dn_maxnu), c.p_dn_lds, n_dn), s, persist_plan(c), dn, c.d_pool.p, c.d_x.p, c.d_flags.p + c.flag_stride, c.d_bad.p, u);
-        else
-            hipLaunchKernelGGL((k_backsolve_t<true>), dim3(n_dn), dim3(TPB), handover_lds(launch_xmode(c, c.p_dn_maxnu), c.p_dn_lds, n_dn), s, persist_plan(c), dn, c.d_pool.p, c.d_x.p, 0, c.d_flags.p + c.flag_stride, 1, c.d_bad.p, u);
-        toc();
-    }
-    for (int l = l0 - 1; l >= 0; l--) {
-        UpdArgs u = upd; if (l == 0) u.bad_out = io_host ? c.h_bad.p : nullptr;
-        cur_level = l;
-        if (l == 0 && c.x_leaf_n > 0) launch_backsolve(c, c.levels[0], s, tic, toc, nullptr, u, c.x_leaf_off, c.x_leaf_n);
-        else launch_backsolve(c, c.levels[l], s, tic, toc, nullptr, u);
-    }
-    if (ev) HIPCHECK(hipEventRecord(ev[3], s));
-    HIPCHECK(hipGetLastError());
-}
-// after the stream was synchronised: fold the event pairs of the last instrumented enqueue into c.k_ms
-static void collect_kernel_times(Context &c) {
-    for (size_t i = 0; i < c.k_ids.size(); i++) {
-        float ms = 0;
-        HIPCHECK(hipEventElapsedTime(&ms, c.k_ev[2 * i], c.k_ev[2 * i + 1]));
-        c.k_ms[c.k_ids[i]] += ms; c.k_calls[c.k_ids[i]]++;
-        const int l = i < c.k_lev.size() ? c.k_lev[i] : -1;
-        if (l >= 0) {
-            if (c.lev_up_ms.size() <= (size_t)l) { c.lev_up_ms.resize(l + 1, 0.0); c.lev_dn_ms.resize(l + 1, 0.0); }
-            (c.k_ids[i] == K_BACKSOLVE ? c.lev_dn_ms : c.lev_up_ms)[l] += ms;
-        }
-    }
-    c.k_ids.clear();
-}
-
-// run the numeric phase, replaying a captured hipGraph when enabled
-static void run_numeric(Context &c, GraphPack &gp, bool timing, bool unary_at_lp = false, bool io_host = false, bool relin = false) {
-    hipStream_t s = gp.stream;
-    set_small_attr();
-    rewind_epoch(c, s, 1);
-    if (timing && !c.have_events) { for (auto &e : c.ev) HIPCHECK(hipEventCreate(&e)); c.have_events = true; }
-    if (io_host) {
-        if (g_opt.use_graph && !timing && gp.host_idx.empty()) {
-            const void *key[9] = { gp.d_state.p, gp.h_state.p, gp.h_lp.p, gp.h_dx.p, c.h_bad.p, (const void *)(size_t)gp.N, (const void *)(size_t)gp.serial, (const void *)(size_t)gp.mx_gen,
-                                   (const void *)(size_t)gp.rb_gen };
-            // A graph is worth its capture, instantiation and destruction (0.3 ms together) only if the configuration comes back:
-            // the first call with a new key -- every fall-back of an incremental run, every cold call -- enqueues its kernels directly.
-            if (memcmp(key, c.api_key, sizeof(key)) != 0) { c.retire(c.gexec_api); memcpy(c.api_key, key, sizeof(key)); c.api_key_runs = 0; }
-            if (c.api_key_runs++ == 0) { enqueue_numeric(c, gp, s, nullptr, false, false, true); return; }
-            if (!c.gexec_api) {
-                hipGraph_t graph = nullptr;
-                HIPCHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-                enqueue_numeric(c, gp, s, nullptr, false, false, true);
-                HIPCHECK(hipStreamEndCapture(s, &graph));
-                HIPCHECK(hipGraphInstantiate(&c.gexec_api, graph, nullptr, nullptr, 0));
-                HIPCHECK(hipGraphDestroy(graph));
-            }
-            c.graph_stream = s;
-            HIPCHECK(hipGraphLaunch(c.gexec_api, s));
-        } else {
-            enqueue_numeric(c, gp, s, timing ? c.ev : nullptr, false, false, true);
-        }
-        return;
-    }
-    if (g_opt.use_graph && !timing && !unary_at_lp && gp.host_idx.empty()) {   // (host-evaluated factors: staging buffers may move)
-        if (!c.gexec || c.gexec_key != (const void *)gp.d_state.p || c.gexec_serial != gp.serial || c.gexec_mx != gp.mx_gen || c.gexec_rb != gp.rb_gen) {
-            c.retire(c.gexec);
-            hipGraph_t graph = nullptr;
-            HIPCHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-            enqueue_numeric(c, gp, s, nullptr, false, false, false, relin);
-            HIPCHECK(hipStreamEndCapture(s, &graph));
-            HIPCHECK(hipGraphInstantiate(&c.gexec, graph, nullptr, nullptr, 0));
-            HIPCHECK(hipGraphDestroy(graph));
-            c.gexec_key = (const void *)gp.d_state.p; c.gexec_serial = gp.serial; c.gexec_mx = gp.mx_gen; c.gexec_rb = gp.rb_gen;
-        }
-        c.graph_stream = s;
-        HIPCHECK(hipGraphLaunch(c.gexec, s));
-    } else {
-        enqueue_numeric(c, gp, s, timing ? c.ev : nullptr, unary_at_lp, false, false, relin);
-    }
 }
 
 static double device_chi2(GraphPack &gp) {     // chi^2 at d_state; synchronises the stream

@@ -184,9 +184,7 @@ static bool inc_fast_step(Context &c, GraphPack &gp, int N, int F, int Fold, int
             rewind_epoch(c, s, 1);
             const int *dn = c.d_tab.p + I.tab_used; const int n_dn = solve_here ? 0 : (int)lst.size();
             const int one_nt = g_opt.inc_one_threads >= 1024 ? 1024 : g_opt.inc_one_threads >= 512 ? 512 : 256;
-            if (one_nt >= 1024) hipLaunchKernelGGL(k_inc_one<1024>, dim3(1), dim3(1024), lds, s, pro, nofl, c.inl, c.dp, tstep, (const int *)nullptr, 0, dn, n_dn, c.d_pool.p, 0ll, c.d_x.p, upd1);
-            else if (one_nt >= 512) hipLaunchKernelGGL(k_inc_one<512>, dim3(1), dim3(512), lds, s, pro, nofl, c.inl, c.dp, tstep, (const int *)nullptr, 0, dn, n_dn, c.d_pool.p, 0ll, c.d_x.p, upd1);
-            else hipLaunchKernelGGL(k_inc_one<256>, dim3(1), dim3(256), lds, s, pro, nofl, c.inl, c.dp, tstep, (const int *)nullptr, 0, dn, n_dn, c.d_pool.p, 0ll, c.d_x.p, upd1);
+            launch_inc_one_nt(one_nt, lds, s, pro, nofl, c.inl, c.dp, tstep, (const int *)nullptr, 0, dn, n_dn, c.d_pool.p, 0ll, c.d_x.p, upd1);
             gp.mirror_sync = true;
             gp.new_states = gp.h_out.p;
             HIPCHECK(hipGetLastError());
@@ -730,6 +728,7 @@ static bool inc_fast_step(Context &c, GraphPack &gp, int N, int F, int Fold, int
         hipLaunchKernelGGL(k_load_states, dim3((3 * N + TPB - 1) / TPB), dim3(TPB), 0, s, 3 * N, gp.h_state.p, gp.d_state.p, gp.d_lp.p);      // l_point <- state
         enqueue_select(gp, s);
         enqueue_robust(gp, s, nullptr);
+        // (not enqueue_linearise: that picks the staged form of the kernel by size, this branch always runs the plain one)
         hipLaunchKernelGGL((k_linearize_t<false>), dim3((F + TPB - 1) / TPB), dim3(TPB), 0, s, 0, F, (const int *)nullptr, gp.d_fa.p, gp.d_fb.p, gp.d_z.p, gp.d_W.p,
                            gp.d_lp.p, gp.d_state.p, c.d_swap.p, c.dp.slot_blk, c.dp.slot_rhs, c.d_H.p, c.d_bad.p, (const double *)nullptr, c.d_epoch.p);
     } else {
@@ -754,8 +753,7 @@ static bool inc_fast_step(Context &c, GraphPack &gp, int N, int F, int Fold, int
         c.one_wait = 0;
         const IncFlags fl = (!one && iu) ? IncFlags{ c.d_epoch.p, c.d_marks.p, c.d_tab.p + iu_off, iu_n } : IncFlags{ c.d_epoch.p, nullptr, nullptr, 0 };
         if (tail_fast && !one) {                       // the refactorisation in the prologue's launch, the back substitution in launches of its own
-            hipLaunchKernelGGL(k_inc_one<1024>, dim3(1), dim3(1024), tail_refactor_lds(), s, pro, fl, c.inl, c.dp, tstep, (const int *)nullptr, 0, (const int *)nullptr, 0,
-                               c.d_pool.p, iu_full, c.d_x.p, UpdArgs{});
+            launch_inc_one_nt(1024, tail_refactor_lds(), s, pro, fl, c.inl, c.dp, tstep, (const int *)nullptr, 0, (const int *)nullptr, 0, c.d_pool.p, iu_full, c.d_x.p, UpdArgs{});
         } else if (one) {
             if (g_incprof_stamps) { c.h_kstamp.need(8 + PROF_SLOTS); memset(c.h_kstamp.p, 0, 8 * (8 + PROF_SLOTS)); pro.stamps = c.h_kstamp.p; }
             if (g_opt.inc_one_spin) {                  // completion through a word in pinned memory: the host spins instead of sleeping in hipStreamSynchronize
@@ -765,9 +763,7 @@ static bool inc_fast_step(Context &c, GraphPack &gp, int N, int F, int Fold, int
             }
             gp.h_out.need((size_t)3 * N);
             const UpdArgs upd1{ c.d_perm.p, gp.d_lp.p, nullptr, gp.d_dx.p, gp.h_out.p, gp.h_dx.p, c.h_bad.p };
-            if (one_nt >= 1024) hipLaunchKernelGGL(k_inc_one<1024>, dim3(1), dim3(1024), one_lds, s, pro, fl, c.inl, c.dp, tstep, c.d_tab.p + iu_off, iu_n, c.d_tab.p + id_off, id_n, c.d_pool.p, iu_full, c.d_x.p, upd1, uctx);
-            else if (one_nt >= 512) hipLaunchKernelGGL(k_inc_one<512>, dim3(1), dim3(512), one_lds, s, pro, fl, c.inl, c.dp, tstep, c.d_tab.p + iu_off, iu_n, c.d_tab.p + id_off, id_n, c.d_pool.p, iu_full, c.d_x.p, upd1, uctx);
-            else hipLaunchKernelGGL(k_inc_one<256>, dim3(1), dim3(256), one_lds, s, pro, fl, c.inl, c.dp, tstep, c.d_tab.p + iu_off, iu_n, c.d_tab.p + id_off, id_n, c.d_pool.p, iu_full, c.d_x.p, upd1, uctx);
+            launch_inc_one_nt(one_nt, one_lds, s, pro, fl, c.inl, c.dp, tstep, c.d_tab.p + iu_off, iu_n, c.d_tab.p + id_off, id_n, c.d_pool.p, iu_full, c.d_x.p, upd1, uctx);
         } else
             hipLaunchKernelGGL(k_inc_prologue, dim3(1), dim3(1024), 0, s, pro, fl, c.inl);
     }
@@ -775,32 +771,17 @@ static bool inc_fast_step(Context &c, GraphPack &gp, int N, int F, int Fold, int
         if (iu) { enqueue_poison(c, s, c.d_tab.p + iu_off, iu_n, 1, any_upd ? c.d_upd.p : nullptr); if (any_upd) HIPCHECK(hipMemsetAsync(c.d_wbuf.p, 0xff, c.d_wbuf.cap * 8, s)); }
         if (id) enqueue_poison(c, s, c.d_tab.p + id_off, id_n, 2);
     }
-    if (iu && !one) {
-        const int *list = c.d_tab.p + iu_off;
-        if (iu_nt >= 1024) hipLaunchKernelGGL(k_front_small<1024>, dim3(iu_n), dim3(1024), iu_lds, s, dpi, list, c.d_pool.p, c.d_H.p, c.d_bad.p, iu_full, c.d_flags.p, 1, uctx);
-        else if (iu_nt >= 512) hipLaunchKernelGGL(k_front_small<512>, dim3(iu_n), dim3(512), iu_lds, s, dpi, list, c.d_pool.p, c.d_H.p, c.d_bad.p, iu_full, c.d_flags.p, 1, uctx);
-        else hipLaunchKernelGGL(k_front_small<256>, dim3(iu_n), dim3(256), iu_lds, s, dpi, list, c.d_pool.p, c.d_H.p, c.d_bad.p, iu_full, c.d_flags.p, 1, uctx);
-    }
+    if (iu && !one) launch_front_small_nt(iu_nt, iu_n, iu_lds, s, dpi, c.d_tab.p + iu_off, c.d_pool.p, c.d_H.p, c.d_bad.p, iu_full, c.d_flags.p, 1, uctx);
     for (int l = 0; l < nLev; l++) {
         if (lev_dirty[l].empty() || iu || one) continue;
         if (mp && l >= 1) {
             if (l > 1) continue;
-            const int *list = c.d_tab.p + mp_up_off;
-            if (mp_nt >= 1024) hipLaunchKernelGGL(k_front_small<1024>, dim3(mp_n), dim3(1024), mp_up_lds, s, dpm, list, c.d_pool.p, c.d_H.p, c.d_bad.p, mp_full, c.d_flags.p, 1);
-            else if (mp_nt >= 512) hipLaunchKernelGGL(k_front_small<512>, dim3(mp_n), dim3(512), mp_up_lds, s, dpm, list, c.d_pool.p, c.d_H.p, c.d_bad.p, mp_full, c.d_flags.p, 1);
-            else hipLaunchKernelGGL(k_front_small<256>, dim3(mp_n), dim3(256), mp_up_lds, s, dpm, list, c.d_pool.p, c.d_H.p, c.d_bad.p, mp_full, c.d_flags.p, 1);
+            launch_front_small_nt(mp_nt, mp_n, mp_up_lds, s, dpm, c.d_tab.p + mp_up_off, c.d_pool.p, c.d_H.p, c.d_bad.p, mp_full, c.d_flags.p, 1);
             continue;
         }
-        const LevelPlan &L = dl[l];
-        if (L.n_small) launch_front_small(c, L, s);
-        if (L.n_big) {
-            hipLaunchKernelGGL(k_assemble_big, dim3(L.asm_big.grid), dim3(TPB), L.asm_lds, s, c.dp, c.d_tab.p + L.asm_big.list_off,
-                               c.d_tab.p + L.asm_big.pre_off, L.asm_big.n, c.d_pool.p, c.d_H.p);
-            enqueue_big_steps(c, L, s, [](int) {}, []() {});
-        }
+        enqueue_factor_level(c, dl[l], s, no_timer);
     }
-    if (mp && g_opt.wave_backsolve && mp_dn_maxns <= BSW_MAX_NS) hipLaunchKernelGGL(k_backsolve_w, dim3(mp_n), dim3(TPB), handover_lds(dpx.xmode, mp_dn_lds, mp_n), s, dpx, c.d_tab.p + mp_dn_off, c.d_pool.p, c.d_x.p, xfl, c.d_bad.p, UpdArgs{});
-    else if (mp) hipLaunchKernelGGL((k_backsolve_t<true>), dim3(mp_n), dim3(TPB), handover_lds(dpx.xmode, mp_dn_lds, mp_n), s, dpx, c.d_tab.p + mp_dn_off, c.d_pool.p, c.d_x.p, 0, xfl, 1, c.d_bad.p, UpdArgs{});
+    if (mp) launch_backsolve_multi(c, s, dpx, c.d_tab.p + mp_dn_off, mp_n, mp_dn_lds, mp_dn_maxns, xfl, UpdArgs{});
     // incremental steps: the state update (state = l_point + dx, pinned mirrors of state / dx / failure record) rides on the
     // back substitution of the front that owns the pose -- every visited pose lives in a front of this sweep -- instead of
     // a launch of its own over all poses
@@ -810,25 +791,22 @@ static bool inc_fast_step(Context &c, GraphPack &gp, int N, int F, int Fold, int
     const UpdArgs upd = batch ? UpdArgs{} : UpdArgs{ c.d_perm.p, gp.d_lp.p, nullptr, gp.d_dx.p, gp.h_out.p, gp.h_dx.p, c.h_bad.p };
     bool rode = one;
     if (id && !one) {
-        if (g_opt.wave_backsolve && id_maxns <= BSW_MAX_NS) hipLaunchKernelGGL(k_backsolve_w, dim3(id_n), dim3(TPB), handover_lds(dpx.xmode, id_lds, id_n), s, dpx, c.d_tab.p + id_off, c.d_pool.p, c.d_x.p, xfl, c.d_bad.p, upd);
-        else hipLaunchKernelGGL((k_backsolve_t<true>), dim3(id_n), dim3(TPB), handover_lds(dpx.xmode, id_lds, id_n), s, dpx, c.d_tab.p + id_off, c.d_pool.p, c.d_x.p, 0, xfl, 1, c.d_bad.p, upd);
+        launch_backsolve_multi(c, s, dpx, c.d_tab.p + id_off, id_n, id_lds, id_maxns, xfl, upd);
         rode = true;
     }
     for (int l = (one ? -1 : id ? (needed ? -1 : id_rest) : nLev - 1); l >= 0; l--) {
         if (mp && l >= 1) continue;
-        if (batch) { launch_backsolve(c, dl[l], s, [](int) {}, []() {}); continue; }
+        if (batch) { launch_backsolve(c, dl[l], s, no_timer); continue; }
         if (l >= I.nLev0 || needed) {
             if (bs_n[l] > 0) {
                 const size_t lds = l >= I.nLev0 ? solve_lds_of(nF0 + l - I.nLev0) : I.base_levels[l].solve_lds;
-                if (g_opt.wave_backsolve && bs_maxns[l] <= BSW_MAX_NS && bs_wlds[l] <= 160 * 1024)      // a few fronts per level: latency is all that counts
-                    hipLaunchKernelGGL(k_backsolve_w, dim3((unsigned)bs_n[l]), dim3(TPB), bs_wlds[l], s, c.dp, c.d_tab.p + bs_off[l], c.d_pool.p, c.d_x.p, (int *)nullptr, c.d_bad.p, upd);
-                else
-                    hipLaunchKernelGGL((k_backsolve_t<false>), dim3((unsigned)bs_n[l]), dim3(TPB), lds, s, c.dp, c.d_tab.p + bs_off[l], c.d_pool.p, c.d_x.p, 0, (int *)nullptr, 0, c.d_bad.p, upd);
+                const bool wave = g_opt.wave_backsolve && bs_maxns[l] <= BSW_MAX_NS && bs_wlds[l] <= 160 * 1024;      // a few fronts per level: latency is all that counts
+                launch_backsolve_list(c, s, wave ? BS_WAVE : BS_THREAD, c.d_tab.p + bs_off[l], bs_n[l], wave ? bs_wlds[l] : lds, 0, c.d_bad.p, upd);
                 rode = true;
             }
         } else {                                     // every pose is visited: all base fronts, level by level
             const LevelPlan &L = I.base_levels[l];
-            hipLaunchKernelGGL((k_backsolve_t<false>), dim3(L.n_all), dim3(TPB), L.solve_lds, s, c.dp, c.d_tab.p + L.all_off, c.d_pool.p, c.d_x.p, 0, (int *)nullptr, 0, c.d_bad.p, upd);
+            launch_backsolve_list(c, s, BS_THREAD, c.d_tab.p + L.all_off, L.n_all, L.solve_lds, 0, c.d_bad.p, upd);
             rode = true;
         }
     }

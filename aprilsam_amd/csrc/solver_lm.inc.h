@@ -53,7 +53,8 @@ static void lm_enqueue_iteration(Context &c, GraphPack &gp, hipStream_t s) {
     const int N = gp.N, F = gp.F, T = std::max(F, 2 * N);
     LmScalars *S = c.d_lm.p;
     double *terms = c.d_lm_terms.p, *parts = terms + T;
-    enqueue_numeric(c, gp, s, nullptr, false, false, false, false, c.d_lm_trial.p);      // select, linearise, factor, solve: x_t -> trial
+    NumericArgs trial; trial.st_dest = c.d_lm_trial.p;
+    enqueue_numeric(c, gp, s, trial);      // select, linearise, factor, solve: x_t -> trial
     lm_enqueue_cost(c, gp, s, c.d_lm_trial.p, &S->Ft);
     hipLaunchKernelGGL(k_lm_model, dim3((F + TPB - 1) / TPB), dim3(TPB), 0, s, F, gp.d_fa.p, gp.d_fb.p, gp.d_z.p, gp.d_W.p, (const double *)gp.d_lp.p,
                        (const double *)gp.d_dx.p, terms);
@@ -70,18 +71,8 @@ static void lm_run_iteration(Context &c, GraphPack &gp, hipStream_t s) {
     if (!g_opt.use_graph) { lm_enqueue_iteration(c, gp, s); return; }
     const void *key[9] = { gp.d_state.p, (const void *)(size_t)gp.serial, (const void *)(size_t)gp.mx_gen, (const void *)(size_t)gp.N,
                            c.d_lm_trial.p, c.d_lm_terms.p, c.d_lm_trace.p, c.d_lm.p, (const void *)(size_t)gp.rb_gen };
-    if (!c.gexec_lm || memcmp(key, c.lm_key, sizeof(key)) != 0) {
-        c.retire(c.gexec_lm);
-        hipGraph_t graph = nullptr;
-        HIPCHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        lm_enqueue_iteration(c, gp, s);
-        HIPCHECK(hipStreamEndCapture(s, &graph));
-        HIPCHECK(hipGraphInstantiate(&c.gexec_lm, graph, nullptr, nullptr, 0));
-        HIPCHECK(hipGraphDestroy(graph));
-        memcpy(c.lm_key, key, sizeof(key));
-    }
-    c.graph_stream = s;
-    HIPCHECK(hipGraphLaunch(c.gexec_lm, s));
+    if (memcmp(key, c.lm_key, sizeof(key)) != 0) { c.retire(c.gexec_lm); memcpy(c.lm_key, key, sizeof(key)); }
+    replay_captured(c, c.gexec_lm, s, [&] { lm_enqueue_iteration(c, gp, s); });
 }
 
 static int optimize_lm_impl(april_graph_t *g, april_graph_cholesky_param_t *param, const aprilsam_amd_lm_opts_t *o, aprilsam_amd_lm_report_t *report,

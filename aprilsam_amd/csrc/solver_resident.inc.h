@@ -55,11 +55,13 @@ static int resident_steps_impl(april_graph_t *g, april_graph_cholesky_param_t *p
             gp.lp_last_valid = true;
         }
         if (mode == 1) {
-            enqueue_numeric(c, gp, s, nullptr, false, true, false, true);
+            NumericArgs a; a.ktime = true; a.relin = true;
+            enqueue_numeric(c, gp, s, a);
             HIPCHECK(hipStreamSynchronize(s));
             collect_kernel_times(c);
         } else {
-            run_numeric(c, gp, false, false, false, true);
+            RunArgs r; r.relin = true;
+            run_numeric(c, gp, r);
         }
     }
     return 0;

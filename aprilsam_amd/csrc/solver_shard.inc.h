@@ -359,7 +359,6 @@ static int shard_iterate_impl(april_graph_t *g, april_graph_cholesky_param_t *pa
     
     set_small_attr();
     const int N = gp.N, me = S.rank;
-    auto nop = [](int) {}; auto nop0 = []() {};
     Transport *T = S.tr.get();
     gp.mirror_sync = false;
     HIPCHECK(hipMemsetAsync(c.d_bad.p, 0, 16, s));          // sticky over the n iterations: the first failure is the one reported
@@ -369,7 +368,7 @@ static int shard_iterate_impl(april_graph_t *g, april_graph_cholesky_param_t *pa
             hipLaunchKernelGGL((k_linearize_t<false>), dim3((S.n_flist + TPB - 1) / TPB), dim3(TPB), 0, s, 0, S.n_flist, (const int *)S.d_flist.p, gp.d_fa.p, gp.d_fb.p,
                                gp.d_z.p, gp.d_W.p, gp.d_lp.p, gp.d_state.p, c.d_swap.p, c.dp.slot_blk, c.dp.slot_rhs, c.d_H.p, (int *)nullptr, (const double *)nullptr);
         for (int l = 0; l < P.nLevels; l++) {
-            enqueue_factor_level(c, S.levels[l], s, nop, nop0, S.d_tab.p);
+            enqueue_factor_level(c, S.levels[l], s, no_timer, S.d_tab.p);
             if (S.up[l].empty() || !T) continue;
             bool any = false;
             for (const auto &x : S.up[l]) {
@@ -393,7 +392,7 @@ static int shard_iterate_impl(april_graph_t *g, april_graph_cholesky_param_t *pa
             }
         }
         for (int l = P.nLevels - 1; l >= 0; l--) {
-            launch_backsolve(c, S.levels[l], s, nop, nop0, S.d_tab.p);
+            launch_backsolve(c, S.levels[l], s, no_timer, S.d_tab.p);
             if (S.down[l].empty() || !T) continue;
             T->group_begin();
             for (const auto &b : S.down[l]) T->bcast(c.d_x.p + b[1], b[2], (int)b[0], s);

@@ -310,6 +310,8 @@ def test_incremental_demo_matches_reference_schedule(lib, inc_fast):
 @pytest.mark.parametrize("opts", [
     {"inc_tail": 0},                                  # every step regenerates its fronts (one launch for the small ones)
     {"inc_tail": 0, "inc_one": 0},                    # ... as prologue + multi-level fronts + multi-level back substitution
+    {"inc_tail": 0, "inc_one": 0, "small_threads": 256}, {"inc_tail": 0, "inc_one": 0, "small_threads": 512},   # ... with the other workgroup sizes of the fronts' launch
+    {"inc_one": 0, "wave_backsolve": 0},              # ... with the back substitutions in their 32-columns-at-a-time form
     {"inc_multi": 0},                                 # ... one launch per level and direction (implies no k_inc_one / tail_refactor)
     {"inc_inline": 0},                                # patches read across PCIe instead of from the kernel arguments
     {"inc_one_spin": 0},                              # completion through hipStreamSynchronize
