@@ -106,6 +106,25 @@ class LmReport(C.Structure):
 LM_CONVERGED_F, LM_CONVERGED_X, LM_STALLED, LM_MAX_ITERS = 1, 2, 3, 4
 
 
+class GncOpts(C.Structure):
+    """aprilsam_amd_gnc_opts_t (include/aprilsam_amd.h)"""
+    _fields_ = [("loss", C.c_int), ("c", C.c_double), ("mu_step", C.c_double), ("max_stages", C.c_int), ("lm", LmOpts)]
+
+
+class GncReport(C.Structure):
+    """aprilsam_amd_gnc_report_t"""
+    _fields_ = [("status", C.c_int), ("stages", C.c_int), ("iterations", C.c_int), ("accepted", C.c_int), ("stages_stalled", C.c_int),
+                ("n_inliers", C.c_int), ("mu_initial", C.c_double), ("mu_final", C.c_double), ("s_max", C.c_double),
+                ("F_final", C.c_double), ("chi2_final", C.c_double)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+GNC_GM, GNC_TLS = 1, 2
+GNC_FINISHED, GNC_MAX_STAGES = 1, 2
+
+
 class ChordalOpts(C.Structure):
     """aprilsam_amd_chordal_opts_t (include/aprilsam_amd.h)"""
     _fields_ = [("stages", C.c_int)]

@@ -308,6 +308,7 @@ double robust_host_s(const double *z, const double *w, const double *pa, const d
     return r[0] * X0 + r[1] * X1 + r[2] * X2;
 }
 
+bool plain_common_factor(const april_graph_factor_t *f) { return is_library_common(f) && f->u.common.W && f->u.common.z; }
 bool robust_of(const april_graph_factor_t *f, int *kind, double *c) {
     const RobustBlock *rb = own_robust(f);
     if (!rb) return false;

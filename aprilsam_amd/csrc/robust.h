@@ -36,6 +36,29 @@ inline ROBUST_HD double robust_rho(int kind, double c, double s) {
     default: return s;
     }
 }
+// Graduated non-convexity: the surrogate of Geman-McClure / truncated least squares at control parameter mu, never
+// a factor's own loss (set_robust refuses the kinds) -- aprilsam_amd_optimize_gnc applies it to its candidates for the length of the call.
+// mu = +inf (TLS, every candidate an inlier at the start) is the limit, TLS itself: lo = hi = c^2.  A NaN s fails every comparison and
+// goes through the sqrt: NaN weight, NaN rho.
+enum { GNC_GM = 1, GNC_TLS = 2 };
+inline ROBUST_HD double gnc_weight(int loss, double c, double mu, double s) {
+    const double cc = c * c;
+    if (loss == GNC_GM) { const double m = mu * cc, q = m / (m + s); return q * q; }
+    const bool lim = mu > 1.7976931348623157e308;
+    const double lo = lim ? cc : mu / (mu + 1.0) * cc, hi = lim ? cc : (mu + 1.0) / mu * cc;
+    if (s <= lo) return 1.0;
+    if (s >= hi) return 0.0;
+    return c * sqrt(mu * (mu + 1.0) / s) - mu;
+}
+inline ROBUST_HD double gnc_rho(int loss, double c, double mu, double s) {
+    const double cc = c * c;
+    if (loss == GNC_GM) { const double m = mu * cc; return m * s / (m + s); }
+    const bool lim = mu > 1.7976931348623157e308;
+    const double lo = lim ? cc : mu / (mu + 1.0) * cc, hi = lim ? cc : (mu + 1.0) / mu * cc;
+    if (s <= lo) return s;
+    if (s >= hi) return cc;
+    return 2.0 * c * sqrt(mu * (mu + 1.0) * s) - mu * (cc + s);
+}
 // the information matrix a robust factor may carry: bitwise symmetric, all three leading minors > 0
 inline bool robust_spd(const double *w) {
     if (w[1] != w[3] || w[2] != w[6] || w[5] != w[7]) return false;

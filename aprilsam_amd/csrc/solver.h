@@ -102,6 +102,10 @@ long long path_solve_bytes(const april_graph_cholesky_param_t *param);
 int max_selected(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *factors, int *out);   // solver_pack.inc.h
 void lm_opts_init(aprilsam_amd_lm_opts_t *opts);                                                                    // solver_lm.inc.h
 int optimize_lm(april_graph_t *g, april_graph_cholesky_param_t *param, const aprilsam_amd_lm_opts_t *opts, aprilsam_amd_lm_report_t *report, double *trace);
+void gnc_opts_init(aprilsam_amd_gnc_opts_t *opts);                                                                  // solver_gnc.inc.h
+int optimize_gnc(april_graph_t *g, april_graph_cholesky_param_t *param, const aprilsam_amd_gnc_opts_t *opts, int n, const int *candidates,
+                 aprilsam_amd_gnc_report_t *report, double *weights, double *stage_trace);
+long long graph_captures(const april_graph_cholesky_param_t *param);                                               // solver_launch.inc.h
 void chordal_opts_init(aprilsam_amd_chordal_opts_t *opts);                                                         // solver_chordal.inc.h
 int initialize_chordal(april_graph_t *g, april_graph_cholesky_param_t *param, const aprilsam_amd_chordal_opts_t *opts, aprilsam_amd_chordal_report_t *report,
                        double *rot_out, double *raw_out);
@@ -113,6 +117,7 @@ double max_const(const april_graph_factor_t *f, int i);           // -2 logw_i -
 int max_select(const april_graph_factor_t *f, const double *pa, const double *pb);
 // robust losses (host_objects.cpp): true for a library xyt / xytpos factor that carries one, with its kind and c
 bool robust_of(const april_graph_factor_t *f, int *kind, double *c);
+bool plain_common_factor(const april_graph_factor_t *f);           // an xyt / xytpos factor made by this library, with its z and W in place (it may carry a loss)
 double robust_host_s(const double *z, const double *w, const double *pa, const double *pb);      // r^T W r at pa (/ pb: xyt), eval_finish's association
 int robust_weights(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *factors, double *w);   // solver_calls.inc.h
 

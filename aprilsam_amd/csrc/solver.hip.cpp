@@ -30,6 +30,7 @@
 #include "kernels.hip.h"
 #include "maxmix.hip.h"
 #include "robust.hip.h"
+#include "gnc.hip.h"
 #include "lm.hip.h"
 #include "chordal.hip.h"
 #include "selinv.hip.h"
@@ -249,6 +250,7 @@ struct PatchList {
 #include "solver_marginals.inc.h"
 #include "solver_gating.inc.h"
 #include "solver_lm.inc.h"
+#include "solver_gnc.inc.h"
 #include "solver_chordal.inc.h"
 
 // ------------------------------------------------------------------------------------------------------
@@ -504,6 +506,12 @@ extern "C" int aprilsam_amd_gate_xyt(april_graph_t *graph, april_graph_cholesky_
     return asam::gate_xyt(graph, param, n, a, b, z, W, d2, S);
 }
 extern "C" long long aprilsam_amd_debug_path_solve_bytes(const april_graph_cholesky_param_t *param) { return asam::path_solve_bytes(param); }
+extern "C" void aprilsam_amd_gnc_opts_init(aprilsam_amd_gnc_opts_t *opts) { asam::gnc_opts_init(opts); }
+extern "C" int aprilsam_amd_optimize_gnc(april_graph_t *graph, april_graph_cholesky_param_t *param, const aprilsam_amd_gnc_opts_t *opts, int n,
+                                         const int *candidates, aprilsam_amd_gnc_report_t *report, double *weights, double *stage_trace) {
+    return asam::optimize_gnc(graph, param, opts, n, candidates, report, weights, stage_trace);
+}
+extern "C" long long aprilsam_amd_debug_graph_captures(const april_graph_cholesky_param_t *param) { return asam::graph_captures(param); }
 extern "C" void aprilsam_amd_lm_opts_init(aprilsam_amd_lm_opts_t *opts) { asam::lm_opts_init(opts); }
 extern "C" int aprilsam_amd_optimize_lm(april_graph_t *graph, april_graph_cholesky_param_t *param, const aprilsam_amd_lm_opts_t *opts,
                                         aprilsam_amd_lm_report_t *report, double *trace) {

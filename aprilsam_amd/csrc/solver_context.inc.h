@@ -158,10 +158,11 @@ struct Context {
     const void *api_key[9] = {};
     // Levenberg-Marquardt (solver_lm.inc.h): one iteration captured as its own graph, keyed like gexec plus the LM buffers it reads
     hipGraphExec_t gexec_lm = nullptr;
-    const void *lm_key[9] = {};
+    const void *lm_key[10] = {};
     DBuf<double> d_lm_trial, d_lm_hacc, d_lm_terms, d_lm_trace; DBuf<LmScalars> d_lm; HBuf<LmScalars> h_lm;
     // chordal initialisation (solver_chordal.inc.h): [scratch of the state update 3N][theta N][4 scalars]; the components chosen for the max factors
     DBuf<double> d_ch; HBuf<double> h_ch; DBuf<int> d_ch_sel;
+    long long n_captures = 0;                      // hipGraphs captured and instantiated for this context so far (aprilsam_amd_debug_graph_captures)
     int api_key_runs = 0;                          // calls seen with this key: the first one runs without a graph (run_numeric)
     // captured graphs that are no longer current: hipGraphExecDestroy takes 0.24 ms on this stack, so they are destroyed while the
     // GPU works on a step (reap_retired), not on the way to the next plan

@@ -176,11 +176,23 @@ static void enqueue_factor_level(Context &c, const LevelPlan &L, hipStream_t s, 
     }
 }
 
+// The kernels of gnc.hip.h that run one thread per candidate of an aprilsam_amd_optimize_gnc run (gp.gc_n of them): `a` is what follows the
+// table (n, gf, gW0, par) in the kernel's arguments
+template <class K, class... Args> static void launch_gnc(hipStream_t s, GraphPack &gp, K kern, const Args &...a) {
+    hipLaunchKernelGGL(kern, dim3((gp.gc_n + TPB - 1) / TPB), dim3(TPB), 0, s, gp.gc_n, (const int *)gp.d_gc_f.p, (const double *)gp.d_gc_W0.p, (const GncPar *)gp.d_gc_par.p, a...);
+}
+// inside such a run every linearisation is preceded by the candidates' surrogate weights (none outside: gc_n = 0)
+static void enqueue_gnc_weight(GraphPack &gp, hipStream_t s, const double *upt) {
+    if (gp.gc_n == 0) return;
+    launch_gnc(s, gp, k_gnc_weight, (const int *)gp.d_fa.p, (const int *)gp.d_fb.p, (const double *)gp.d_z.p, (const double *)gp.d_lp.p, (const double *)gp.d_state.p, upt, gp.d_W.p, gp.d_gc_w.p);
+}
+
 // what fills the contribution slots of a Gauss-Newton step: selection, robust weights, linearisation (+ the host-evaluated factors' blocks)
 static void enqueue_linearise(Context &c, GraphPack &gp, hipStream_t s, bool unary_at_lp) {
     const int F = c.plan.F;
     enqueue_select(gp, s);                           // max-mixture factors: the component selected at l_point goes into the factor's slot
     enqueue_robust(gp, s, unary_at_lp ? gp.d_upt.p : (const double *)nullptr);      // robust factors: W_eff = w(s) W0 into the factor's slot
+    enqueue_gnc_weight(gp, s, unary_at_lp ? gp.d_upt.p : (const double *)nullptr);  // GNC candidates: W_eff = w_mu(s) W0
     // (a variant of the kernel without the asymmetric-W orientation branch, for graphs that have no such factor, was measured in round 6: no
     // difference -- 0.79 ms on the 1 M lattice either way)
     auto launch = [&](auto kern) {
@@ -274,9 +286,16 @@ template <class Enqueue> static void replay_captured(Context &c, hipGraphExec_t 
         HIPCHECK(hipStreamEndCapture(s, &graph));
         HIPCHECK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
         HIPCHECK(hipGraphDestroy(graph));
+        c.n_captures++;
     }
     c.graph_stream = s;
     HIPCHECK(hipGraphLaunch(exec, s));
+}
+
+long long graph_captures(const april_graph_cholesky_param_t *param) {
+    SlotLock lk(param, nullptr);
+    auto it = g_ctx.find(param);
+    return it == g_ctx.end() ? -1 : it->second->n_captures;
 }
 
 // run the numeric phase, replaying a captured hipGraph when enabled.  timing: record the stage events c.ev (never captured); the rest as NumericArgs (io_host: the other two do not apply)

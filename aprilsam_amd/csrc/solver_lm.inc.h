@@ -41,6 +41,8 @@ static void lm_enqueue_cost(Context &c, GraphPack &gp, hipStream_t s, const doub
     if (R > 0)           // (robust factors: rho(r^T W0 r) in place of the weighted slot's term)
         hipLaunchKernelGGL(k_lm_cost_robust, dim3((R + TPB - 1) / TPB), dim3(TPB), 0, s, R, gp.d_rb_f.p, gp.d_rb_kind.p, gp.d_rb_c.p, gp.d_rb_W0.p,
                            gp.d_fa.p, gp.d_fb.p, gp.d_z.p, st, terms);
+    if (gp.gc_n > 0)     // (candidates of an aprilsam_amd_optimize_gnc run: rho_mu(r^T W0 r), solver_gnc.inc.h)
+        launch_gnc(s, gp, k_gnc_cost, (const int *)gp.d_fa.p, (const int *)gp.d_fb.p, (const double *)gp.d_z.p, st, terms);
     lm_reduce(s, F, terms, terms + T, out);
 }
 static void lm_enqueue_commit(Context &c, GraphPack &gp, hipStream_t s) {
@@ -69,53 +71,55 @@ static void lm_enqueue_iteration(Context &c, GraphPack &gp, hipStream_t s) {
 static void lm_run_iteration(Context &c, GraphPack &gp, hipStream_t s) {
     rewind_epoch(c, s, 1);
     if (!g_opt.use_graph) { lm_enqueue_iteration(c, gp, s); return; }
-    const void *key[9] = { gp.d_state.p, (const void *)(size_t)gp.serial, (const void *)(size_t)gp.mx_gen, (const void *)(size_t)gp.N,
-                           c.d_lm_trial.p, c.d_lm_terms.p, c.d_lm_trace.p, c.d_lm.p, (const void *)(size_t)gp.rb_gen };
+    const void *key[10] = { gp.d_state.p, (const void *)(size_t)gp.serial, (const void *)(size_t)gp.mx_gen, (const void *)(size_t)gp.N,
+                           c.d_lm_trial.p, c.d_lm_terms.p, c.d_lm_trace.p, c.d_lm.p, (const void *)(size_t)gp.rb_gen, (const void *)(size_t)gp.gc_gen };
     if (memcmp(key, c.lm_key, sizeof(key)) != 0) { c.retire(c.gexec_lm); memcpy(c.lm_key, key, sizeof(key)); }
     replay_captured(c, c.gexec_lm, s, [&] { lm_enqueue_iteration(c, gp, s); });
 }
 
-static int optimize_lm_impl(april_graph_t *g, april_graph_cholesky_param_t *param, const aprilsam_amd_lm_opts_t *o, aprilsam_amd_lm_report_t *report,
-                            double *trace) {
-    const char *who = "aprilsam_amd_optimize_lm";
+// ---- the pieces of a run, shared with the stage driver of aprilsam_amd_optimize_gnc (solver_gnc.inc.h) --------------------------------
+// refusals before anything is uploaded: the param keeps whatever it had.  0, or the code gate_refuse returned
+static int lm_refuse_graph(const char *who, april_graph_t *g, april_graph_cholesky_param_t *param) {
     char msg[256];
-    ensure_device();
-    {   // refusals before anything is uploaded: the param keeps whatever it had
-        SlotLock lk(param, g);
-        if (g_shard.find(param) != g_shard.end()) { snprintf(msg, sizeof msg, "%s: sharded params are not supported", who); return gate_refuse(ERR_UNSUPPORTED, msg); }
-        GraphPack &gp = pack_for(g);
-        pack_factors(gp, g);
-        if (!gp.host_idx.empty()) { snprintf(msg, sizeof msg, "%s: the graph holds host-evaluated factors (foreign types): use april_graph_cholesky", who); return gate_refuse(-4, msg); }
-        if (gp.n_asym > 0) {
-            snprintf(msg, sizeof msg, "%s: a factor has an asymmetric information matrix (the reference-order step does not minimise the cost)", who);
-            return gate_refuse(ERR_UNSUPPORTED, msg);
-        }
-    }
-    if (int rc = resident_begin_impl(g, param)) return rc;        // pack, plan, upload (as the resident loop)
     SlotLock lk(param, g);
-    Context &c = ctx_for(param);
+    if (g_shard.find(param) != g_shard.end()) { snprintf(msg, sizeof msg, "%s: sharded params are not supported", who); return gate_refuse(ERR_UNSUPPORTED, msg); }
     GraphPack &gp = pack_for(g);
-    hipStream_t s = gp.stream;
+    pack_factors(gp, g);
+    if (!gp.host_idx.empty()) { snprintf(msg, sizeof msg, "%s: the graph holds host-evaluated factors (foreign types): use april_graph_cholesky", who); return gate_refuse(-4, msg); }
+    if (gp.n_asym > 0) {
+        snprintf(msg, sizeof msg, "%s: a factor has an asymmetric information matrix (the reference-order step does not minimise the cost)", who);
+        return gate_refuse(ERR_UNSUPPORTED, msg);
+    }
+    return 0;
+}
+// after resident_begin_impl: the run's buffers, state = l_point = x0, no step accepted yet
+static void lm_enter(Context &c, GraphPack &gp, hipStream_t s, const aprilsam_amd_lm_opts_t *o) {
     const int N = gp.N, F = gp.F, T = std::max(F, 2 * N);
     set_small_attr();
     gp.mirror_sync = false; gp.lp_last_valid = false;
     c.d_lm_trial.need((size_t)3 * N); c.d_lm_hacc.need((size_t)3 * N);
     c.d_lm_terms.need((size_t)T + REDUCE_PARTS); c.d_lm_trace.need((size_t)4 * o->max_iters);
     c.d_lm.need(1); c.h_lm.need(1);
+    HIPCHECK(hipMemcpyAsync(gp.d_lp.p, gp.d_state.p, (size_t)24 * N, hipMemcpyDeviceToDevice, s));          // state = l_point = x0
+    HIPCHECK(hipMemsetAsync(c.d_lm_hacc.p, 0xff, (size_t)24 * N, s));                                     // (NaN: no step accepted yet)
+    // d_lambda is about to hold the LM damping: whatever runs next on this param must rewrite it
+    c.lambda_N = -1; c.lambda_val = -1;
+    c.have_fact = false; c.fact_kind = FACT_NONE;
+}
+// the scalars of a run that starts at the current x (lambda0, nu = 2, counters 0), F(x) and the first commit; the stream is NOT synchronised.
+// mirror: F(x) is copied into c.h_lm as well (valid once the stream has been synchronised, and not to be read before)
+static void lm_enqueue_start(Context &c, GraphPack &gp, hipStream_t s, const aprilsam_amd_lm_opts_t *o, bool mirror = true) {
     LmScalars &h = *c.h_lm.p;
     h = LmScalars{};
     h.lambda = o->lambda0; h.nu = 2.0; h.eta = o->eta; h.ftol = o->ftol; h.xtol = o->xtol; h.lambda_max = o->lambda_max; h.max_iters = o->max_iters;
     HIPCHECK(hipMemcpyAsync(c.d_lm.p, c.h_lm.p, sizeof(LmScalars), hipMemcpyHostToDevice, s));
-    HIPCHECK(hipMemcpyAsync(gp.d_lp.p, gp.d_state.p, (size_t)24 * N, hipMemcpyDeviceToDevice, s));          // state = l_point = x0
-    HIPCHECK(hipMemsetAsync(c.d_lm_hacc.p, 0xff, (size_t)24 * N, s));                                     // (NaN: no step accepted yet)
     lm_enqueue_cost(c, gp, s, gp.d_state.p, &c.d_lm.p->F);
     lm_enqueue_commit(c, gp, s);           // (accept_now = 0: trial = x0, d_lambda = lambda0, failure record cleared)
-    HIPCHECK(hipMemcpyAsync(c.h_lm.p, c.d_lm.p, sizeof(LmScalars), hipMemcpyDeviceToHost, s));
-    HIPCHECK(hipStreamSynchronize(s));
-    const double F0 = h.F;
-    // d_lambda now holds the LM damping: whatever runs next on this param must rewrite it
-    c.lambda_N = -1; c.lambda_val = -1;
-    c.have_fact = false; c.fact_kind = FACT_NONE;
+    if (mirror) HIPCHECK(hipMemcpyAsync(c.h_lm.p, c.d_lm.p, sizeof(LmScalars), hipMemcpyDeviceToHost, s));
+}
+// iterations until a stop test holds, the host synchronising every check_every of them
+static void lm_iterate(Context &c, GraphPack &gp, hipStream_t s, const aprilsam_amd_lm_opts_t *o) {
+    LmScalars &h = *c.h_lm.p;
     while (true) {
         // (status 0: fewer than max_iters iterations so far; the chunk never runs past the iterations still allowed)
         const int chunk = std::min(o->check_every, o->max_iters - h.iterations);
@@ -127,15 +131,13 @@ static int optimize_lm_impl(april_graph_t *g, april_graph_cholesky_param_t *para
         }
         if (h.status != 0) break;
     }
-    // results: state = l_point = x*, delta_X = the last accepted h
+}
+// results: state = l_point = x*, delta_X = the last accepted h; returns april_graph_chi2 of x* (synchronises the stream)
+static double lm_write_back(Context &c, GraphPack &gp, hipStream_t s, april_graph_t *g) {
+    const int N = gp.N;
     HIPCHECK(hipMemcpyAsync(gp.h_state.p, gp.d_state.p, (size_t)24 * N, hipMemcpyDeviceToHost, s));
     HIPCHECK(hipMemcpyAsync(gp.h_dx.p, c.d_lm_hacc.p, (size_t)24 * N, hipMemcpyDeviceToHost, s));
     const double chi2 = device_chi2(gp);          // (synchronises the stream)
-    std::vector<double> tr;
-    if (trace && h.iterations > 0) {
-        tr.resize((size_t)4 * h.iterations);
-        HIPCHECK(hipMemcpy(tr.data(), c.d_lm_trace.p, tr.size() * 8, hipMemcpyDeviceToHost));
-    }
     memcpy(gp.h_lp.p, gp.h_state.p, (size_t)24 * N);
     april_graph_node_t **ns = (april_graph_node_t **)g->nodes->data;
     for (int i = 0; i < N; i++) {
@@ -145,6 +147,30 @@ static int optimize_lm_impl(april_graph_t *g, april_graph_cholesky_param_t *para
         const double *dx = gp.h_dx.p + (size_t)3 * i;
         if (!(std::isnan(dx[0]) || std::isnan(dx[1]) || std::isnan(dx[2]))) memcpy(n->delta_X, dx, 24);
     }
+    return chi2;
+}
+
+static int optimize_lm_impl(april_graph_t *g, april_graph_cholesky_param_t *param, const aprilsam_amd_lm_opts_t *o, aprilsam_amd_lm_report_t *report,
+                            double *trace) {
+    ensure_device();
+    if (int rc = lm_refuse_graph("aprilsam_amd_optimize_lm", g, param)) return rc;
+    if (int rc = resident_begin_impl(g, param)) return rc;        // pack, plan, upload (as the resident loop)
+    SlotLock lk(param, g);
+    Context &c = ctx_for(param);
+    GraphPack &gp = pack_for(g);
+    hipStream_t s = gp.stream;
+    lm_enter(c, gp, s, o);
+    lm_enqueue_start(c, gp, s, o);
+    HIPCHECK(hipStreamSynchronize(s));
+    LmScalars &h = *c.h_lm.p;
+    const double F0 = h.F;
+    lm_iterate(c, gp, s, o);
+    std::vector<double> tr;
+    if (trace && h.iterations > 0) {
+        tr.resize((size_t)4 * h.iterations);
+        HIPCHECK(hipMemcpy(tr.data(), c.d_lm_trace.p, tr.size() * 8, hipMemcpyDeviceToHost));      // (lm_iterate left the stream idle)
+    }
+    const double chi2 = lm_write_back(c, gp, s, g);
     if (trace && !tr.empty()) memcpy(trace, tr.data(), tr.size() * 8);
     report->status = h.status; report->iterations = h.iterations; report->accepted = h.accepted; report->rejected_not_spd = h.rejected_not_spd;
     report->F_initial = F0; report->F_final = h.F; report->chi2_final = chi2; report->lambda_final = h.lambda;

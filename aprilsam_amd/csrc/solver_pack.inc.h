@@ -86,6 +86,11 @@ struct GraphPack {
     void rb_clear() {
         if (!rb_f.empty() || rb_on_device) rb_gen++;      // (a pack that never held robust factors keeps its captured graphs)
         rb_f.clear(); rb_kind.clear(); rb_of.clear(); rb_c.clear(); rb_W0.clear(); rb_w.clear(); rb_on_device = 0; rb_dirty = false; }
+    // GNC candidates (gnc.hip.h): a table that exists on the device for the length of ONE aprilsam_amd_optimize_gnc
+    // call -- gc_n > 0 only inside it.  d_gc_f / d_gc_W0 / d_gc_w: packed entry, plain W and last weight per candidate, d_gc_par: loss, c
+    // and mu; d_gc_out / gc_stage: results and their pinned staging.  gc_gen changes with every run: captured LM iterations are keyed by it
+    DBuf<int> d_gc_f; DBuf<double> d_gc_W0, d_gc_w, d_gc_out; DBuf<GncPar> d_gc_par; HBuf<double> gc_stage;
+    int gc_n = 0; long long gc_gen = 0;
     hipStream_t stream = nullptr;
     HBuf<double> h_scalar;
     // incremental steps: the pinned mirrors h_state / h_lp and the device arrays d_state / d_lp hold the same values (mirror_sync),
@@ -99,6 +104,7 @@ struct GraphPack {
         d_chi2f.release(); d_scalar.release(); h_scalar.release(); h_hostH.release(); d_hostH.release(); d_host_idx.release(); d_upt.release();
         d_mx_f.release(); d_mx_k.release(); d_sel.release(); d_mx_z.release(); d_mx_W.release(); d_mx_c.release(); mx_stage.release(); mx_clear();
         d_rb_f.release(); d_rb_kind.release(); d_rb_c.release(); d_rb_W0.release(); d_rb_w.release(); rb_stage.release(); rb_clear();
+        d_gc_f.release(); d_gc_W0.release(); d_gc_w.release(); d_gc_out.release(); d_gc_par.release(); gc_stage.release(); gc_n = 0;
         if (stream) { forget_stream(stream); park_stream(slot, stream); }
         stream = nullptr;
     }

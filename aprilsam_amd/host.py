@@ -50,6 +50,14 @@ class LMError(RuntimeError):
         self.code = code
 
 
+class GncError(RuntimeError):
+    """a negative return of aprilsam_amd_optimize_gnc: .code is the return value"""
+
+    def __init__(self, code, msg=None):
+        super().__init__(f"optimize_gnc failed: {code} {msg or ''}".strip())
+        self.code = code
+
+
 class ChordalError(RuntimeError):
     """a negative return of aprilsam_amd_initialize_chordal: .code is the return value, .report the report's fields (written on -2 only)"""
 
@@ -135,6 +143,13 @@ class SolverLib:
                 d.aprilsam_amd_lm_opts_init.restype = None
                 d.aprilsam_amd_optimize_lm.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.POINTER(abi.LmOpts),
                                                        C.POINTER(abi.LmReport), _dp]
+            if hasattr(d, "aprilsam_amd_optimize_gnc"):         # (defined in the HIP translation unit)
+                d.aprilsam_amd_gnc_opts_init.argtypes = [C.POINTER(abi.GncOpts)]
+                d.aprilsam_amd_gnc_opts_init.restype = None
+                d.aprilsam_amd_optimize_gnc.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.POINTER(abi.GncOpts), C.c_int, _ip,
+                                                        C.POINTER(abi.GncReport), _dp, _dp]
+                d.aprilsam_amd_debug_graph_captures.argtypes = [C.POINTER(abi.CholeskyParam)]
+                d.aprilsam_amd_debug_graph_captures.restype = C.c_longlong
             if hasattr(d, "aprilsam_amd_initialize_chordal"):    # (defined in the HIP translation unit)
                 d.aprilsam_amd_chordal_opts_init.argtypes = [C.POINTER(abi.ChordalOpts)]
                 d.aprilsam_amd_chordal_opts_init.restype = None
@@ -261,6 +276,10 @@ class Param:
         if rc != 0:
             raise RuntimeError("no solver context for this param yet")
         return st.asdict()
+
+    def graph_captures(self):
+        """hipGraphs captured and instantiated for this param so far (aprilsam_amd_debug_graph_captures); -1: no context yet"""
+        return int(self.lib.dll.aprilsam_amd_debug_graph_captures(self.ptr))
 
     def destroy(self):
         if self.ptr:
@@ -563,6 +582,37 @@ class Graph:
         out = rep.asdict()
         if trace:
             out["trace"] = tr[:rep.iterations].copy()
+        return out
+
+    def optimize_gnc(self, param, candidates, trace=False, **opts):
+        """Graduated non-convexity on the GPU (include/aprilsam_amd.h: aprilsam_amd_optimize_gnc) with the surrogate
+        loss on the graph factors listed in `candidates`.  opts: fields of aprilsam_amd_gnc_opts_t (loss, c, mu_step, max_stages) and of
+        its lm member (max_iters per stage, check_every, lambda0, lambda_max, eta, ftol, xtol), defaults for the rest.  Returns the
+        report's fields as a dict, plus "weights": w_mu_final(s) per candidate at the returned states, and when trace is true
+        "stage_trace": a (stages, 4) array (mu, F on entry, F at the end, LM iterations).  Raises GncError(rc) on a negative return."""
+        o = abi.GncOpts()
+        self.lib.dll.aprilsam_amd_gnc_opts_init(C.byref(o))
+        for k, v in opts.items():
+            if k in ("loss", "c", "mu_step", "max_stages"):
+                setattr(o, k, v)
+            elif k in dict(abi.LmOpts._fields_):
+                setattr(o.lm, k, v)
+            else:
+                raise TypeError(f"unknown GNC option {k}")
+        cand = None if candidates is None else np.ascontiguousarray(candidates, dtype=np.int32).ravel()
+        n = 0 if cand is None else len(cand)
+        rep = abi.GncReport()
+        w = np.full(max(n, 1), np.nan)
+        tr = np.full((max(int(o.max_stages), 1), 4), np.nan) if trace else None
+        rc = self.lib.dll.aprilsam_amd_optimize_gnc(self.ptr, param.ptr if param is not None else None, C.byref(o), n,
+                                                    _np_i(cand) if cand is not None else None, C.byref(rep), _np_d(w),
+                                                    _np_d(tr) if trace else None)
+        if rc < 0:
+            raise GncError(rc, self.lib.last_error())
+        out = rep.asdict()
+        out["weights"] = w[:n].copy()
+        if trace:
+            out["stage_trace"] = tr[:rep.stages].copy()
         return out
 
     def initialize_chordal(self, param, rot=False, raw=False, **opts):

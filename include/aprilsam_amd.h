@@ -600,6 +600,66 @@ int aprilsam_amd_factor_get_robust(const april_graph_factor_t *factor, int *kind
  * Returns 0 or -13 (an index out of range or a bad argument) */
 int aprilsam_amd_robust_weights(april_graph_t *graph, april_graph_cholesky_param_t *param, int n, const int *factors, double *w);
 
+/* ---- graduated non-convexity: outlier-robust optimisation (Yang et al., RA-L 2020) ---------------------------
+ * The robust losses above are non-convex and help only from a start near the optimum.  aprilsam_amd_optimize_gnc optimises a sequence of
+ * surrogate losses on a list of CANDIDATE factors (typically every loop closure): the first almost quadratic, so the start does not
+ * matter, the last Geman-McClure (GM) or truncated least squares (TLS).  With r the plain factor's residual (theta wrapped), s = r' W r,
+ * the threshold c on sqrt(s), cc = c^2 and the control parameter mu:
+ *     GM    m = mu cc:                       rho_mu(s) = m s / (m + s)                         w_mu(s) = (m / (m + s))^2
+ *     TLS   lo = mu / (mu + 1) cc, hi = (mu + 1) / mu cc:
+ *           s <= lo                          rho_mu(s) = s                                     w_mu(s) = 1
+ *           s >= hi                          rho_mu(s) = cc                                    w_mu(s) = 0
+ *           otherwise                        rho_mu(s) = 2 c sqrt(mu (mu + 1) s) - mu (cc + s)   w_mu(s) = c sqrt(mu (mu + 1) / s) - mu
+ *           (mu = +inf: lo = hi = cc, TLS itself.)  w_mu = d rho_mu / d s.  A NaN s gives a NaN weight and a NaN rho.
+ *   Start      s_max = the largest s over the candidates at the incoming states (a max reduction on the device).
+ *              GM: mu_0 = max(1, 2 s_max / cc).  TLS: mu_0 = cc / (2 s_max - cc) when 2 s_max > cc; otherwise every candidate is an
+ *              inlier: mu_0 = +inf, one stage with all weights 1 runs and the schedule is finished.
+ *   Stage      exactly the iteration loop of aprilsam_amd_optimize_lm from the current x with opts.lm: lambda restarts at lambda0 and nu
+ *              at 2; in the objective every candidate's term is rho_mu(s); at every linearisation every candidate's W_eff is
+ *              w_mu(s) W, s taken where a robust factor's is (xyt: the l_points; xytpos: the node's state -- both x inside the run).
+ *              Whatever LM status ends the stage, the run goes on (STALLED is counted in stages_stalled).
+ *   Schedule   GM: after a stage stop if mu == 1 (status 1), else mu <- max(1, mu / mu_step).  TLS: after a stage evaluate the weights
+ *              at the stage's final x; stop if all are exactly 0 or 1 (status 1), else mu <- mu * mu_step.  max_stages stages without
+ *              that: status 2.
+ *   mu lives in device memory and is written between stages; the ONE captured LM iteration is replayed for every stage.  The host
+ *   synchronises once for s_max, once per lm.check_every iterations and (TLS) once per stage; results never depend on check_every, and
+ *   two runs give identical bits.
+ * Non-candidate factors keep their own behaviour inside the run: plain, robust and max factors as in aprilsam_amd_optimize_lm.
+ * What the call leaves is what aprilsam_amd_optimize_lm leaves: state = l_point = x*, delta_X = the last accepted h (untouched if none), the
+ * plan kept, the retained factor DROPPED, param->tikhanov untouched.  No factor object is modified: aprilsam_amd_factor_get_robust of a
+ * candidate still says NONE, the packed W slots hold the plain W again, and a following april_graph_cholesky gives the bits it gives on a
+ * fresh copy of the graph at the same states.
+ * candidates: n distinct graph factor indices.  weights: NULL or n doubles, w_mu_final(s) of candidate i evaluated by a last device pass at
+ * the returned states (not whatever the last linearisation used).  stage_trace: NULL or 4 * opts->max_stages doubles, one row per stage:
+ * mu, F on entry under that mu, F at the stage's end, the stage's LM iterations.
+ * Returns 0 (reason in report->status), or: -1 empty graph; -4 host-evaluated (foreign) factors; -12 sharded param, an asymmetric W
+ * anywhere, or a candidate that is not a library-made xyt / xytpos factor, already carries a robust loss, is a max factor, or whose W is
+ * not symmetric positive definite (all three leading minors > 0, mirror entries bitwise equal); -13 a null argument, n <= 0, an index out
+ * of range, a duplicate index, bad options (loss, c, mu_step <= 1, max_stages < 1, anything aprilsam_amd_optimize_lm refuses in lm); -14
+ * no HIP device.  On a refusal nothing is written and graph and param stay usable.  A failure during the run behaves as in
+ * aprilsam_amd_optimize_lm.  aprilsam_amd_factor_set_robust keeps refusing kinds above 3: the surrogates are internal to the run. */
+enum { APRILSAM_AMD_GNC_GM = 1, APRILSAM_AMD_GNC_TLS = 2 };
+typedef struct {
+    int    loss;          /* GM (default) or TLS */
+    double c;             /* finite, > 0: threshold on the Mahalanobis distance sqrt(s); default sqrt(16.27), chi^2 of 3 dof at 0.999 */
+    double mu_step;       /* > 1, default 1.4 */
+    int    max_stages;    /* >= 1, default 100 */
+    aprilsam_amd_lm_opts_t lm;   /* one stage's LM run; lm.max_iters is the cap PER STAGE, default 10 here; the rest as lm_opts_init */
+} aprilsam_amd_gnc_opts_t;
+void aprilsam_amd_gnc_opts_init(aprilsam_amd_gnc_opts_t *opts);
+typedef struct {
+    int    status;            /* 1 schedule finished (GM: the mu = 1 stage ran; TLS: every weight 0 or 1 after a stage), 2 max_stages */
+    int    stages, iterations, accepted, stages_stalled;      /* iterations / accepted: LM iterations / accepted steps over all stages */
+    int    n_inliers;         /* candidates with s <= c^2 at the returned states */
+    double mu_initial, mu_final, s_max;
+    double F_final;           /* the objective of the LAST stage at the returned states */
+    double chi2_final;        /* april_graph_chi2 of the returned states (plain factors) */
+} aprilsam_amd_gnc_report_t;
+int aprilsam_amd_optimize_gnc(april_graph_t *graph, april_graph_cholesky_param_t *param, const aprilsam_amd_gnc_opts_t *opts,
+                              int n, const int *candidates, aprilsam_amd_gnc_report_t *report, double *weights, double *stage_trace);
+/* debug: hipGraphs captured and instantiated for this param so far (-1: no context; restarts when a failure drops the context) */
+long long aprilsam_amd_debug_graph_captures(const april_graph_cholesky_param_t *param);
+
 /* ---- multi-GPU: nested-dissection subtree sharding, one process per GPU -------
  * The reference has no counterpart (it is sequential); a C host drives a sharded solve through the same graph / param
  * objects it hands to april_graph_cholesky (aprilsam.h:268-281):
