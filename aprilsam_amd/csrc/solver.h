@@ -47,6 +47,7 @@ struct Options {
     int tagged_x = 1;             // multi-level back substitutions: how a front hands its x to its children.  1 = as epoch-tagged 16-byte granules, no flag (kernels.hip.h: gather_x; a launch holding a front of more than 256 update rows takes form 2: launch_xmode); 0 = write-through x, drained, then the flag -- no L2 write-back (publish_flag_wt); 2 = plain x, L2 write-back, flag (publish_flag: the form before, kept for measurements).  Measured on M3500, resident step: 0.2092 (2 and the commit before) / 0.2093 (0) / 0.2028 ms (1), profiles/r08_downsweep_handover.txt
     int linearize_staged_min = 32768; // factors per launch from which k_linearize writes its results out through LDS (coalesced stores)
     int mem_cap_mb = 0;           // > 0: refuse any single device buffer above this size with ERR_OOM (tests: the out-of-memory path)
+    int solve_chunk_cols = 0;     // aprilsam_amd_solve: columns per chunk of the work buffer, rounded up to a multiple of 16 (0 = as many as keep the buffer under 1 GB / mem_cap_mb, at least 16); the results do not depend on it
     int pool_guard = 0;           // debug: > 0 = every frontal array of a plan is followed by a guard band of this many doubles, NaN-filled at plan upload and checked after every synchronised step (ERR_GUARD); a stray read that is used poisons the result
     int pool_poison = 0;          // debug: 1 = before every step, the update block of every front the step (re)factorises and x at its own positions are filled with NaN: a dependency wait of a multi-level launch that passes early yields NaN instead of the previous step's numbers
     int skip_flag_waits = 0;      // debug, negative control of pool_poison: 1 = the fronts of the batch path's multi-level factorisation launch do NOT wait for their children
@@ -99,6 +100,11 @@ long long selinv_runs(const april_graph_cholesky_param_t *param);
 int marginals_joint_any(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, double *cov);      // solver_gating.inc.h
 int gate_xyt(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, const double *z, const double *W, double *d2, double *S);
 long long path_solve_bytes(const april_graph_cholesky_param_t *param);
+int tree_solve(april_graph_t *g, april_graph_cholesky_param_t *param, int mode, int nrhs, const double *B, double *X);                // solver_treesolve.inc.h
+int marginals_cross(april_graph_t *g, april_graph_cholesky_param_t *param, int anchor, int n, const int *nodes, double *cov);
+int relative_covariances(april_graph_t *g, april_graph_cholesky_param_t *param, int anchor, int n, const int *nodes, double *cov);
+long long tree_solve_bytes(const april_graph_cholesky_param_t *param);
+int factorised_nodes(const april_graph_cholesky_param_t *param);
 int max_selected(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *factors, int *out);   // solver_pack.inc.h
 void lm_opts_init(aprilsam_amd_lm_opts_t *opts);                                                                    // solver_lm.inc.h
 int optimize_lm(april_graph_t *g, april_graph_cholesky_param_t *param, const aprilsam_amd_lm_opts_t *opts, aprilsam_amd_lm_report_t *report, double *trace);

@@ -35,6 +35,7 @@
 #include "chordal.hip.h"
 #include "selinv.hip.h"
 #include "pathsolve.hip.h"
+#include "treesolve.hip.h"
 #include "plan.h"
 #include "refmodel.h"
 #include "solver.h"
@@ -79,7 +80,7 @@ static const OptionDef OPTION_TABLE[] = {
     { "speculate_factors", &Options::speculate_factors, 0, true }, { "warm_up", &Options::warm_up, 0, true }, { "pin_last", &Options::pin_last, 0, false }, { "persist", &Options::persist, 0, false },
     { "persist_max_fronts", &Options::persist_max_fronts, 0, false }, { "xcd_place", &Options::xcd_place, 0, false }, { "linearize_staged_min", &Options::linearize_staged_min, 0, false },
     { "wave_backsolve", &Options::wave_backsolve, 0, false }, { "tagged_x", &Options::tagged_x, 0, false, 2 }, { "blk_backsolve", &Options::blk_backsolve, 0, false }, { "tail_poses", &Options::tail_poses, 8, false },
-    { "batch_extend", &Options::batch_extend, 0, true }, { "extend_tail_fronts", &Options::extend_tail_fronts, 0, true }, { "mem_cap_mb", &Options::mem_cap_mb, 0, true },
+    { "batch_extend", &Options::batch_extend, 0, true }, { "extend_tail_fronts", &Options::extend_tail_fronts, 0, true }, { "mem_cap_mb", &Options::mem_cap_mb, 0, true }, { "solve_chunk_cols", &Options::solve_chunk_cols, 0, true },
     { "pool_guard", &Options::pool_guard, 0, false }, { "amalg", &Options::amalg, 0, false }, { "amalg_max", &Options::amalg_max, 1, false }, { "pool_poison", &Options::pool_poison, 0, false }, { "skip_flag_waits", &Options::skip_flag_waits, 0, false },
 };
 static const OptionDef *find_option(const char *name) {
@@ -249,6 +250,7 @@ struct PatchList {
 #include "solver_shard.inc.h"
 #include "solver_marginals.inc.h"
 #include "solver_gating.inc.h"
+#include "solver_treesolve.inc.h"
 #include "solver_lm.inc.h"
 #include "solver_gnc.inc.h"
 #include "solver_chordal.inc.h"
@@ -506,6 +508,18 @@ extern "C" int aprilsam_amd_gate_xyt(april_graph_t *graph, april_graph_cholesky_
     return asam::gate_xyt(graph, param, n, a, b, z, W, d2, S);
 }
 extern "C" long long aprilsam_amd_debug_path_solve_bytes(const april_graph_cholesky_param_t *param) { return asam::path_solve_bytes(param); }
+extern "C" int aprilsam_amd_solve(april_graph_t *graph, april_graph_cholesky_param_t *param, int mode, int nrhs, const double *B, double *X) {
+    return asam::tree_solve(graph, param, mode, nrhs, B, X);
+}
+extern "C" int aprilsam_amd_marginals_cross(april_graph_t *graph, april_graph_cholesky_param_t *param, int anchor, int n, const int *nodes, double *cov) {
+    return asam::marginals_cross(graph, param, anchor, n, nodes, cov);
+}
+extern "C" int aprilsam_amd_relative_covariances(april_graph_t *graph, april_graph_cholesky_param_t *param, int anchor, int n, const int *nodes,
+                                                 double *cov) {
+    return asam::relative_covariances(graph, param, anchor, n, nodes, cov);
+}
+extern "C" int aprilsam_amd_factorised_nodes(const april_graph_cholesky_param_t *param) { return asam::factorised_nodes(param); }
+extern "C" long long aprilsam_amd_debug_solve_bytes(const april_graph_cholesky_param_t *param) { return asam::tree_solve_bytes(param); }
 extern "C" void aprilsam_amd_gnc_opts_init(aprilsam_amd_gnc_opts_t *opts) { asam::gnc_opts_init(opts); }
 extern "C" int aprilsam_amd_optimize_gnc(april_graph_t *graph, april_graph_cholesky_param_t *param, const aprilsam_amd_gnc_opts_t *opts, int n,
                                          const int *candidates, aprilsam_amd_gnc_report_t *report, double *weights, double *stage_trace) {

@@ -78,6 +78,23 @@ struct PathState {
     }
 };
 
+// solves with the retained factor (solver_treesolve.inc.h): the tables of the whole-tree passes, kept against the factorisation counter,
+// and the device / pinned buffers of one call
+struct TsLevel { int asm_off = 0, n_asm = 0, tr_off = 0, n_tr = 0, gm_off = 0, n_gm = 0, gat_off = 0, n_gat = 0, gt_off = 0, n_gt = 0; };
+struct TreeState {
+    long long serial = -1;                 // fact_serial the tables describe
+    long long rows = 0;                    // sum over the fronts of s + u: the work buffer takes this many doubles per column
+    std::vector<int> wrow; std::vector<TsLevel> lev;      // a front's first row in the work buffer; the levels, root first
+    DBuf<PsFront> d_fr; DBuf<TsFront> d_tf; DBuf<int2> d_ent; DBuf<int> d_cptr, d_npos, d_pos, d_nodes; DBuf<TsKid> d_cent;
+    DBuf<double> d_buf, d_B, d_st; HBuf<double> h_B, h_X;
+    long long peak_bytes = 0;              // the largest work buffer a call has used
+    void release() {
+        d_fr.release(); d_tf.release(); d_ent.release(); d_cptr.release(); d_npos.release(); d_pos.release(); d_nodes.release(); d_cent.release();
+        d_buf.release(); d_B.release(); d_st.release(); h_B.release(); h_X.release();
+        wrow.clear(); lev.clear(); serial = -1;
+    }
+};
+
 struct Context {
     Plan plan;
     bool have_plan = false;
@@ -202,10 +219,11 @@ struct Context {
     std::vector<SelLevel> sel_levels; int sel_tab_kind = 0, sel_N = 0;
     long long sel_serial = -1, sel_tab_serial = -1, sel_runs = 0, sel_pool = 1; double sel_flops = 0;
     PathState ps;
+    TreeState ts;
     void release_sel() {
         d_sigma.release(); d_sel_scr.release(); d_sel_fd.release(); d_sel_i32.release(); d_sel_q.release(); d_sel_ent.release(); h_cov.release();
         sel_levels.clear(); sel_serial = -1; sel_tab_serial = -1;
-        ps.release();
+        ps.release(); ts.release();
     }
     void release() {
         release_sel();

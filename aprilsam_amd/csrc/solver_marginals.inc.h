@@ -127,6 +127,19 @@ static void record_factor(Context &c, int kind, const GraphPack &gp) {
     c.fact_kind = kind; c.fact_epoch = c.epoch_steps; c.fact_asym = gp.n_asym > 0 || c.wt_any; c.fact_serial++;
 }
 
+// Sigma of the retained factor on stream s, unless it is there already; the caller stamps c.sel_serial = c.fact_serial once the stream has
+// been synchronised.  Shared with aprilsam_amd_relative_covariances (solver_treesolve.inc.h).
+static void sel_ensure(Context &c, hipStream_t s) {
+    if (c.sel_serial == c.fact_serial) return;
+    c.sel_serial = -1;
+    // (the plan's tables serve every factor of that plan; an extended structure changes with every incremental step)
+    if (c.sel_tab_serial < 0 || c.fact_kind == FACT_EXTENDED || c.sel_tab_kind != FACT_PLAN) build_sel_tables(c, s);
+    c.sel_tab_kind = c.fact_kind;
+    c.d_sigma.need((size_t)c.sel_pool);
+    enqueue_selinv(c, s);
+    c.sel_runs++;
+}
+
 static int marginals_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *qa, const int *qb, double *cov, bool joint) {
     auto refuse = [](int code, const char *msg) { set_last_error(code, msg); fprintf(stderr, "aprilsam_amd: ERROR %d: %s\n", code, msg); fflush(stderr); return code; };
     if (!param || !cov) return refuse(ERR_BAD_GRAPH, "aprilsam_amd_marginals: null param or output");
@@ -154,15 +167,7 @@ static int marginals_impl(april_graph_t *g, april_graph_cholesky_param_t *param,
     if (n == 0) return 0;
     hipStream_t s = take_stream(t_slot);
     struct Park { int slot; hipStream_t s; ~Park() { park_stream(slot, s); } } park{ t_slot, s };
-    if (c.sel_serial != c.fact_serial) {                  // Sigma of this factor not computed yet
-        c.sel_serial = -1;
-        // (the plan's tables serve every factor of that plan; an extended structure changes with every incremental step)
-        if (c.sel_tab_serial < 0 || c.fact_kind == FACT_EXTENDED || c.sel_tab_kind != FACT_PLAN) build_sel_tables(c, s);
-        c.sel_tab_kind = c.fact_kind;
-        c.d_sigma.need((size_t)c.sel_pool);
-        enqueue_selinv(c, s);
-        c.sel_runs++;
-    }
+    sel_ensure(c, s);
     const int per = joint ? 36 : 9;
     c.d_sel_q.need((size_t)2 * n);
     HIPCHECK(hipMemcpyAsync(c.d_sel_q.p, qa, (size_t)4 * n, hipMemcpyHostToDevice, s));

@@ -138,6 +138,13 @@ class SolverLib:
                 d.aprilsam_amd_gate_xyt.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.c_int, _ip, _ip, _dp, _dp, _dp, _dp]
                 d.aprilsam_amd_debug_path_solve_bytes.argtypes = [C.POINTER(abi.CholeskyParam)]
                 d.aprilsam_amd_debug_path_solve_bytes.restype = C.c_longlong
+            if hasattr(d, "aprilsam_amd_solve"):                  # (defined in the HIP translation unit)
+                d.aprilsam_amd_solve.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.c_int, C.c_int, _dp, _dp]
+                for nm in ("aprilsam_amd_marginals_cross", "aprilsam_amd_relative_covariances"):
+                    getattr(d, nm).argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.c_int, C.c_int, _ip, _dp]
+                d.aprilsam_amd_factorised_nodes.argtypes = [C.POINTER(abi.CholeskyParam)]
+                d.aprilsam_amd_debug_solve_bytes.argtypes = [C.POINTER(abi.CholeskyParam)]
+                d.aprilsam_amd_debug_solve_bytes.restype = C.c_longlong
             if hasattr(d, "aprilsam_amd_optimize_lm"):          # (defined in the HIP translation unit)
                 d.aprilsam_amd_lm_opts_init.argtypes = [C.POINTER(abi.LmOpts)]
                 d.aprilsam_amd_lm_opts_init.restype = None
@@ -561,6 +568,49 @@ class Graph:
         if rc < 0:
             raise MarginalsError(rc, self.lib.last_error())
         return d2, S
+
+    SOLVE_MODES = {"full": 0, "forward": 1, "backward": 2}
+
+    def solve(self, param, B, mode="full"):
+        """Solve with the factor of the last solver call on `param` (include/aprilsam_amd.h: aprilsam_amd_solve).  B: [3N] or [nrhs, 3N]
+        in node order; mode "full" (A^-1 B), "forward" (L^-1, permuted back to node order) or "backward" (L^-T).  Returns an array of
+        B's shape.  Raises MarginalsError(rc) on a negative return."""
+        B = np.ascontiguousarray(B, dtype=float)
+        B2 = B.reshape(1, -1) if B.ndim == 1 else B
+        n = self._factorised_nodes(param)
+        if B2.ndim != 2 or B2.shape[0] < 1 or (n >= 0 and B2.shape[1] != 3 * n):
+            raise ValueError(f"B must have shape [3N] or [nrhs, 3N] with N = {n}, the nodes of the last solver call")
+        X = np.empty_like(B2)
+        rc = self.lib.dll.aprilsam_amd_solve(self.ptr, param.ptr, self.SOLVE_MODES[mode], B2.shape[0], _np_d(B2), _np_d(X))
+        if rc < 0:
+            raise MarginalsError(rc, self.lib.last_error())
+        return X.reshape(B.shape)
+
+    def _factorised_nodes(self, param):
+        """the nodes of the system the retained factor of `param` was made for (what the C entry points call N); -1: no factor"""
+        return int(self.lib.dll.aprilsam_amd_factorised_nodes(param.ptr))
+
+    def _anchored(self, fn, param, anchor, nodes):
+        if nodes is None:
+            out = np.zeros((max(self._factorised_nodes(param), 0), 3, 3))
+            rc = fn(self.ptr, param.ptr, int(anchor), 0, None, _np_d(out))
+        else:
+            idx = np.ascontiguousarray(nodes, dtype=np.int32).ravel()
+            out = np.empty((len(idx), 3, 3))
+            rc = fn(self.ptr, param.ptr, int(anchor), len(idx), _np_i(idx), _np_d(out))
+        if rc < 0:
+            raise MarginalsError(rc, self.lib.last_error())
+        return out
+
+    def marginals_cross(self, param, anchor, nodes=None):
+        """[n, 3, 3] cross-covariances Sigma_{node, anchor} of `nodes` (all nodes: None) with the pose `anchor`, the node's unknowns as
+        rows (include/aprilsam_amd.h: aprilsam_amd_marginals_cross).  Raises MarginalsError(rc) on a negative return."""
+        return self._anchored(self.lib.dll.aprilsam_amd_marginals_cross, param, anchor, nodes)
+
+    def relative_covariances(self, param, anchor, nodes=None):
+        """[n, 3, 3] covariances of the predicted xyt measurement anchor^-1 o node in the anchor's frame, Jacobians at the current states
+        (include/aprilsam_amd.h: aprilsam_amd_relative_covariances).  Raises MarginalsError(rc) on a negative return."""
+        return self._anchored(self.lib.dll.aprilsam_amd_relative_covariances, param, anchor, nodes)
 
     def optimize_lm(self, param, trace=False, **opts):
         """Levenberg-Marquardt on the GPU until a stop test holds (include/aprilsam_amd.h: aprilsam_amd_optimize_lm).

@@ -463,6 +463,41 @@ int aprilsam_amd_gate_xyt(april_graph_t *graph, april_graph_cholesky_param_t *pa
 /* debug: the largest path-solve work buffer this param has used, in bytes (-1: no context) */
 long long aprilsam_amd_debug_path_solve_bytes(const april_graph_cholesky_param_t *param);
 
+/* ---- solves with the retained factor -----------------------------------------------------------------------
+ * The system is the one aprilsam_amd_marginals describes: A = sum J^T W J + diag(lambda) of the last successful solver call on `param`
+ * (lambda where that step put it, everything at the l_points, robust and max factors as they were factorised).  Write A = P' L L' P with
+ * P the permutation from node order to elimination order (a pose keeps its three consecutive rows).  aprilsam_amd_solve computes, for
+ * nrhs right-hand sides,
+ *     APRILSAM_AMD_SOLVE_FULL      X = A^-1 B
+ *     APRILSAM_AMD_SOLVE_FORWARD   X = P' L^-1 P B        (X'X = B' Sigma B: whitening, Mahalanobis norms)
+ *     APRILSAM_AMD_SOLVE_BACKWARD  X = P' L^-T P B        (E[X X'] = Sigma for white noise B: posterior samples)
+ * B and X hold nrhs vectors of 3 N doubles each (vector r at offset r 3 N, node i's unknowns at 3 i .. 3 i + 2 in the order of delta_X; N
+ * = the number of factorised nodes).  X == B is allowed, any other overlap is undefined.  FULL equals BACKWARD applied to FORWARD bit
+ * for bit; the caller never needs the permutation.  Non-finite values in B propagate; a zero column gives a column that compares equal
+ * to 0.0.  The columns are processed in chunks (multiples of 16) so that the work buffer -- (sum over the fronts of rows) x columns
+ * doubles -- stays under 1 GB or option mem_cap_mb, one tile of 16 columns at the least; option solve_chunk_cols forces the width.  The
+ * results do not depend on the chunking, and two calls give the same bits.
+ * Returns 0, or the codes of aprilsam_amd_marginals: -1 no retained factor or a resident run in progress (also after
+ * aprilsam_amd_optimize_lm / _gnc / aprilsam_amd_initialize_chordal, which drop the factor); -12 sharded param or asymmetric W in the
+ * factorised graph; -13 a null argument, mode outside 0..2, nrhs < 1, anchor or a node out of range of the factorised system (for
+ * aprilsam_amd_relative_covariances also of graph); -14 no HIP device; -11 the work buffer does not fit under option mem_cap_mb.  A
+ * refused or failed call writes nothing to X / cov (the chunks of a call are kept back until the last one has succeeded), sets aprilsam_amd_last_error and leaves plan, factor and Sigma in place. */
+enum { APRILSAM_AMD_SOLVE_FULL = 0, APRILSAM_AMD_SOLVE_FORWARD = 1, APRILSAM_AMD_SOLVE_BACKWARD = 2 };
+int aprilsam_amd_solve(april_graph_t *graph, april_graph_cholesky_param_t *param, int mode, int nrhs, const double *B, double *X);
+/* Sigma_{node, anchor} for the n listed nodes (nodes == NULL: all N nodes, n ignored): 9 doubles per node, row-major, the node's unknowns
+ * as rows.  One FULL solve of the anchor's three unit columns over the whole tree, then an extraction. */
+int aprilsam_amd_marginals_cross(april_graph_t *graph, april_graph_cholesky_param_t *param, int anchor, int n, const int *nodes, double *cov);
+/* The covariance of the predicted xyt measurement x_anchor^-1 o x_i in the anchor's frame for the n listed nodes i (NULL: all), 9 doubles
+ * each, row-major:  [J_a J_i] [[S_aa S_ai]; [S_ia S_ii]] [J_a J_i]'  with the Jacobians an xyt factor computes at the nodes' CURRENT
+ * states, exactly as aprilsam_amd_gate_xyt takes them: the result equals gate_xyt's S - W^-1 for the pair (anchor, i).  S_ai comes from
+ * the column solve, S_aa and S_ii from the selected inversion's Sigma pool: the first call after a solver call runs the inversion as
+ * aprilsam_amd_marginals does.  i == anchor gives exact zeros. */
+int aprilsam_amd_relative_covariances(april_graph_t *graph, april_graph_cholesky_param_t *param, int anchor, int n, const int *nodes, double *cov);
+/* N of the calls above: the nodes of the system the retained factor of `param` was made for, or -1 when there is none (no device needed) */
+int aprilsam_amd_factorised_nodes(const april_graph_cholesky_param_t *param);
+/* debug: the largest whole-tree work buffer this param has used, in bytes (-1: no context) */
+long long aprilsam_amd_debug_solve_bytes(const april_graph_cholesky_param_t *param);
+
 /* ---- Levenberg-Marquardt optimisation -------------------------------------------------------------------
  * The reference has no counterpart: april_graph_cholesky is one Gauss-Newton step with the fixed damping param->tikhanov, and the
  * drop-in entry points keep exactly that.  aprilsam_amd_optimize_lm runs a whole damped optimisation on the GPU, every iteration one
