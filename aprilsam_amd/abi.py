@@ -142,6 +142,10 @@ class ChordalReport(C.Structure):
 # robust loss kinds of xyt / xytpos factors (include/aprilsam_amd.h: aprilsam_amd_factor_set_robust)
 ROBUST_NONE, ROBUST_HUBER, ROBUST_CAUCHY, ROBUST_DCS = 0, 1, 2, 3
 
+# range / bearing / range-bearing factors (include/aprilsam_amd.h: aprilsam_amd_factor_polar_create)
+POLAR_RANGE, POLAR_BEARING, POLAR_RANGE_BEARING = 1, 2, 3
+FACTOR_POLAR_TYPE = 4
+
 # measured LP64 layout of the reference; checked by tests/test_abi.py
 EXPECTED_SIZES = {"ZArray": 24, "Graph": 32, "Factor": 104, "Node": 112, "CholeskyParam": 128}
 EXPECTED_OFFSETS = {

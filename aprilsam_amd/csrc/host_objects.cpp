@@ -8,7 +8,8 @@
 // callers; the solver entry points never call them — factors of type 1/2 are evaluated by the HIP
 // kernels (csrc/kernels.hip.h).  Max-mixture factors (type 3) are built here too: their selection rule
 // (max_select) is the one the incremental path applies on the host and k_select_mixture restates on the device.  Robust losses on xyt /
-// xytpos factors are kept here as well: a tagged block hung off u.common.impl, applied by eval_finish.
+// xytpos factors are kept here as well: a tagged block hung off u.common.impl, applied by eval_finish.  Range, bearing
+// and range-bearing factors (type 4) are built here: true m-row factors on the host, xyt slots on the device (polar.h).
 #include <cmath>
 #include <cstdio>
 #include <string>
@@ -21,6 +22,7 @@
 #include "solver.h"
 #include "errors.h"
 #include "robust.h"
+#include "polar.h"
 
 namespace {
 
@@ -237,6 +239,95 @@ april_graph_factor_t *max_copy(april_graph_factor_t *f) {
     return c;
 }
 
+// ---- range / bearing / range-bearing factor -------------------------------------------------
+// u.common as the reference lays it out: z holds m doubles, W is m x m (m = 1 or 2), ztruth stays NULL; the kind lives in a tagged block
+// hung off u.common.impl (as a robust loss does on an xyt factor).
+constexpr unsigned long long POLAR_TAG = 0x706f6c61725f616dULL;        // "polar_am"
+struct PolarBlock { unsigned long long tag = POLAR_TAG; int kind = 0; };
+april_graph_factor_eval_t *polar_eval(april_graph_factor_t *f, april_graph_t *g, april_graph_factor_eval_t *e);
+PolarBlock *own_polar(const april_graph_factor_t *f) {
+    if (f->type != APRILSAM_AMD_FACTOR_POLAR_TYPE || f->nnodes != 2 || f->eval != polar_eval) return nullptr;
+    void *p = f->u.common.impl;
+    return (p && *(const unsigned long long *)p == POLAR_TAG) ? (PolarBlock *)p : nullptr;
+}
+matd_t *matd_new(int nr, int nc, const double *data) {
+    matd_t *m = (matd_t *)calloc(1, sizeof(matd_t) + (size_t)nr * nc * sizeof(double));
+    m->nrows = nr; m->ncols = nc;
+    if (data) memcpy(m->data, data, (size_t)nr * nc * sizeof(double));
+    return m;
+}
+// april_graph_factor_eval_destroy frees `length` Jacobians (april_graph.c:38-43), and this factor has two nodes whatever its length: with
+// m = 1 both Jacobians live in ONE block (the second is an interior pointer, freed with the first), with m = 2 in one block each
+april_graph_factor_eval_t *polar_eval_alloc(int m) {
+    april_graph_factor_eval_t *e = (april_graph_factor_eval_t *)calloc(1, sizeof(*e));
+    e->jacobians = (matd_t **)calloc(3, sizeof(matd_t *));            // NULL-terminated
+    const size_t one = sizeof(matd_t) + (size_t)m * 3 * sizeof(double);
+    if (m == 1) {
+        char *blk = (char *)calloc(2, one);
+        e->jacobians[0] = (matd_t *)blk; e->jacobians[1] = (matd_t *)(blk + one);
+    } else { e->jacobians[0] = (matd_t *)calloc(1, one); e->jacobians[1] = (matd_t *)calloc(1, one); }
+    for (int i = 0; i < 2; i++) { e->jacobians[i]->nrows = m; e->jacobians[i]->ncols = 3; }
+    e->r = (double *)calloc(m, sizeof(double));
+    e->W = matd_new(m, m, nullptr);
+    e->length = m;
+    return e;
+}
+// the true m-row factor: r = z - h(q), J = G J_xyt (rows 0, 1 of the xyt Jacobians), W, chi2 = r' W r.  rho^2 == 0: J = 0
+april_graph_factor_eval_t *polar_eval_at(april_graph_factor_t *f, april_graph_t *g, april_graph_factor_eval_t *e, bool at_state) {
+    const PolarBlock *pb_ = own_polar(f);
+    if (!pb_) return nullptr;
+    const int kind = pb_->kind, m = asam::polar_rows(kind);
+    if (!e) e = polar_eval_alloc(m);
+    april_graph_node_t **ns = (april_graph_node_t **)g->nodes->data;
+    const double *pa = at_state ? ns[f->nodes[0]]->state : ns[f->nodes[0]]->l_point;
+    const double *pb = at_state ? ns[f->nodes[1]]->state : ns[f->nodes[1]]->l_point;
+    const double ca = cos(pa[2]), sa = sin(pa[2]);
+    const double dx = pb[0] - pa[0], dy = pb[1] - pa[1];
+    const double q0 = ca * dx + sa * dy, q1 = -sa * dx + ca * dy;
+    const double Jx[2][6] = { { -ca, -sa, -sa * dx + ca * dy, sa, -ca, -ca * dx - sa * dy }, { ca, sa, 0, -sa, ca, 0 } };
+    double G[4] = { 0, 0, 0, 0 };
+    (void)asam::polar_G(kind, q0, q1, G);
+    for (int n = 0; n < 2; n++)
+        for (int i = 0; i < m; i++)
+            for (int j = 0; j < 3; j++) e->jacobians[n]->data[i * 3 + j] = G[2 * i] * Jx[n][j] + G[2 * i + 1] * Jx[n][3 + j];
+    asam::polar_residual(kind, f->u.common.z, q0, q1, e->r);
+    e->length = m;
+    memcpy(e->W->data, f->u.common.W->data, sizeof(double) * (size_t)m * m);
+    e->chi2 = asam::polar_cost(kind, f->u.common.z, f->u.common.W->data, q0, q1);
+    return e;
+}
+april_graph_factor_eval_t *polar_eval(april_graph_factor_t *f, april_graph_t *g, april_graph_factor_eval_t *e) { return polar_eval_at(f, g, e, false); }
+april_graph_factor_eval_t *polar_state_eval(april_graph_factor_t *f, april_graph_t *g, april_graph_factor_eval_t *e) { return polar_eval_at(f, g, e, true); }
+void polar_destroy(april_graph_factor_t *f) {
+    delete own_polar(f);
+    free(f->nodes); free(f->u.common.z); free(f->u.common.ztruth); free(f->u.common.W);
+    attr_free(f->attr);
+    free(f);
+}
+april_graph_factor_t *polar_make(int kind, int a, int b, const double *z, const double *W) {
+    const int m = asam::polar_rows(kind);
+    april_graph_factor_t *f = (april_graph_factor_t *)calloc(1, sizeof(april_graph_factor_t));
+    f->type = APRILSAM_AMD_FACTOR_POLAR_TYPE;
+    f->nnodes = 2;
+    f->nodes = (int *)calloc(2, sizeof(int));
+    f->nodes[0] = a; f->nodes[1] = b;
+    f->length = m;
+    f->u.common.z = (double *)malloc(sizeof(double) * (size_t)m);
+    memcpy(f->u.common.z, z, sizeof(double) * (size_t)m);
+    f->u.common.W = matd_new(m, m, W);
+    PolarBlock *blk = new PolarBlock(); blk->kind = kind;
+    f->u.common.impl = blk;
+    return f;
+}
+april_graph_factor_t *polar_copy(april_graph_factor_t *f) {
+    const PolarBlock *pb_ = own_polar(f);
+    if (!pb_) return nullptr;
+    april_graph_factor_t *c = polar_make(pb_->kind, f->nodes[0], f->nodes[1], f->u.common.z, f->u.common.W->data);
+    c->copy = f->copy; c->eval = f->eval; c->state_eval = f->state_eval; c->destroy = f->destroy;
+    c->attr = attr_clone(f->attr);
+    return c;
+}
+
 }  // namespace
 
 namespace asam {
@@ -308,6 +399,12 @@ double robust_host_s(const double *z, const double *w, const double *pa, const d
     return r[0] * X0 + r[1] * X1 + r[2] * X2;
 }
 
+bool polar_of(const april_graph_factor_t *f, int *kind) {
+    const PolarBlock *pb = own_polar(f);
+    if (!pb || !f->u.common.z || !f->u.common.W) return false;
+    *kind = pb->kind;
+    return true;
+}
 bool plain_common_factor(const april_graph_factor_t *f) { return is_library_common(f) && f->u.common.W && f->u.common.z; }
 bool robust_of(const april_graph_factor_t *f, int *kind, double *c) {
     const RobustBlock *rb = own_robust(f);
@@ -378,6 +475,44 @@ april_graph_factor_t *aprilsam_amd_factor_max_create(april_graph_factor_t **comp
     }
     f->copy = max_copy; f->eval = max_eval; f->state_eval = max_state_eval; f->destroy = max_destroy;
     return f;
+}
+
+april_graph_factor_t *aprilsam_amd_factor_polar_create(int kind, int a, int b, const double *z, const double *W) {
+    const char *who = "aprilsam_amd_factor_polar_create: ";
+    if (kind < APRILSAM_AMD_POLAR_RANGE || kind > APRILSAM_AMD_POLAR_RANGE_BEARING || !z || !W) {
+        asam::set_last_error(asam::ERR_BAD_GRAPH, std::string(who) + "kind " + std::to_string(kind) + " out of range (1 to 3) or a null argument");
+        return nullptr;
+    }
+    if (a == b) {
+        asam::set_last_error(asam::ERR_BAD_GRAPH, std::string(who) + "nodes (" + std::to_string(a) + ", " + std::to_string(b) + "): two different nodes are needed");
+        return nullptr;
+    }
+    const int m = asam::polar_rows(kind);
+    for (int i = 0; i < m; i++)
+        if (!std::isfinite(z[i])) { asam::set_last_error(asam::ERR_BAD_GRAPH, std::string(who) + "z is not finite"); return nullptr; }
+    if (!asam::polar_spd(kind, W)) {
+        asam::set_last_error(asam::ERR_UNSUPPORTED, std::string(who) + "W must be finite, symmetric (mirror entries bitwise equal) and positive definite");
+        return nullptr;
+    }
+    april_graph_factor_t *f = polar_make(kind, a, b, z, W);
+    f->copy = polar_copy; f->eval = polar_eval; f->state_eval = polar_state_eval; f->destroy = polar_destroy;
+    return f;
+}
+
+int aprilsam_amd_factor_get_polar(const april_graph_factor_t *f, int *kind) {
+    int k = 0;
+    if (f) (void)asam::polar_of(f, &k);
+    if (kind) *kind = k;
+    return 0;
+}
+
+int aprilsam_amd_debug_polar_slot(int kind, const double *pa, const double *pb, const double *z, const double *W, double *z_eff3, double *W_eff9) {
+    if (kind < APRILSAM_AMD_POLAR_RANGE || kind > APRILSAM_AMD_POLAR_RANGE_BEARING || !pa || !pb || !z || !W || !z_eff3 || !W_eff9) {
+        asam::set_last_error(asam::ERR_BAD_GRAPH, "aprilsam_amd_debug_polar_slot: kind out of range (1 to 3) or a null argument");
+        return asam::ERR_BAD_GRAPH;
+    }
+    asam::polar_host_slot(kind, z, W, pa, pb, z_eff3, W_eff9);
+    return 0;
 }
 
 april_graph_t *april_graph_create(void) {

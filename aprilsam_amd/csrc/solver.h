@@ -51,6 +51,7 @@ struct Options {
     int pool_guard = 0;           // debug: > 0 = every frontal array of a plan is followed by a guard band of this many doubles, NaN-filled at plan upload and checked after every synchronised step (ERR_GUARD); a stray read that is used poisons the result
     int pool_poison = 0;          // debug: 1 = before every step, the update block of every front the step (re)factorises and x at its own positions are filled with NaN: a dependency wait of a multi-level launch that passes early yields NaN instead of the previous step's numbers
     int skip_flag_waits = 0;      // debug, negative control of pool_poison: 1 = the fronts of the batch path's multi-level factorisation launch do NOT wait for their children
+    int polar_on_host = 0;        // debug: 1 = polar factors are packed as host-evaluated foreign factors through their own eval() (the A/B oracle of the native path)
     int panel_mode = 1;           // fronts too large for LDS whose own columns fit run in k_front_small's panel mode
 };
 extern Options g_opt;
@@ -125,6 +126,8 @@ int max_select(const april_graph_factor_t *f, const double *pa, const double *pb
 bool robust_of(const april_graph_factor_t *f, int *kind, double *c);
 bool plain_common_factor(const april_graph_factor_t *f);           // an xyt / xytpos factor made by this library, with its z and W in place (it may carry a loss)
 double robust_host_s(const double *z, const double *w, const double *pa, const double *pb);      // r^T W r at pa (/ pb: xyt), eval_finish's association
+// range / bearing / range-bearing factors (host_objects.cpp): true for this library's polar factor, with its kind
+bool polar_of(const april_graph_factor_t *f, int *kind);
 int robust_weights(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *factors, double *w);   // solver_calls.inc.h
 
 }  // namespace asam

@@ -65,6 +65,7 @@ static void batch_impl(april_graph_t *g, april_graph_cholesky_param_t *param) {
             if (F > gp.F_cap || gp.dirty_hi > gp.dirty_lo) upload_factors(gp);
             upload_mixture(gp);                         // (max factors appended: their components, for the step's k_select_mixture)
             upload_robust(gp);                          // (robust factors appended or edited: their table, for the step's k_robust_weight)
+            upload_polar(gp);                           // (polar factors appended or edited: their table, for the step's k_polar_slot)
             c.h_bad.need(4);
             hybrid = inc_fast_step(c, gp, N, F, c.inc_F, c.inc_N, nullptr, lam);
             reused = hybrid;
@@ -304,11 +305,13 @@ static void inc_impl(april_graph_t *g, april_graph_cholesky_param_t *param) {
     } else patch_states = pack_states_diff(gp, g);
     select_new_max(gp, g, c.inc_F);                    // new max factors: selected at their l_points as the mirror holds them, into h_z / h_W
     select_new_robust(gp, c.inc_F);                    // new robust factors: weighted at the points the mirror holds, into h_W
+    select_new_polar(gp, c.inc_F);                     // new polar factors: their xyt slots at the l_points the mirror holds, into h_z / h_W
     const double tp1 = now_ms() - (tp0b - tp0a);      // (profile: "pack" = factors + states, "model" = the bookkeeping in between)
     const double tp2 = tp1 + (tp0b - tp0a);
     if (F > gp.F_cap || !g_opt.inc_fast || !gp.host_idx.empty()) upload_factors(gp);     // (growing the device arrays re-uploads everything)
     upload_mixture(gp);
     upload_robust(gp);
+    upload_polar(gp);
     if (!gp.host_idx.empty()) {       // new foreign factors are linearised now, at the host objects' current l_points
         eval_host_factors(gp, g, gp.host_evaluated);     // (aprilsam.c:508-542); older ones keep their evaluation
         upload_host_index(gp);
@@ -551,7 +554,10 @@ static double chi2_impl(april_graph_t *g) {
             const int gi = gp.p2g[idx];
             if (gi == last) continue;                      // (the pairs of a factor with more than two nodes: one evaluation)
             last = gi;
-            april_graph_factor_eval_t *e = fs[gi]->eval ? fs[gi]->eval(fs[gi], g, nullptr) : nullptr;
+            // (debug option polar_on_host: a polar factor's term is taken at the states, where the native path's k_chi2_polar takes it)
+            int pk = 0;
+            const bool at_state = polar_of(fs[gi], &pk) && fs[gi]->state_eval;
+            april_graph_factor_eval_t *e = at_state ? fs[gi]->state_eval(fs[gi], g, nullptr) : fs[gi]->eval ? fs[gi]->eval(fs[gi], g, nullptr) : nullptr;
             if (!e) fail(ERR_BAD_GRAPH, "factor %d: eval() returned no evaluation (aprilsam.h:75-89)", gi);      // (never takes the process down: errors.h)
             chi2 += e->chi2;
             april_graph_factor_eval_destroy(e);

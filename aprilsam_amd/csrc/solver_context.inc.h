@@ -169,13 +169,14 @@ struct Context {
     long long gexec_serial = 0;
     long long gexec_mx = -1;              // GraphPack::mx_gen it was captured with (max-mixture table)
     long long gexec_rb = -1;              // GraphPack::rb_gen it was captured with (robust table)
+    long long gexec_pl = -1;              // GraphPack::pl_gen it was captured with (polar table)
     // the same phase as the API call runs it: first kernel reads the caller's states from the pinned mirror, last kernel
     // writes new states / dx / pivot flag back to pinned mirrors -- one graph launch + one stream sync per call
     hipGraphExec_t gexec_api = nullptr;
-    const void *api_key[9] = {};
+    const void *api_key[10] = {};
     // Levenberg-Marquardt (solver_lm.inc.h): one iteration captured as its own graph, keyed like gexec plus the LM buffers it reads
     hipGraphExec_t gexec_lm = nullptr;
-    const void *lm_key[10] = {};
+    const void *lm_key[11] = {};
     DBuf<double> d_lm_trial, d_lm_hacc, d_lm_terms, d_lm_trace; DBuf<LmScalars> d_lm; HBuf<LmScalars> h_lm;
     // chordal initialisation (solver_chordal.inc.h): [scratch of the state update 3N][theta N][4 scalars]; the components chosen for the max factors
     DBuf<double> d_ch; HBuf<double> h_ch; DBuf<int> d_ch_sel;
@@ -746,12 +747,14 @@ static void rewind_epoch(Context &c, hipStream_t s, long long phases) {
     c.epoch_steps = phases;
 }
 
+static void enqueue_chi2_polar(GraphPack &gp, hipStream_t s);      // solver_launch.inc.h (launch_polar)
 static double device_chi2(GraphPack &gp) {     // chi^2 at d_state; synchronises the stream
     hipStream_t s = gp.stream;
     if (gp.F == 0) return 0;
     hipLaunchKernelGGL(k_chi2, dim3((gp.F + TPB - 1) / TPB), dim3(TPB), 0, s, gp.F, gp.d_fa.p, gp.d_fb.p, gp.d_z.p, gp.d_W.p, gp.d_state.p, gp.d_chi2f.p);
     enqueue_chi2_mixture(gp, s);       // (max factors: their terms selected at the states, in place -- the sums below keep their order)
     enqueue_chi2_robust(gp, s);        // (robust factors: rho(s) in place of s)
+    enqueue_chi2_polar(gp, s);         // (polar factors: r_p' Wp r_p in place of the slot's term)
     if (gp.F > REDUCE_SPLIT) {         // (the parts live behind the F_cap per-factor terms: upload_factors)
         double *parts = gp.d_chi2f.p + gp.F_cap;
         hipLaunchKernelGGL(k_reduce_parts, dim3(REDUCE_PARTS), dim3(TPB), 0, s, gp.F, gp.d_chi2f.p, parts);

@@ -187,12 +187,26 @@ static void enqueue_gnc_weight(GraphPack &gp, hipStream_t s, const double *upt) 
     launch_gnc(s, gp, k_gnc_weight, (const int *)gp.d_fa.p, (const int *)gp.d_fb.p, (const double *)gp.d_z.p, (const double *)gp.d_lp.p, (const double *)gp.d_state.p, upt, gp.d_W.p, gp.d_gc_w.p);
 }
 
+// The kernels of polar.hip.h that run one thread per polar factor of the pack: `a` is what follows the table (n, pf, pkind, pz, pW) and the
+// endpoints (fa, fb) in the kernel's arguments.  None for a pack without polar factors
+template <class K, class... Args> static void launch_polar(hipStream_t s, GraphPack &gp, K kern, const Args &...a) {
+    const int P = gp.n_polar();
+    if (P == 0) return;
+    hipLaunchKernelGGL(kern, dim3((P + TPB - 1) / TPB), dim3(TPB), 0, s, P, (const int *)gp.d_pl_f.p, (const int *)gp.d_pl_kind.p, (const double *)gp.d_pl_z.p,
+                       (const double *)gp.d_pl_W.p, (const int *)gp.d_fa.p, (const int *)gp.d_fb.p, a...);
+}
+// every linearisation of a pack with polar factors is preceded by their slots at the l_points (what k_linearize_t reads for a binary factor)
+static void enqueue_polar(GraphPack &gp, hipStream_t s) { launch_polar(s, gp, k_polar_slot, (const double *)gp.d_lp.p, gp.d_z.p, gp.d_W.p); }
+// ... and every chi^2 is followed by their true terms at the states, in place of what k_chi2 made of the slot
+static void enqueue_chi2_polar(GraphPack &gp, hipStream_t s) { launch_polar(s, gp, k_chi2_polar, (const double *)gp.d_state.p, gp.d_chi2f.p); }
+
 // what fills the contribution slots of a Gauss-Newton step: selection, robust weights, linearisation (+ the host-evaluated factors' blocks)
 static void enqueue_linearise(Context &c, GraphPack &gp, hipStream_t s, bool unary_at_lp) {
     const int F = c.plan.F;
     enqueue_select(gp, s);                           // max-mixture factors: the component selected at l_point goes into the factor's slot
     enqueue_robust(gp, s, unary_at_lp ? gp.d_upt.p : (const double *)nullptr);      // robust factors: W_eff = w(s) W0 into the factor's slot
     enqueue_gnc_weight(gp, s, unary_at_lp ? gp.d_upt.p : (const double *)nullptr);  // GNC candidates: W_eff = w_mu(s) W0
+    enqueue_polar(gp, s);                            // polar factors: z_eff, W_eff at the l_points into the factor's slot
     // (a variant of the kernel without the asymmetric-W orientation branch, for graphs that have no such factor, was measured in round 6: no
     // difference -- 0.79 ms on the 1 M lattice either way)
     auto launch = [&](auto kern) {
@@ -310,17 +324,17 @@ static void run_numeric(Context &c, GraphPack &gp, const RunArgs &r = RunArgs{})
     if (!r.io_host) a.relin = r.relin;
     const bool graph = g_opt.use_graph && !r.timing && gp.host_idx.empty();      // (host-evaluated factors: staging buffers may move)
     if (r.io_host && graph) {
-        const void *key[9] = { gp.d_state.p, gp.h_state.p, gp.h_lp.p, gp.h_dx.p, c.h_bad.p, (const void *)(size_t)gp.N, (const void *)(size_t)gp.serial, (const void *)(size_t)gp.mx_gen,
-                               (const void *)(size_t)gp.rb_gen };
+        const void *key[10] = { gp.d_state.p, gp.h_state.p, gp.h_lp.p, gp.h_dx.p, c.h_bad.p, (const void *)(size_t)gp.N, (const void *)(size_t)gp.serial, (const void *)(size_t)gp.mx_gen,
+                                (const void *)(size_t)gp.rb_gen, (const void *)(size_t)gp.pl_gen };
         // A graph is worth its capture, instantiation and destruction (0.3 ms together) only if the configuration comes back:
         // the first call with a new key -- every fall-back of an incremental run, every cold call -- enqueues its kernels directly.
         if (memcmp(key, c.api_key, sizeof(key)) != 0) { c.retire(c.gexec_api); memcpy(c.api_key, key, sizeof(key)); c.api_key_runs = 0; }
         if (c.api_key_runs++ == 0) enqueue_numeric(c, gp, s, a);
         else replay_captured(c, c.gexec_api, s, [&] { enqueue_numeric(c, gp, s, a); });
     } else if (!r.io_host && graph && !r.unary_at_lp) {
-        if (c.gexec_key != (const void *)gp.d_state.p || c.gexec_serial != gp.serial || c.gexec_mx != gp.mx_gen || c.gexec_rb != gp.rb_gen) {
+        if (c.gexec_key != (const void *)gp.d_state.p || c.gexec_serial != gp.serial || c.gexec_mx != gp.mx_gen || c.gexec_rb != gp.rb_gen || c.gexec_pl != gp.pl_gen) {
             c.retire(c.gexec);
-            c.gexec_key = (const void *)gp.d_state.p; c.gexec_serial = gp.serial; c.gexec_mx = gp.mx_gen; c.gexec_rb = gp.rb_gen;
+            c.gexec_key = (const void *)gp.d_state.p; c.gexec_serial = gp.serial; c.gexec_mx = gp.mx_gen; c.gexec_rb = gp.rb_gen; c.gexec_pl = gp.pl_gen;
         }
         replay_captured(c, c.gexec, s, [&] { enqueue_numeric(c, gp, s, a); });
     } else {

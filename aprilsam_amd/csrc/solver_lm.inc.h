@@ -43,6 +43,7 @@ static void lm_enqueue_cost(Context &c, GraphPack &gp, hipStream_t s, const doub
                            gp.d_fa.p, gp.d_fb.p, gp.d_z.p, st, terms);
     if (gp.gc_n > 0)     // (candidates of an aprilsam_amd_optimize_gnc run: rho_mu(r^T W0 r), solver_gnc.inc.h)
         launch_gnc(s, gp, k_gnc_cost, (const int *)gp.d_fa.p, (const int *)gp.d_fb.p, (const double *)gp.d_z.p, st, terms);
+    launch_polar(s, gp, k_lm_cost_polar, st, terms);      // (polar factors: r_p' Wp r_p in place of the slot's term)
     lm_reduce(s, F, terms, terms + T, out);
 }
 static void lm_enqueue_commit(Context &c, GraphPack &gp, hipStream_t s) {
@@ -71,8 +72,8 @@ static void lm_enqueue_iteration(Context &c, GraphPack &gp, hipStream_t s) {
 static void lm_run_iteration(Context &c, GraphPack &gp, hipStream_t s) {
     rewind_epoch(c, s, 1);
     if (!g_opt.use_graph) { lm_enqueue_iteration(c, gp, s); return; }
-    const void *key[10] = { gp.d_state.p, (const void *)(size_t)gp.serial, (const void *)(size_t)gp.mx_gen, (const void *)(size_t)gp.N,
-                           c.d_lm_trial.p, c.d_lm_terms.p, c.d_lm_trace.p, c.d_lm.p, (const void *)(size_t)gp.rb_gen, (const void *)(size_t)gp.gc_gen };
+    const void *key[11] = { gp.d_state.p, (const void *)(size_t)gp.serial, (const void *)(size_t)gp.mx_gen, (const void *)(size_t)gp.N,
+                           c.d_lm_trial.p, c.d_lm_terms.p, c.d_lm_trace.p, c.d_lm.p, (const void *)(size_t)gp.rb_gen, (const void *)(size_t)gp.gc_gen, (const void *)(size_t)gp.pl_gen };
     if (memcmp(key, c.lm_key, sizeof(key)) != 0) { c.retire(c.gexec_lm); memcpy(c.lm_key, key, sizeof(key)); }
     replay_captured(c, c.gexec_lm, s, [&] { lm_enqueue_iteration(c, gp, s); });
 }

@@ -86,6 +86,16 @@ struct GraphPack {
     void rb_clear() {
         if (!rb_f.empty() || rb_on_device) rb_gen++;      // (a pack that never held robust factors keeps its captured graphs)
         rb_f.clear(); rb_kind.clear(); rb_of.clear(); rb_c.clear(); rb_W0.clear(); rb_w.clear(); rb_on_device = 0; rb_dirty = false; }
+    // polar factors (polar.hip.h): per polar factor p its packed entry pl_f[p], kind pl_kind[p], measurement pl_z[2p] and
+    // information matrix pl_W[4p] (the slot of h_z / h_W holds a null placeholder until k_polar_slot or select_new_polar writes z_eff / W_eff).
+    // pl_of: per graph factor its p or -1.  pl_gen changes whenever the table's size or device addresses do: captured graphs are keyed by it
+    std::vector<int> pl_f, pl_kind, pl_of; std::vector<double> pl_z, pl_W;
+    DBuf<int> d_pl_f, d_pl_kind; DBuf<double> d_pl_z, d_pl_W; HBuf<double> pl_stage;
+    int pl_on_device = 0; bool pl_dirty = false; long long pl_gen = 0;
+    int n_polar() const { return (int)pl_f.size(); }
+    void pl_clear() {
+        if (!pl_f.empty() || pl_on_device) pl_gen++;      // (a pack that never held polar factors keeps its captured graphs)
+        pl_f.clear(); pl_kind.clear(); pl_of.clear(); pl_z.clear(); pl_W.clear(); pl_on_device = 0; pl_dirty = false; }
     // GNC candidates (gnc.hip.h): a table that exists on the device for the length of ONE aprilsam_amd_optimize_gnc
     // call -- gc_n > 0 only inside it.  d_gc_f / d_gc_W0 / d_gc_w: packed entry, plain W and last weight per candidate, d_gc_par: loss, c
     // and mu; d_gc_out / gc_stage: results and their pinned staging.  gc_gen changes with every run: captured LM iterations are keyed by it
@@ -104,6 +114,7 @@ struct GraphPack {
         d_chi2f.release(); d_scalar.release(); h_scalar.release(); h_hostH.release(); d_hostH.release(); d_host_idx.release(); d_upt.release();
         d_mx_f.release(); d_mx_k.release(); d_sel.release(); d_mx_z.release(); d_mx_W.release(); d_mx_c.release(); mx_stage.release(); mx_clear();
         d_rb_f.release(); d_rb_kind.release(); d_rb_c.release(); d_rb_W0.release(); d_rb_w.release(); rb_stage.release(); rb_clear();
+        d_pl_f.release(); d_pl_kind.release(); d_pl_z.release(); d_pl_W.release(); pl_stage.release(); pl_clear();
         d_gc_f.release(); d_gc_W0.release(); d_gc_w.release(); d_gc_out.release(); d_gc_par.release(); gc_stage.release(); gc_n = 0;
         if (stream) { forget_stream(stream); park_stream(slot, stream); }
         stream = nullptr;
@@ -176,19 +187,26 @@ static void pack_factors(GraphPack &gp, const april_graph_t *g, bool validate_ol
     // (incremental calls only ever look at the factors added since the previous call, aprilsam.c:508-511: first and last packed pointer
     // as a sanity check instead of all of them -- the comparison of 5 000 pointers was a microsecond of every step)
     if (valid && trust) valid = from == 0 || (validate_old ? memcmp(gp.fptr.data(), fs, sizeof(void *) * from) == 0 : (gp.fptr[0] == fs[0] && gp.fptr[from - 1] == fs[from - 1]));
-    auto restart = [&]() { gp.topo_version++; from = 0; gp.F = 0; gp.F_on_device = 0; gp.host_idx.clear(); gp.host_evaluated = 0; gp.is_host.clear(); gp.p2g.clear(); gp.vslot.clear(); gp.g2p.assign(1, 0); gp.asym.clear(); gp.n_asym = 0; gp.mx_clear(); gp.rb_clear(); };
+    auto restart = [&]() { gp.topo_version++; from = 0; gp.F = 0; gp.F_on_device = 0; gp.host_idx.clear(); gp.host_evaluated = 0; gp.is_host.clear(); gp.p2g.clear(); gp.vslot.clear(); gp.g2p.assign(1, 0); gp.asym.clear(); gp.n_asym = 0; gp.mx_clear(); gp.rb_clear(); gp.pl_clear(); };
     if (!valid) restart();
     // one graph factor -> its packed entries (a, b, host flag, node slots of a host pair, what the pair carries)
     struct Ent { int a, b; bool host; unsigned short slots; unsigned char carry; };
-    Ent ents[64]; int ne = 0; bool is_max = false, is_rb = false; int rb_kind = 0; double rb_c = 0;
+    Ent ents[64]; int ne = 0; bool is_max = false, is_rb = false, is_pl = false; int rb_kind = 0, pl_kind = 0; double rb_c = 0;
     auto classify = [&](const april_graph_factor_t *f, int i) {
-        ne = 0; is_max = false; is_rb = false;
+        ne = 0; is_max = false; is_rb = false; is_pl = false;
         if (is_native_max(f)) {        // (before anything reads u.common: u.max aliases it)
             char why[192];
             if (f->nnodes != 2 || !max_check(f, why, sizeof why)) fail(ERR_UNSUPPORTED, "factor %d: max factor: %s", i, f->nnodes != 2 ? "not binary" : why);
             ents[ne++] = Ent{ f->nodes[0], f->nodes[1], false, 0, 3 }; is_max = true;
         } else if (f->type == APRIL_GRAPH_FACTOR_XYT_TYPE && f->nnodes == 2) { ents[ne++] = Ent{ f->nodes[0], f->nodes[1], false, 0, 3 }; is_rb = robust_of(f, &rb_kind, &rb_c); }
         else if (f->type == APRIL_GRAPH_FACTOR_XYTPOS_TYPE && f->nnodes == 1) { ents[ne++] = Ent{ f->nodes[0], -1, false, 0, 3 }; is_rb = robust_of(f, &rb_kind, &rb_c); }
+        else if (!g_opt.polar_on_host && polar_of(f, &pl_kind)) {      // this library's range / bearing / range-bearing factor
+            const int m = polar_rows(pl_kind);
+            bool ok = (int)f->u.common.W->nrows == m && (int)f->u.common.W->ncols == m && polar_spd(pl_kind, f->u.common.W->data);
+            for (int k = 0; k < m && ok; k++) ok = std::isfinite(f->u.common.z[k]);     // (the constructor checked both; the caller may have edited them since)
+            if (!ok) fail(ERR_UNSUPPORTED, "factor %d: a polar factor's z must be finite and its W finite, symmetric and positive definite (DESIGN.md section 19)", i);
+            ents[ne++] = Ent{ f->nodes[0], f->nodes[1], false, 0, 3 }; is_pl = true;
+        }
         else if ((f->nnodes == 1 || f->nnodes == 2) && f->eval)       // any other type: the factor's own eval(), on the host
             ents[ne++] = Ent{ f->nodes[0], f->nnodes == 2 ? f->nodes[1] : -1, true, (unsigned short)(f->nnodes == 2 ? 1 : 0xff), 3 };
         else if (f->nnodes >= 3 && f->nnodes <= 11 && f->eval) {      // a clique of pairs (see above); 11 nodes = 55 pairs
@@ -226,6 +244,7 @@ static void pack_factors(GraphPack &gp, const april_graph_t *g, bool validate_ol
                 changed = ents[e].a != gp.h_fa.p[p0 + e] || ents[e].b != gp.h_fb.p[p0 + e] || ents[e].host != (bool)gp.is_host[p0 + e];
             if (!changed) changed = is_max != (gp.mx_of[i] >= 0) || (is_max && gp.mx_k[gp.mx_of[i] + 1] - gp.mx_k[gp.mx_of[i]] != f->u.max.nfactors);
             if (!changed) changed = is_rb != (i < (int)gp.rb_of.size() && gp.rb_of[i] >= 0);      // (a loss gained or lost: the table is packed again)
+            if (!changed) changed = is_pl != (i < (int)gp.pl_of.size() && gp.pl_of[i] >= 0) || (is_pl && gp.pl_kind[gp.pl_of[i]] != pl_kind);
             if (changed) break;
             gp.fptr[i] = f;
             if (ents[0].host) continue;
@@ -242,6 +261,15 @@ static void pack_factors(GraphPack &gp, const april_graph_t *g, bool validate_ol
                     }
                 }
                 if (edit) { gp.mx_dirty = true; lo = std::min(lo, p0); hi = std::max(hi, p0 + 1); }
+                continue;
+            }
+            if (is_pl) {               // the slot holds z_eff / W_eff: the object against the table
+                const int q = gp.pl_of[i], m = polar_rows(pl_kind);
+                double *tz = gp.pl_z.data() + (size_t)2 * q, *tW = gp.pl_W.data() + (size_t)4 * q;
+                if (memcmp(tz, f->u.common.z, (size_t)8 * m) != 0 || memcmp(tW, f->u.common.W->data, (size_t)8 * m * m) != 0) {
+                    memcpy(tz, f->u.common.z, (size_t)8 * m); memcpy(tW, f->u.common.W->data, (size_t)8 * m * m);
+                    gp.pl_dirty = true; lo = std::min(lo, p0); hi = std::max(hi, p0 + 1);
+                }
                 continue;
             }
             double *zp = gp.h_z.p + (size_t)3 * p0, *Wp = gp.h_W.p + (size_t)9 * p0;
@@ -268,7 +296,7 @@ static void pack_factors(GraphPack &gp, const april_graph_t *g, bool validate_ol
             gp.content_version++;
         }
     }
-    gp.fptr.resize(Fg); gp.g2p.resize((size_t)Fg + 1); gp.mx_of.resize(Fg, -1); gp.rb_of.resize(Fg, -1);
+    gp.fptr.resize(Fg); gp.g2p.resize((size_t)Fg + 1); gp.mx_of.resize(Fg, -1); gp.rb_of.resize(Fg, -1); gp.pl_of.resize(Fg, -1);
     int F = gp.g2p[from];
     {   // the pinned mirrors are sized ONCE for everything this call appends (a pinned reallocation costs a quarter of a millisecond)
         size_t total = (size_t)F;
@@ -307,6 +335,15 @@ static void pack_factors(GraphPack &gp, const april_graph_t *g, bool validate_ol
                 }
                 gp.mx_k.push_back((int)gp.mx_c.size());
                 gp.mx_gen++;
+            } else if (is_pl) {        // the slot holds a null factor (symmetric) until k_polar_slot / select_new_polar writes z_eff / W_eff
+                memset(gp.h_z.p + (size_t)3 * F, 0, 24); memset(gp.h_W.p + (size_t)9 * F, 0, 72);
+                gp.note_asym(F, gp.h_W.p + (size_t)9 * F, true);
+                const int m = polar_rows(pl_kind);
+                double tz[2] = { 0, 0 }, tW[4] = { 0, 0, 0, 0 };
+                memcpy(tz, f->u.common.z, (size_t)8 * m); memcpy(tW, f->u.common.W->data, (size_t)8 * m * m);
+                gp.pl_of[i] = gp.n_polar(); gp.pl_f.push_back(F); gp.pl_kind.push_back(pl_kind);
+                gp.pl_z.insert(gp.pl_z.end(), tz, tz + 2); gp.pl_W.insert(gp.pl_W.end(), tW, tW + 4);
+                gp.pl_gen++;
             } else {
                 memcpy(gp.h_z.p + (size_t)3 * F, f->u.common.z, 24);
                 memcpy(gp.h_W.p + (size_t)9 * F, f->u.common.W->data, 72);
@@ -459,6 +496,45 @@ static void enqueue_chi2_robust(GraphPack &gp, hipStream_t s) {
     hipLaunchKernelGGL(k_chi2_robust, dim3((R + TPB - 1) / TPB), dim3(TPB), 0, s, R, gp.d_rb_f.p, gp.d_rb_kind.p, gp.d_rb_c.p, gp.d_rb_W0.p,
                        gp.d_fa.p, gp.d_fb.p, gp.d_z.p, gp.d_state.p, gp.d_chi2f.p);
 }
+// the polar table -> device, the rule of upload_robust: what was appended since the last upload, everything after an
+// edit or a move
+static void upload_polar(GraphPack &gp) {
+    const int P = gp.n_polar();
+    if (P == 0 || (gp.pl_on_device == P && !gp.pl_dirty)) return;
+    hipStream_t s = gp.stream;
+    HIPCHECK(hipStreamSynchronize(s));       // (the pinned staging buffer is written below)
+    if ((size_t)P > gp.d_pl_f.cap || (size_t)P > gp.d_pl_kind.cap || (size_t)2 * P > gp.d_pl_z.cap || (size_t)4 * P > gp.d_pl_W.cap) {
+        const size_t cap = (size_t)P + P / 2 + 64;
+        gp.d_pl_f.need(cap); gp.d_pl_kind.need(cap); gp.d_pl_z.need(2 * cap); gp.d_pl_W.need(4 * cap);
+        gp.pl_on_device = 0; gp.pl_dirty = true; gp.pl_gen++;
+    }
+    const int q0 = gp.pl_dirty ? 0 : gp.pl_on_device;
+    // staging layout (8-byte words): z | W | f, kind (ints, packed by two)
+    const size_t n = (size_t)(P - q0);
+    gp.pl_stage.need(2 * n + 4 * n + n);
+    double *st = gp.pl_stage.p;
+    memcpy(st, gp.pl_z.data() + (size_t)2 * q0, 16 * n);
+    memcpy(st + 2 * n, gp.pl_W.data() + (size_t)4 * q0, 32 * n);
+    int *si = (int *)(st + 6 * n);
+    memcpy(si, gp.pl_f.data() + q0, 4 * n);
+    memcpy(si + n, gp.pl_kind.data() + q0, 4 * n);
+    if (n) {
+        HIPCHECK(hipMemcpyAsync(gp.d_pl_z.p + (size_t)2 * q0, st, 16 * n, hipMemcpyHostToDevice, s));
+        HIPCHECK(hipMemcpyAsync(gp.d_pl_W.p + (size_t)4 * q0, st + 2 * n, 32 * n, hipMemcpyHostToDevice, s));
+        HIPCHECK(hipMemcpyAsync(gp.d_pl_f.p + q0, si, 4 * n, hipMemcpyHostToDevice, s));
+        HIPCHECK(hipMemcpyAsync(gp.d_pl_kind.p + q0, si + n, 4 * n, hipMemcpyHostToDevice, s));
+    }
+    gp.pl_on_device = P; gp.pl_dirty = false;
+}
+// incremental steps: the slots of the polar factors packed at or after entry f_from are written on the host (polar.h, the formulas
+// k_polar_slot applies) at the l_point mirror -- the fast path uploads and linearises them as plain xyt factors
+static void select_new_polar(GraphPack &gp, int f_from) {
+    for (int q = gp.n_polar() - 1; q >= 0 && gp.pl_f[q] >= f_from; q--) {
+        const int p = gp.pl_f[q], a = gp.h_fa.p[p], b = gp.h_fb.p[p];
+        polar_host_slot(gp.pl_kind[q], gp.pl_z.data() + (size_t)2 * q, gp.pl_W.data() + (size_t)4 * q, gp.h_lp.p + (size_t)3 * a, gp.h_lp.p + (size_t)3 * b,
+                        gp.h_z.p + (size_t)3 * p, gp.h_W.p + (size_t)9 * p);
+    }
+}
 static void upload_factors(GraphPack &gp) {
     const int F = gp.F;
     if (F > gp.F_cap) {           // reallocation loses the old content: re-upload everything
@@ -485,6 +561,7 @@ static void upload_factors(GraphPack &gp) {
     gp.d_scalar.need(8); gp.h_scalar.need(8);
     upload_mixture(gp);
     upload_robust(gp);
+    upload_polar(gp);
 }
 // evaluate the host factors [from, end) through their vtable (aprilsam.c:156 calls factor->eval the same way) and form
 // (J_a^T W) J_a, (J_a^T W) J_b, (J_b^T W) J_b, (J^T W) r in the reference's association (aprilsam.c:162-187)

@@ -260,6 +260,7 @@ static int debug_stage_impl(april_graph_t *g, april_graph_cholesky_param_t *para
     HIPCHECK(hipMemcpyAsync(gp.d_lp.p, gp.d_state.p, (size_t)24 * N, hipMemcpyDeviceToDevice, s));
     enqueue_select(gp, s);
     enqueue_robust(gp, s, nullptr);
+    enqueue_polar(gp, s);
     hipLaunchKernelGGL((k_linearize_t<false>), dim3((F + TPB - 1) / TPB), dim3(TPB), 0, s, 0, F, (const int *)nullptr, gp.d_fa.p, gp.d_fb.p, gp.d_z.p, gp.d_W.p,
                        gp.d_lp.p, gp.d_state.p, c.d_swap.p, c.dp.slot_blk, c.dp.slot_rhs, c.d_H.p, c.d_bad.p, (const double *)nullptr);
     if (what == 0) {

@@ -173,6 +173,11 @@ class SolverLib:
                 d.aprilsam_amd_factor_get_robust.argtypes = [C.POINTER(abi.Factor), C.POINTER(C.c_int), C.POINTER(C.c_double)]
             if hasattr(d, "aprilsam_amd_robust_weights"):    # (defined in the HIP translation unit)
                 d.aprilsam_amd_robust_weights.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.c_int, _ip, _dp]
+            if hasattr(d, "aprilsam_amd_factor_polar_create"):
+                d.aprilsam_amd_factor_polar_create.restype = C.POINTER(abi.Factor)
+                d.aprilsam_amd_factor_polar_create.argtypes = [C.c_int, C.c_int, C.c_int, _dp, _dp]
+                d.aprilsam_amd_factor_get_polar.argtypes = [C.POINTER(abi.Factor), C.POINTER(C.c_int)]
+                d.aprilsam_amd_debug_polar_slot.argtypes = [C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]
             d.aprilsam_amd_graph_save_ex.argtypes = [C.POINTER(abi.Graph), C.c_char_p, C.c_ulonglong]
             d.aprilsam_amd_graph_load.restype = C.POINTER(abi.Graph)
             d.aprilsam_amd_graph_load.argtypes = [C.c_char_p]
@@ -247,6 +252,18 @@ class SolverLib:
 
     def new_graph(self):
         return Graph(self)
+
+    def polar_slot(self, kind, pa, pb, z, W):
+        """(z_eff [3], W_eff [3, 3]): the xyt slot of a polar factor at poses pa, pb (aprilsam_amd_debug_polar_slot: host only)"""
+        ze = np.zeros(3); We = np.zeros(9)
+        m = 2 if int(kind) == abi.POLAR_RANGE_BEARING else 1
+        zz = np.zeros(2); zz[:m] = np.asarray(z, float).ravel()[:m]
+        WW = np.zeros(4); WW[:m * m] = np.asarray(W, float).ravel()[:m * m]
+        rc = self.dll.aprilsam_amd_debug_polar_slot(int(kind), _np_d(np.ascontiguousarray(pa, float)), _np_d(np.ascontiguousarray(pb, float)),
+                                                    _np_d(zz), _np_d(WW), _np_d(ze), _np_d(We))
+        if rc != 0:
+            raise ValueError(f"aprilsam_amd_debug_polar_slot failed rc={rc}: {self.last_error()}")
+        return ze, We.reshape(3, 3)
 
     def load_graph(self, path):
         """april_graph_create_from_file (april_graph.c:398-426); None when the file cannot be read"""
@@ -379,6 +396,31 @@ class Graph:
         if rc != 0:
             raise RuntimeError(f"aprilsam_amd_robust_weights failed rc={rc}: {self.lib.last_error()}")
         return out
+
+    def make_factor_polar(self, kind, a, b, z, W):
+        """a range / bearing / range-bearing factor, a observing b (include/aprilsam_amd.h: aprilsam_amd_factor_polar_create; DESIGN.md
+        section 19), NOT added to the graph: kind one of abi.POLAR_*, z the m measurements, W their m x m information matrix (m = 2 for
+        POLAR_RANGE_BEARING, else 1).  Raises ValueError (message of the library) when refused."""
+        zz = np.ascontiguousarray(z, float).ravel(); WW = np.ascontiguousarray(W, float).ravel()
+        m = 2 if int(kind) == abi.POLAR_RANGE_BEARING else 1
+        if int(kind) in (abi.POLAR_RANGE, abi.POLAR_BEARING, abi.POLAR_RANGE_BEARING) and (len(zz) != m or len(WW) != m * m):
+            raise ValueError(f"kind {kind} takes {m} measurements and an {m} x {m} W")
+        f = self.lib.dll.aprilsam_amd_factor_polar_create(int(kind), int(a), int(b), _np_d(zz), _np_d(WW))
+        if not f:
+            code, msg = self.lib.last_error()
+            raise ValueError(f"aprilsam_amd_factor_polar_create refused its arguments ({code}): {msg}")
+        return f
+
+    def add_factor_polar(self, kind, a, b, z, W):
+        """append a polar factor (make_factor_polar); returns its factor index"""
+        self.lib._add_factor(self.ptr, self.make_factor_polar(kind, a, b, z, W))
+        return self.n_factors - 1
+
+    def get_polar(self, i):
+        """kind of factor i when it is a polar factor of this library, 0 for any other factor"""
+        k = C.c_int(-1)
+        self.lib.dll.aprilsam_amd_factor_get_polar(self.factor_ptr(i), C.byref(k))
+        return k.value
 
     def add_factor_xytpos(self, a, z, W):
         zz = (C.c_double * 3)(*z)

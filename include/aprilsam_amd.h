@@ -372,7 +372,9 @@ void aprilsam_amd_clear_error(void);
  *                       numbers (which are the right ones whenever the previous step solved the same system: the mask that hid round 5's
  *                       release defect from everything but a soak).  Costs one extra pass over the fronts.  0 = off (default)
  *   "skip_flag_waits"   debug, 1: the fronts of the batch path's multi-level factorisation launch do NOT wait for their children -- the negative
- *                       control of "pool_poison" (the result must then come back NaN / not positive definite).  0 = off (default) */
+ *                       control of "pool_poison" (the result must then come back NaN / not positive definite).  0 = off (default)
+ *   "polar_on_host"     debug, 1: range / bearing / range-bearing factors are packed as host-evaluated foreign
+ *                       factors through their own eval() instead of natively -- the A/B oracle of the native path.  0 = off (default) */
 int aprilsam_amd_set_option(const char *name, double value);
 /* debug, with option "pool_guard" on and after a step on this param: points the guard check at a band inside a live frontal array; returns
  * -16 (the check works), -1 when the param has no guarded plan.  The param's cached plan is dropped, as after any failure */
@@ -634,6 +636,42 @@ int aprilsam_amd_factor_get_robust(const april_graph_factor_t *factor, int *kind
 /* for each listed graph factor: the weight its most recent linearisation used; -1 for a non-robust factor or one not yet linearised.
  * Returns 0 or -13 (an index out of range or a bad argument) */
 int aprilsam_amd_robust_weights(april_graph_t *graph, april_graph_cholesky_param_t *param, int n, const int *factors, double *w);
+
+/* ---- range, bearing and range-bearing factors ------------------------------------------------------------------
+ * Measurements whose noise is Gaussian in POLAR coordinates: UWB or sonar ranges, a camera's bearing to a tag, the range-bearing
+ * observation of a landmark.  Node a observes node b.  With q the position of b in a's frame (what an xyt factor predicts as its first
+ * two components), rho = |q| and beta = atan2(q1, q0):
+ *     RANGE          z = {rho}          W = {w}
+ *     BEARING        z = {beta}         W = {w}
+ *     RANGE_BEARING  z = {rho, beta}    W 2 x 2 row-major
+ * The residual is z - h(q), its bearing component wrapped with mod2pi; b's heading never enters.  W must be finite, symmetric (mirror
+ * entries bitwise equal) and positive definite, z finite, a != b.
+ * The object is a valid reference factor: nnodes = 2, length = m (1 or 2), u.common.z holds m doubles, u.common.W is an m x m matd;
+ * eval / state_eval return the true m-row r, J, W and chi2 = r' W r at l_point / state; copy is deep.  april_graph_chi2 and
+ * aprilsam_amd_resident_chi2 count the full r' W r (the reference's rule for every type but xyt, april_graph.c:86-94), at the states;
+ * the LM objective counts the same.
+ * Wherever the solver linearises the factor -- batch, resident, LM and GNC steps on the GPU, every fall-back of an incremental run -- a
+ * kernel writes the xyt slot  W_eff = [[G' W G, 0], [0, 0]],  z_eff = (q + G' (G G')^-1 r, zh2)  with G = dh/dq at the linearisation
+ * point, and the factor is linearised as that xyt factor: its contribution to the normal equations is exactly J' W J and J' W r of the
+ * m-row factor.  An incremental fast step writes a NEW factor's slot on the host when it first linearises it.  If rho^2 == 0 at the
+ * linearisation point the factor is silent for that step (W_eff = 0); there is no threshold, a tiny non-zero rho keeps its 1 / rho
+ * Jacobian.  A non-finite input fails the call as a plain factor that went non-finite does.
+ * A LANDMARK is an ordinary xyt node, and nothing observes its heading: give it param->tikhanov > 0 (the default), LM's damping, or an
+ * xytpos prior with W = diag(0, 0, w) -- otherwise the system is singular in that heading.  april_graph_cholesky_inc puts no tikhanov term
+ * on the nodes it adds (aprilsam.c:508-542): a landmark that arrives in an incremental step needs the prior.
+ * A factor is native only if type == APRILSAM_AMD_FACTOR_POLAR_TYPE AND its eval is this library's: a foreign factor that uses tag 4 keeps
+ * the host-evaluated path.  Not supported, refused with -12: a robust loss on a polar factor, a polar factor as a max component or as a
+ * GNC candidate, aprilsam_amd_initialize_chordal on a graph that holds one (it carries no relative heading), sharded params; .graph files
+ * cannot hold them (save returns 0 and writes nothing).  Debug option "polar_on_host" = 1 packs polar factors as host-evaluated foreign
+ * factors through their own eval() (the A/B oracle of the tests; april_graph_chi2 then takes their term from state_eval). */
+enum { APRILSAM_AMD_POLAR_RANGE = 1, APRILSAM_AMD_POLAR_BEARING = 2, APRILSAM_AMD_POLAR_RANGE_BEARING = 3 };
+#define APRILSAM_AMD_FACTOR_POLAR_TYPE 4
+/* copies z and W; NULL (+ aprilsam_amd_last_error: -12 for W, -13 otherwise) on a bad argument, owning nothing then */
+april_graph_factor_t *aprilsam_amd_factor_polar_create(int kind, int a, int b, const double *z, const double *W);
+int aprilsam_amd_factor_get_polar(const april_graph_factor_t *factor, int *kind);      /* 0 for any other factor */
+/* debug, host only, no device: the slot (z_eff: 3, W_eff: 9 row-major) of a polar factor at poses pa, pb -- the formulas host and kernels
+ * share.  0, or -13 on a bad argument */
+int aprilsam_amd_debug_polar_slot(int kind, const double *pa, const double *pb, const double *z, const double *W, double *z_eff3, double *W_eff9);
 
 /* ---- graduated non-convexity: outlier-robust optimisation (Yang et al., RA-L 2020) ---------------------------
  * The robust losses above are non-convex and help only from a start near the optimum.  aprilsam_amd_optimize_gnc optimises a sequence of
