@@ -179,6 +179,25 @@ int aprilsam_amd_xcd_place(int nF, const int *parent, const int *level, const in
     return (int)v.size();
 }
 
+// The back substitution's list with level 0 inside its multi-level launch (plan.h: dn_with_leaves) for a tree whose multi-level launches start
+// at level 1.  which: 0 the level-ordered list (parents first, then level 0), 1 the XCD-placed one (the down-sweep list, then the leaf list),
+// 2 / 3 dn_with_leaves_check's code for 0 / 1
+int aprilsam_amd_persist_leaves_list(int nF, const int *parent, const int *level, const int *nsb, int cap, int cap_leaf, int which, int *out, int out_cap) {
+    if (nF < 0 || !parent || !level || !nsb || which < 0 || which > 3) return -100;
+    std::vector<int> up, leaves;
+    int top = 0;
+    for (int t = 0; t < nF; t++) top = std::max(top, level[t]);
+    for (int l = 1; l <= top; l++) for (int t = 0; t < nF; t++) if (level[t] == l) up.push_back(t);
+    for (int t = 0; t < nF; t++) if (level[t] == 0) leaves.push_back(t);
+    const bool placed = which % 2 == 1;
+    std::vector<int> dn(up.rbegin(), up.rend()), leaf(leaves);
+    if (placed) { asam::XcdLists x = asam::xcd_place(up, leaves, parent, nsb, nF, cap, cap_leaf); dn.swap(x.dn); leaf.swap(x.leaf); }
+    const std::vector<int> v = asam::dn_with_leaves(dn, leaf);
+    if (which >= 2) return asam::dn_with_leaves_check(v, dn, leaf, parent, nF, placed);
+    if (out) for (int i = 0; i < (int)v.size() && i < out_cap; i++) out[i] = v[i];
+    return (int)v.size();
+}
+
 long long aprilsam_amd_plan_query(const aprilsam_amd_plan_t *plan, const char *what, long long **out) {
     std::string k(what);
     if (k.compare(0, 3, "bd_") == 0 || k.compare(0, 3, "rd_") == 0) asam::build_gather_lists(const_cast<asam::Plan &>(plan->P));

@@ -97,6 +97,12 @@ struct XcdLists { std::vector<int> up, dn, leaf; };
 XcdLists xcd_place(const std::vector<int> &up, const std::vector<int> &leaves, const int *parent, const int *nsb, int nF, int cap, int cap_leaf);
 // 0, or a negative code naming the first violated invariant (permutation plus padding, dependencies at lower ids, classes within cap)
 int xcd_check(const XcdLists &x, const std::vector<int> &up, const std::vector<int> &leaves, const int *parent, int nF, int cap, int cap_leaf);
+// The back substitution's list when level 0 joins its multi-level launch (option persist_leaves): `dn` (parents first: XcdLists::dn, or the
+// level-ordered list) followed by `leaf` (XcdLists::leaf, or level 0's list).  The upper fronts keep their workgroup ids, and -- both placed lists
+// being whole multiples of 8 slots -- every leaf keeps the class it has in its own list, beside its parent's.
+std::vector<int> dn_with_leaves(const std::vector<int> &dn, const std::vector<int> &leaf);
+// 0, or a negative code: `list` is dn's slots unchanged, then exactly leaf's fronts, every parent at a lower id, (placed) classes as in dn / leaf
+int dn_with_leaves_check(const std::vector<int> &list, const std::vector<int> &dn, const std::vector<int> &leaf, const int *parent, int nF, bool placed);
 
 // ---- pieces, exposed for tests --------------------------------------------------------------------------
 struct NDTree {

@@ -154,6 +154,7 @@ struct Context {
     // of fronts, run as ONE launch for the factorisation and ONE for the back substitution, fronts waiting on per-front
     // dependency flags instead of on kernel boundaries (kernels.hip.h: wait_flag / publish_flag)
     int persist_l0 = -1;                  // first level of the multi-level launch, -1: none
+    int persist_dn_l0 = -1;               // ... of the back substitution's: persist_l0, or 0 where level 0 joins that launch alone (option persist_leaves; upload_plan)
     int p_up_off = 0, p_up_n = 0, p_dn_off = 0, p_dn_n = 0, p_nt = 1024; size_t p_up_lds = 0, p_dn_lds = 0; long long p_up_full = 0; int p_dn_maxns = 0, p_dn_maxnu = 0;      // (p_dn_maxnu: tallest update block, rows, of the back substitution's list)
     int x_up_off = 0, x_up_n = 0, x_dn_off = 0, x_dn_n = 0;      // the same two lists in XCD-placed order (option xcd_place; x_up_n = 0: not placed)
     int x_leaf_off = 0, x_leaf_n = 0;                           // ... and level 0's fronts for its two launches (x_leaf_n = 0: level 0 keeps its own list)
@@ -631,6 +632,24 @@ static void upload_plan(Context &c, hipStream_t s, const ShardLayout *lay = null
             for (int l = P.nLevels - 1; l >= l0; l--) { const LevelPlan &L = c.levels[l]; for (int k = 0; k < L.n_all; k++) tab.push_back(tab[L.all_off + k]); }
         }
     }
+    // The back substitution's launch takes level 0 in as well (option persist_leaves, bit 0) where only the count stopped the walk above it:
+    // level 0 holds single-workgroup fronts only, the launch still fits the LDS with them, and every front keeps the kernel it runs today
+    // (k_backsolve_w for the launch and for level 0's own launch, or wave_backsolve = 0), so that the result keeps its bits.  The leaves then
+    // wait for their parents' granules with their L panel already in LDS instead of behind a kernel boundary.  Their workgroups follow the
+    // upper fronts': every parent keeps a lower id.
+    c.persist_dn_l0 = c.persist_l0;
+    if (c.persist_l0 == 1 && (g_opt.persist_leaves & 1)) {
+        const LevelPlan &L0 = c.levels[0];
+        const bool small_only = L0.n_big == 0 && L0.bs_gemv.grid == 0 && L0.bs_blk.grid == 0 && L0.n_small == L0.n_all;
+        const bool same_kernel = !g_opt.wave_backsolve || (c.p_dn_maxns <= BSW_MAX_NS && L0.n_all < g_opt.tp_fronts && L0.maxns <= BSW_MAX_NS && L0.solve_w_lds <= 80 * 1024);
+        size_t lds = c.p_dn_lds; int maxns = c.p_dn_maxns, maxnu = c.p_dn_maxnu;
+        for (int k = 0; k < L0.n_all; k++) { const int t = tab[L0.all_off + k]; lds = std::max(lds, backsolve_lds(P.cols(t), 3 * P.f_nsb[t], true)); maxns = std::max(maxns, 3 * P.f_nsb[t]); maxnu = std::max(maxnu, P.cols(t) - 3 * P.f_nsb[t]); }
+        if (small_only && same_kernel && lds <= 160 * 1024) {
+            c.persist_dn_l0 = 0; c.p_dn_lds = lds; c.p_dn_maxns = maxns; c.p_dn_maxnu = maxnu;
+            for (int k = 0; k < L0.n_all; k++) tab.push_back(tab[L0.all_off + k]);
+            c.p_dn_n += L0.n_all;
+        }
+    }
     c.x_up_n = c.x_dn_n = c.x_leaf_n = 0;
     if (c.persist_l0 >= 0 && g_opt.xcd_place) {
         // XCD-placed copies of the multi-level lists (plan.h: xcd_place), and of level 0's when it is the one launch below them and holds
@@ -648,7 +667,9 @@ static void upload_plan(Context &c, hipStream_t s, const ShardLayout *lay = null
         const int cap = per_xcd * per_cu(c.p_up_lds, c.p_nt), cap_leaf = per_xcd * (((int)leaves.size() + 8 * per_xcd - 1) / (8 * per_xcd));
         const XcdLists x = xcd_place(up, leaves, P.f_parent.data(), P.f_nsb.data(), P.nF, cap, cap_leaf);
         c.x_up_off = (int)tab.size(); c.x_up_n = (int)x.up.size(); tab.insert(tab.end(), x.up.begin(), x.up.end());
-        c.x_dn_off = (int)tab.size(); c.x_dn_n = (int)x.dn.size(); tab.insert(tab.end(), x.dn.begin(), x.dn.end());
+        // (level 0 inside the back substitution's launch: its placed list follows the upper fronts' slots there; x.leaf stays the factorisation's)
+        const std::vector<int> dn = c.persist_dn_l0 < c.persist_l0 ? dn_with_leaves(x.dn, x.leaf) : x.dn;
+        c.x_dn_off = (int)tab.size(); c.x_dn_n = (int)dn.size(); tab.insert(tab.end(), dn.begin(), dn.end());
         c.x_leaf_off = (int)tab.size(); c.x_leaf_n = (int)x.leaf.size(); tab.insert(tab.end(), x.leaf.begin(), x.leaf.end());
     }
     // (dependency flags / front levels: also used by the extended-plan batch step, whose tail fronts get levels of their own)

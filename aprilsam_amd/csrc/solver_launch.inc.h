@@ -259,14 +259,15 @@ static void enqueue_numeric(Context &c, GraphPack &gp, hipStream_t s, const Nume
     // the state update of a front's own poses rides on its back substitution (no kernel of its own); the last launch also
     // mirrors the pivot flag for the API call
     UpdArgs upd{ c.d_perm.p, gp.d_lp.p, a.st_dest ? a.st_dest : gp.d_state.p, gp.d_dx.p, io_host ? gp.h_lp.p : nullptr, io_host ? gp.h_dx.p : nullptr, nullptr, a.relin ? gp.d_lp.p : nullptr };
+    const int dl0 = l0 < P.nLevels ? c.persist_dn_l0 : l0;              // ... the back substitution's may hold level 0 as well (option persist_leaves)
     if (l0 < P.nLevels) {
-        UpdArgs u = upd; if (l0 == 0) u.bad_out = io_host ? c.h_bad.p : nullptr;
+        UpdArgs u = upd; if (dl0 == 0) u.bad_out = io_host ? c.h_bad.p : nullptr;
         kt.tic(K_BACKSOLVE);
         const bool xp = c.x_dn_n > 0;                            // the XCD-placed list (empty slots included)
         launch_backsolve_multi(c, s, persist_plan(c), c.d_tab.p + (xp ? c.x_dn_off : c.p_dn_off), xp ? c.x_dn_n : c.p_dn_n, c.p_dn_lds, c.p_dn_maxns, c.d_flags.p + c.flag_stride, u);
         kt.toc();
     }
-    for (int l = l0 - 1; l >= 0; l--) {
+    for (int l = dl0 - 1; l >= 0; l--) {
         UpdArgs u = upd; if (l == 0) u.bad_out = io_host ? c.h_bad.p : nullptr;
         kt.level = l;
         if (l == 0 && c.x_leaf_n > 0) launch_backsolve(c, c.levels[0], s, kt, nullptr, u, c.x_leaf_off, c.x_leaf_n);

@@ -513,4 +513,35 @@ int xcd_check(const XcdLists &x, const std::vector<int> &up, const std::vector<i
     return 0;
 }
 
+// ---- the back substitution's list with the leaves inside (plan.h) ------------------------------------------------------------------------
+std::vector<int> dn_with_leaves(const std::vector<int> &dn, const std::vector<int> &leaf) {
+    std::vector<int> list(dn);
+    list.insert(list.end(), leaf.begin(), leaf.end());
+    return list;
+}
+
+int dn_with_leaves_check(const std::vector<int> &list, const std::vector<int> &dn, const std::vector<int> &leaf, const int *parent, int nF, bool placed) {
+    constexpr int NX = 8;
+    if (list.size() != dn.size() + leaf.size() || (placed && (dn.size() % NX || leaf.size() % NX))) return -1;
+    if (!std::equal(dn.begin(), dn.end(), list.begin())) return -2;              // the upper fronts keep their slots
+    std::vector<int> id((size_t)nF, -1), want((size_t)nF, -1);
+    for (size_t b = 0; b < list.size(); b++) {
+        const int t = list[b];
+        if (t == -1) continue;
+        if (t < 0 || t >= nF || id[t] >= 0) return -3;                           // every front at most once
+        id[t] = (int)b;
+    }
+    for (size_t b = 0; b < dn.size(); b++) if (dn[b] >= 0) want[dn[b]] = (int)(b % NX);
+    for (size_t b = 0; b < leaf.size(); b++) if (leaf[b] >= 0) { if (leaf[b] >= nF || want[leaf[b]] >= 0) return -3; want[leaf[b]] = (int)(b % NX); }
+    for (int t = 0; t < nF; t++) {
+        if ((id[t] >= 0) != (want[t] >= 0)) return -4;                           // ... and exactly the fronts of the two lists
+        if (id[t] < 0) continue;
+        if (placed && id[t] % NX != want[t]) return -5;// one class per front, the one it has in its own list
+        const int p = parent[t];
+        if (p >= 0 && id[p] >= 0 && id[p] >= id[t]) return -6;                   // every parent below its children
+        if (p >= 0 && id[p] < 0 && id[t] >= (int)dn.size()) return -7;           // a leaf's parent is in the launch
+    }
+    return 0;
+}
+
 }  // namespace asam

@@ -345,6 +345,10 @@ void aprilsam_amd_clear_error(void);
  *   "xcd_place"         1 (default): the lists of those launches, and of the level-0 launches below them, are ordered so that a front
  *                       runs on the XCD of the child on its critical path (workgroups b and b + 8 share an XCD: observed, not promised);
  *                       speed only, results bitwise the same; 0 = level by level
+ *   "persist_leaves"    1 (default): where only "persist_max_fronts" kept level 0 out of those launches -- level 0 holds single-workgroup
+ *                       fronts only, the launch still fits the LDS with them, every front keeps its kernel -- the leaves run as the last
+ *                       workgroups of the back substitution's launch and take x from their parents inside it (M3500: one launch of 680
+ *                       fronts instead of 201 + 479); speed only, results bitwise the same; 0 = level 0 keeps its own launch
  *   "blk_backsolve"     1 (default): multi-workgroup fronts are back-substituted 128 columns at a time by a chain
  *                       workgroup + helper workgroups, with the inverse diagonal blocks the factorisation left behind; 0 = one
  *                       workgroup per front, 32 columns at a time
@@ -802,6 +806,10 @@ long long aprilsam_amd_shard_plan(const aprilsam_amd_plan_t *plan, int world, in
  * of levels >= l0 (and, when l0 == 1, the level-0 leaves) as padded workgroup lists, -1 = empty slot.  which: 0 up-sweep list,
  * 1 down-sweep list, 2 leaf list (returns the length; fills out up to out_cap), 3 the self-check (0 or a negative code); host logic only. */
 int aprilsam_amd_xcd_place(int nF, const int *parent, const int *level, const int *nsb, int l0, int cap, int cap_leaf, int which, int *out, int out_cap);
+/* The same tree's back substitution list when level 0 joins the multi-level launch that starts at level 1 (option "persist_leaves"): the
+ * upper fronts' slots unchanged, then the leaves.  which: 0 level order, 1 XCD-placed (down-sweep list, then leaf list), 2 / 3 the self-check of
+ * 0 / 1 (0 or a negative code); host logic only. */
+int aprilsam_amd_persist_leaves_list(int nF, const int *parent, const int *level, const int *nsb, int cap, int cap_leaf, int which, int *out, int out_cap);
 void aprilsam_amd_free(void *p);
 
 /* Host logic behind the incremental path: the reference's elimination order (aprilsam.c:999-1249, restated

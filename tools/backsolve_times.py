@@ -5,7 +5,9 @@ then the hand-over of x inside the multi-level launch, per level for the front t
 to its own "parent seen" (slot 4), split at the parent's stamps "last x store issued" (14), "stores drained, barrier passed" (11) and
 "flag store issued" (15).  APRILSAM_AMD_TAGGED_X selects the hand-over (option tagged_x): with granules (1) there is no flag, slot 4 is
 taken when the lanes start polling their own granules and slots 14 / 15 when the granule stores are issued -- compare the hop, parent's
-chain end to child's gather end (slot 5), which means the same in every form."""
+chain end to child's gather end (slot 5), which means the same in every form.  Level 0 is the NEXT launch (its hop holds a kernel boundary)
+unless the plan took it into the multi-level launch (option persist_leaves, APRILSAM_AMD_PERSIST_LEAVES=0 / 1: stats dn_launch_fronts then
+counts every front); the last line gives the sweep's tail, from the last level-1 front's chain end to the last leaf's."""
 import ctypes as C, os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -18,6 +20,7 @@ g = lib.new_graph(); g.build_from_arrays(*arr); p = lib.new_param()
 lib.set_option("use_graph", 0)
 for _ in range(3): g.cholesky(p)
 nF = p.stats()["n_fronts"]
+dn_fronts = p.stats()["dn_launch_fronts"]
 buf = np.zeros((nF, 16), np.int64)
 lib.dll.aprilsam_amd_debug_front_times(p.ptr, buf.ctypes.data_as(C.POINTER(C.c_longlong)), nF)
 P = PlanView(lib, len(arr[0]), arr[1], arr[2], xy=arr[0][:, :2], leaf_nodes=16)
@@ -58,3 +61,6 @@ if lv:
         print(f"{l:5d} {len(lv[l]):6d} | {row[0]:6.2f} = {row[1]:5.2f} + {row[2]:5.2f} + {row[3]:5.2f} + {row[4]:5.2f} | {row[5]:5.2f} | {row[6]:6.2f} | {med:6.2f}")
     n = len(lv)
     print(f" mean        | {tot[0]/n:6.2f} = {tot[1]/n:5.2f} + {tot[2]/n:5.2f} + {tot[3]/n:5.2f} + {tot[4]/n:5.2f} | {tot[5]/n:5.2f} | {tot[6]/n:6.2f} |   sum of hops {tot[6]:.2f}")
+    if 0 in lv and 1 in lv:
+        tail = (max(buf[t, 7] for t in lv[0]) - max(buf[t, 7] for t in lv[1])) * 0.01
+        print(f"level 0 runs {'inside the multi-level launch' if dn_fronts == nF else 'as the NEXT launch'} ({dn_fronts} fronts in the launch): last leaf's chain end {tail:.2f} us after the last level-1 front's")
