@@ -198,6 +198,19 @@ int aprilsam_amd_persist_leaves_list(int nF, const int *parent, const int *level
     return (int)v.size();
 }
 
+// The order of the factorisation's one launch (plan.h: up_schedule) from its level-ordered list `base`.  which: 0 the list, 1 up_schedule_check's
+// code; *makespan: the model's makespan of the returned list (mode 0 / 1 return base: the makespan of any list)
+int aprilsam_amd_up_schedule(int nF, const int *parent, const int *nsb, const int *base, int n_base, int cap, int mode, int which, int *out, int out_cap, double *makespan) {
+    if (nF < 0 || !parent || !nsb || !base || n_base < 0 || cap < 1 || mode < 0 || mode > 3 || which < 0 || which > 1) return -100;
+    const std::vector<int> b(base, base + n_base);
+    for (int t : b) if (t < -1 || t >= nF) return -100;
+    const std::vector<int> v = asam::up_schedule(b, parent, nsb, nF, cap, mode);
+    if (makespan) *makespan = asam::up_makespan(v, parent, nsb, nF, cap);
+    if (which == 1) return asam::up_schedule_check(v, b, parent, nF);
+    if (out) for (int i = 0; i < (int)v.size() && i < out_cap; i++) out[i] = v[i];
+    return (int)v.size();
+}
+
 long long aprilsam_amd_plan_query(const aprilsam_amd_plan_t *plan, const char *what, long long **out) {
     std::string k(what);
     if (k.compare(0, 3, "bd_") == 0 || k.compare(0, 3, "rd_") == 0) asam::build_gather_lists(const_cast<asam::Plan &>(plan->P));

@@ -104,6 +104,21 @@ std::vector<int> dn_with_leaves(const std::vector<int> &dn, const std::vector<in
 // 0, or a negative code: `list` is dn's slots unchanged, then exactly leaf's fronts, every parent at a lower id, (placed) classes as in dn / leaf
 int dn_with_leaves_check(const std::vector<int> &list, const std::vector<int> &dn, const std::vector<int> &leaf, const int *parent, int nF, bool placed);
 
+// ---- the order of the up-sweep's launch once level 0 is inside it (option persist_up) ---------------------------------------------------
+// Dispatch follows the workgroup ids, so the ids are the schedule.  `base`: the launch's list in level order, children before parents, -1 in
+// empty slots; a front's class is its slot % 8 there and stays (one class per front in both sweeps).  mode 2: descending priority, a front's
+// priority being its remaining path to the root's end under the cost model (12 us + 0.19 us per own column with children, 4.8 us without).
+// mode 3: a list schedule on the slot model -- `cap` slots per class, a class's ids dispatched in order as its slots free, a front holding its
+// slot from dispatch to end, running its 4.3 us prelude at once and going on when its last child has ended; a front with children is emitted
+// no earlier than its last child's end minus that prelude, highest priority first.  Either order is turned into ids by xcd_place's rule (the
+// next id of the class above the class's last and above every child's), so every child keeps a lower id than its parent; the list is at most
+// 8 n slots long for n fronts.  Where the model's makespan of the result exceeds that of `base`, `base` is returned.
+std::vector<int> up_schedule(const std::vector<int> &base, const int *parent, const int *nsb, int nF, int cap, int mode);
+// 0, or a negative code: whole rounds of 8 (-1), base's fronts each once (-2) in base's classes (-3), children at lower ids (-4), at most 8 n slots (-5)
+int up_schedule_check(const std::vector<int> &list, const std::vector<int> &base, const int *parent, int nF);
+// the model's makespan (us) of any such list, -1 where a child does not precede its parent
+double up_makespan(const std::vector<int> &list, const int *parent, const int *nsb, int nF, int cap);
+
 // ---- pieces, exposed for tests --------------------------------------------------------------------------
 struct NDTree {
     struct Node { std::vector<int> verts; std::vector<int> children; };

@@ -79,7 +79,7 @@ static const OptionDef OPTION_TABLE[] = {
     { "inc_inline", &Options::inc_inline, 0, true }, { "inc_update", &Options::inc_update, 0, true }, { "inc_tail_solve", &Options::inc_tail_solve, 0, true },
     { "inc_lazy_states", &Options::inc_lazy_states, 0, true }, { "inc_replan_tall", &Options::inc_replan_tall, 0, true },
     { "speculate_factors", &Options::speculate_factors, 0, true }, { "warm_up", &Options::warm_up, 0, true }, { "pin_last", &Options::pin_last, 0, false }, { "persist", &Options::persist, 0, false },
-    { "persist_max_fronts", &Options::persist_max_fronts, 0, false }, { "xcd_place", &Options::xcd_place, 0, false }, { "persist_leaves", &Options::persist_leaves, 0, false, 1 }, { "linearize_staged_min", &Options::linearize_staged_min, 0, false },
+    { "persist_max_fronts", &Options::persist_max_fronts, 0, false }, { "xcd_place", &Options::xcd_place, 0, false }, { "persist_leaves", &Options::persist_leaves, 0, false, 1 }, { "persist_up", &Options::persist_up, 0, false, 3 }, { "linearize_staged_min", &Options::linearize_staged_min, 0, false },
     { "wave_backsolve", &Options::wave_backsolve, 0, false }, { "tagged_x", &Options::tagged_x, 0, false, 2 }, { "blk_backsolve", &Options::blk_backsolve, 0, false }, { "tail_poses", &Options::tail_poses, 8, false },
     { "batch_extend", &Options::batch_extend, 0, true }, { "extend_tail_fronts", &Options::extend_tail_fronts, 0, true }, { "mem_cap_mb", &Options::mem_cap_mb, 0, true }, { "solve_chunk_cols", &Options::solve_chunk_cols, 0, true },
     { "pool_guard", &Options::pool_guard, 0, false }, { "amalg", &Options::amalg, 0, false }, { "amalg_max", &Options::amalg_max, 1, false }, { "pool_poison", &Options::pool_poison, 0, false }, { "skip_flag_waits", &Options::skip_flag_waits, 0, false },
@@ -442,6 +442,16 @@ int selftest() {
                 if (const int rl = dn_with_leaves_check(dn_with_leaves(x.dn, x.leaf), x.dn, x.leaf, parent.data(), nF, true)) return -60 + rl;
                 const std::vector<int> dn(up.rbegin(), up.rend());
                 if (const int rl = dn_with_leaves_check(dn_with_leaves(dn, leaves), dn, leaves, parent.data(), nF, false)) return -70 + rl;
+                // ... and the factorisation's one launch in both scheduled orders (plan.h: up_schedule): base's fronts in base's classes, children at
+                // lower ids, bounded padding, and under the model never behind level order
+                std::vector<int> base(x.leaf);
+                base.insert(base.end(), x.up.begin(), x.up.end());
+                for (int mode : { 2, 3 }) {
+                    const std::vector<int> ul = up_schedule(base, parent.data(), nsb.data(), nF, cap, mode);
+                    if (const int ru = up_schedule_check(ul, base, parent.data(), nF)) return -80 + ru;
+                    const double m = up_makespan(ul, parent.data(), nsb.data(), nF, cap);
+                    if (m < 0 || m > up_makespan(base, parent.data(), nsb.data(), nF, cap)) return -86;
+                }
             }
         }
     return 0;

@@ -158,6 +158,8 @@ struct Context {
     int p_up_off = 0, p_up_n = 0, p_dn_off = 0, p_dn_n = 0, p_nt = 1024; size_t p_up_lds = 0, p_dn_lds = 0; long long p_up_full = 0; int p_dn_maxns = 0, p_dn_maxnu = 0;      // (p_dn_maxnu: tallest update block, rows, of the back substitution's list)
     int x_up_off = 0, x_up_n = 0, x_dn_off = 0, x_dn_n = 0;      // the same two lists in XCD-placed order (option xcd_place; x_up_n = 0: not placed)
     int x_leaf_off = 0, x_leaf_n = 0;                           // ... and level 0's fronts for its two launches (x_leaf_n = 0: level 0 keeps its own list)
+    int persist_up_l0 = -1;               // first level of the factorisation's multi-level launch: persist_l0, or 0 where level 0 joins that launch too (option persist_up; upload_plan)
+    int u_off = 0, u_n = 0, u_fronts = 0; // ... and the list it runs (empty slots included), in the order option persist_up asks for; u_fronts: its fronts
     DBuf<int> d_flags, d_flevel, d_perm, d_epoch, d_marks;   // d_epoch: the step counter every dependency flag carries (kernels.hip.h wait_flag); d_marks: fronts regenerated by an incremental step
     DBuf<uint4> d_xg;                     // x as epoch-tagged granules, one per entry of d_x: the hand-over inside the multi-level back substitutions (kernels.hip.h: gather_x; option tagged_x)
     int flag_stride = 0;                  // d_flags = three arrays of this many words: "factor done", "x done", "vectors ready" per front
@@ -650,8 +652,37 @@ static void upload_plan(Context &c, hipStream_t s, const ShardLayout *lay = null
             c.p_dn_n += L0.n_all;
         }
     }
+    // The factorisation's launch takes level 0 in as well (option persist_up) under the same condition: only the count stopped the walk above level
+    // 0 (small fronts only, the launch's workgroup size), the launch still fits the LDS, and NO front changes form -- the kernel picks full or panel
+    // mode per front from the launch's full_limit, so every front's answer under the joined limit must be the one its own level gives, or the
+    // result would lose its bits.  The parents then wait for their leaves' flags (DevPlan::l0 = 0) instead of a kernel boundary.
+    c.persist_up_l0 = c.persist_l0;
+    const size_t up_lds_own = c.p_up_lds;                  // (what the upper fronts' launch asks for alone: xcd_place's cap, so that its lists do not move)
+    if (c.persist_l0 == 1 && g_opt.persist_up > 0) {
+        const LevelPlan &L0 = c.levels[0];
+        const bool small_only = L0.n_big == 0 && L0.bs_gemv.grid == 0 && L0.n_small == L0.n_all && L0.small_nt == c.p_nt;
+        const size_t lds = std::max(c.p_up_lds, L0.small_lds);
+        const long long full = std::max(c.p_up_full, L0.full_limit);
+        bool same_form = true;
+        const int nw = waves_of(c.p_nt);
+        for (int l = 0; l < P.nLevels && same_form; l++)
+            for (int k = 0; k < c.levels[l].n_small && same_form; k++) {
+                const int t = tab[c.levels[l].small_off + k];
+                const long long fl = (long long)small_front_lds(P.rows(t), P.cols(t), nw);
+                same_form = (fl <= c.levels[l].full_limit) == (fl <= full);
+            }
+        if (small_only && same_form && lds <= 160 * 1024) { c.persist_up_l0 = 0; c.p_up_lds = lds; c.p_up_full = full; }
+    }
+    const bool up_joined = c.persist_up_l0 < c.persist_l0;
+    const bool up_sched = c.persist_up_l0 == 0 && g_opt.persist_up >= 2;      // (graphs that run one launch per sweep anyway get the order too)
     c.x_up_n = c.x_dn_n = c.x_leaf_n = 0;
-    if (c.persist_l0 >= 0 && g_opt.xcd_place) {
+    c.u_off = c.p_up_off; c.u_n = c.p_up_n; c.u_fronts = c.persist_l0 >= 0 ? c.p_up_n + (up_joined ? c.levels[0].n_small : 0) : 0;
+    if (up_joined && !g_opt.xcd_place && !up_sched) {      // level order, nothing placed: level 0's list, then the upper fronts'
+        c.u_off = (int)tab.size(); c.u_n = c.u_fronts;
+        for (int k = 0; k < c.levels[0].n_small; k++) tab.push_back(tab[c.levels[0].small_off + k]);
+        for (int k = 0; k < c.p_up_n; k++) tab.push_back(tab[c.p_up_off + k]);
+    }
+    if (c.persist_l0 >= 0 && (g_opt.xcd_place || up_sched)) {
         // XCD-placed copies of the multi-level lists (plan.h: xcd_place), and of level 0's when it is the one launch below them and holds
         // small fronts only (the kernels that may run it return at once on an empty slot).  Classes hold what an XCD runs at once: its
         // compute units times the workgroups per unit the launch's LDS allows.
@@ -664,13 +695,24 @@ static void upload_plan(Context &c, hipStream_t s, const ShardLayout *lay = null
         const bool leaf = c.persist_l0 == 1 && L0.n_big == 0 && L0.bs_gemv.grid == 0 && L0.bs_blk.grid == 0 && L0.n_small == L0.n_all;
         const std::vector<int> leaves = leaf ? std::vector<int>(tab.begin() + L0.small_off, tab.begin() + L0.small_off + L0.n_small) : std::vector<int>();
         // (leaves: an even share per class, rounded up to whole rounds of the XCD's units -- no class runs more rounds than before)
-        const int cap = per_xcd * per_cu(c.p_up_lds, c.p_nt), cap_leaf = per_xcd * (((int)leaves.size() + 8 * per_xcd - 1) / (8 * per_xcd));
+        const int cap = per_xcd * per_cu(up_lds_own, c.p_nt), cap_leaf = per_xcd * (((int)leaves.size() + 8 * per_xcd - 1) / (8 * per_xcd));
         const XcdLists x = xcd_place(up, leaves, P.f_parent.data(), P.f_nsb.data(), P.nF, cap, cap_leaf);
-        c.x_up_off = (int)tab.size(); c.x_up_n = (int)x.up.size(); tab.insert(tab.end(), x.up.begin(), x.up.end());
-        // (level 0 inside the back substitution's launch: its placed list follows the upper fronts' slots there; x.leaf stays the factorisation's)
-        const std::vector<int> dn = c.persist_dn_l0 < c.persist_l0 ? dn_with_leaves(x.dn, x.leaf) : x.dn;
-        c.x_dn_off = (int)tab.size(); c.x_dn_n = (int)dn.size(); tab.insert(tab.end(), dn.begin(), dn.end());
-        c.x_leaf_off = (int)tab.size(); c.x_leaf_n = (int)x.leaf.size(); tab.insert(tab.end(), x.leaf.begin(), x.leaf.end());
+        if (g_opt.xcd_place) {
+            c.x_up_off = (int)tab.size(); c.x_up_n = (int)x.up.size(); tab.insert(tab.end(), x.up.begin(), x.up.end());
+            // (level 0 inside the back substitution's launch: its placed list follows the upper fronts' slots there; x.leaf stays the factorisation's)
+            const std::vector<int> dn = c.persist_dn_l0 < c.persist_l0 ? dn_with_leaves(x.dn, x.leaf) : x.dn;
+            c.x_dn_off = (int)tab.size(); c.x_dn_n = (int)dn.size(); tab.insert(tab.end(), dn.begin(), dn.end());
+            c.x_leaf_off = (int)tab.size(); c.x_leaf_n = (int)x.leaf.size(); tab.insert(tab.end(), x.leaf.begin(), x.leaf.end());
+            if (!up_joined) { c.u_off = c.x_up_off; c.u_n = c.x_up_n; }
+        }
+        if (up_joined || up_sched) {
+            // the factorisation's one launch: the placed leaf list (whole rounds of 8: every class stays), then the upper fronts' -- level order --
+            // or that list in the order of a schedule (plan.h: up_schedule; the slots per class are what the joined launch's LDS allows)
+            std::vector<int> list(up_joined ? x.leaf : std::vector<int>());
+            list.insert(list.end(), x.up.begin(), x.up.end());
+            if (up_sched) list = up_schedule(list, P.f_parent.data(), P.f_nsb.data(), P.nF, per_xcd * per_cu(c.p_up_lds, c.p_nt), g_opt.persist_up);
+            c.u_off = (int)tab.size(); c.u_n = (int)list.size(); tab.insert(tab.end(), list.begin(), list.end());
+        }
     }
     // (dependency flags / front levels: also used by the extended-plan batch step, whose tail fronts get levels of their own)
     {
@@ -748,6 +790,7 @@ static void upload_plan(Context &c, hipStream_t s, const ShardLayout *lay = null
     if (uprof) fprintf(stderr, "aprilsam_amd upload: graphs destroyed + descriptors %.3f, index arrays + copies %.3f, launch tables %.3f, last copies + sync %.3f, pools %.3f ms\n", u1 - u0, u2 - u1, u3 - u2, u4 - u3, now_ms() - u4);
     c.st.n_fronts = P.nF; c.st.n_levels = P.nLevels; c.st.max_front_rows = P.max_rows;
     c.st.dn_launch_fronts = c.persist_l0 >= 0 ? c.p_dn_n : 0;       // fronts of the batch step's multi-level back substitution (an incremental step overwrites it with its own)
+    c.st.up_launch_fronts = c.u_fronts;                             // ... and of its multi-level factorisation (level 0 included where option persist_up joined it)
     c.st.nnz_L = P.nnzL; c.st.flops_factor = P.flops; c.st.bytes_fronts = 8.0 * (double)pool_doubles;
 }
 

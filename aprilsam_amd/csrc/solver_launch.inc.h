@@ -113,11 +113,11 @@ static void enqueue_poison(Context &c, hipStream_t s, const int *list, int n, in
     hipLaunchKernelGGL(k_poison, dim3(n), dim3(TPB), 0, s, c.dp, list, n, recs ? (const int *)((const char *)recs + offsetof(UpdRec, mode)) : (const int *)nullptr,
                        (int)(sizeof(UpdRec) / 4), what, c.d_pool.p, c.d_x.p);
 }
-// the multi-level launch of the factorisation: every small front of levels >= persist_l0
+// the multi-level launch of the factorisation: every small front of levels >= persist_up_l0, in the order upload_plan chose (empty slots included)
 static void launch_front_persist(Context &c, hipStream_t s) {
-    const bool xp = c.x_up_n > 0;                          // the XCD-placed list (empty slots included)
-    const int *list = c.d_tab.p + (xp ? c.x_up_off : c.p_up_off), n = xp ? c.x_up_n : c.p_up_n;
+    const int *list = c.d_tab.p + c.u_off, n = c.u_n;
     DevPlan dpe = persist_plan(c);
+    dpe.l0 = c.persist_up_l0;                              // (level 0 inside the launch: its parents wait for its flags)
     if (g_opt.skip_flag_waits > 0) dpe.l0 = 1 << 30;       // debug (negative control of pool_poison): no front of this launch waits for its children
     launch_front_small_nt(c.p_nt, n, c.p_up_lds, s, dpe, list, c.d_pool.p, c.d_H.p, c.d_bad.p, c.p_up_full, c.d_flags.p, 1);
 }
@@ -248,12 +248,13 @@ static void enqueue_numeric(Context &c, GraphPack &gp, hipStream_t s, const Nume
     kt.toc();
     if (a.ev) HIPCHECK(hipEventRecord(a.ev[1], s));
     const int l0 = c.persist_l0 >= 0 ? c.persist_l0 : P.nLevels;        // levels >= l0: one multi-level launch each way
-    for (int l = 0; l < l0; l++) {
+    const int ul0 = l0 < P.nLevels ? c.persist_up_l0 : l0;              // ... the factorisation's may hold level 0 as well (option persist_up)
+    for (int l = 0; l < ul0; l++) {
         kt.level = l;
         if (l == 0 && c.x_leaf_n > 0) { kt.tic(K_FRONT_SMALL); launch_front_small(c, c.levels[0], s, nullptr, c.x_leaf_off, c.x_leaf_n); kt.toc(); }      // (small fronts only)
         else enqueue_factor_level(c, c.levels[l], s, kt);
     }
-    kt.level = l0;
+    kt.level = ul0;
     if (l0 < P.nLevels) { kt.tic(K_FRONT_SMALL); launch_front_persist(c, s); kt.toc(); }
     if (a.ev) HIPCHECK(hipEventRecord(a.ev[2], s));
     // the state update of a front's own poses rides on its back substitution (no kernel of its own); the last launch also

@@ -544,4 +544,142 @@ int dn_with_leaves_check(const std::vector<int> &list, const std::vector<int> &d
     return 0;
 }
 
+// ---- the order of the up-sweep's one launch (plan.h: up_schedule) ----------------------------------------------------------------------------
+namespace {
+constexpr int UP_NX = 8;
+// us: a front with children from its last child's end to its own (amalgamate's model, as in xcd_place), a front without children from start to
+// end, and what a front with children does before it needs them (zero fill, factor blocks, work lists): profiles/persist_leaves.txt section 5
+constexpr double UP_HAND = 12.0, UP_PERCOL = 0.19, UP_LEAF = 4.8, UP_LEAD = 4.3;
+
+struct UpTree {
+    int n = 0;
+    std::vector<int> front, cls, par, first_kid, next_kid;      // per entry of `base` (its order kept): front, class, parent's entry or -1, child chain
+    std::vector<double> cost, prio;
+    UpTree(const std::vector<int> &base, const int *parent, const int *nsb, int nF) {
+        std::vector<int> at((size_t)nF, -1);
+        for (size_t b = 0; b < base.size(); b++) if (base[b] >= 0 && base[b] < nF) { at[base[b]] = (int)front.size(); front.push_back(base[b]); cls.push_back((int)(b % UP_NX)); }
+        n = (int)front.size();
+        par.assign(n, -1); first_kid.assign(n, -1); next_kid.assign(n, -1); cost.assign(n, UP_LEAF); prio.assign(n, 0.0);
+        for (int i = n - 1; i >= 0; i--) {
+            const int p = parent[front[i]] >= 0 ? at[parent[front[i]]] : -1;
+            par[i] = p;
+            if (p >= 0) { next_kid[i] = first_kid[p]; first_kid[p] = i; }
+        }
+        for (int i = 0; i < n; i++) if (first_kid[i] >= 0) cost[i] = UP_HAND + UP_PERCOL * 3.0 * (double)nsb[front[i]];
+        // remaining path to the root's end, own cost included: parents first (they follow their children in base)
+        for (int i = n - 1; i >= 0; i--) prio[i] = cost[i] + (par[i] >= 0 ? prio[par[i]] : 0.0);
+    }
+};
+// place()'s rule of xcd_place in the order `seq`: the next id 8 k + c of the front's class above the class's last one and above every child's
+std::vector<int> up_slots(const UpTree &T, const std::vector<int> &seq) {
+    std::vector<int> id(T.n, -1), dep(T.n, -1), cur(UP_NX, 0);
+    int kmax = 0;
+    for (int i : seq) {
+        const int c = T.cls[i], need = dep[i] + 1;
+        const int k = std::max(cur[c], need > c ? (need - c + UP_NX - 1) / UP_NX : 0);
+        id[i] = UP_NX * k + c; cur[c] = k + 1; kmax = std::max(kmax, k + 1);
+        if (T.par[i] >= 0) dep[T.par[i]] = std::max(dep[T.par[i]], id[i]);
+    }
+    std::vector<int> list((size_t)UP_NX * kmax, -1);
+    for (int i : seq) list[id[i]] = T.front[i];
+    return list;
+}
+struct SlotHeap {                                   // when each of a class's slots is free next
+    std::vector<double> h;
+    explicit SlotHeap(int cap) : h((size_t)std::max(cap, 1), 0.0) {}
+    double top() const { return h.front(); }
+    double second() const { return h.size() < 2 ? 1e300 : h.size() < 3 ? h[1] : std::min(h[1], h[2]); }      // when the next one frees once the first is taken
+    void replace_top(double v) { std::pop_heap(h.begin(), h.end(), std::greater<double>()); h.back() = v; std::push_heap(h.begin(), h.end(), std::greater<double>()); }
+};
+}  // namespace
+
+double up_makespan(const std::vector<int> &list, const int *parent, const int *nsb, int nF, int cap) {
+    const UpTree T(list, parent, nsb, nF);
+    std::vector<SlotHeap> slots(UP_NX, SlotHeap(cap));
+    std::vector<double> last(UP_NX, 0.0), end(T.n, -1.0);
+    double span = 0.0;
+    for (int i = 0; i < T.n; i++) {                 // (entries in the order of their ids)
+        const int c = T.cls[i];
+        const double start = std::max(last[c], slots[c].top());
+        double kids = -1.0;
+        for (int k = T.first_kid[i]; k >= 0; k = T.next_kid[k]) { if (end[k] < 0) return -1.0; kids = std::max(kids, end[k]); }
+        end[i] = T.first_kid[i] >= 0 ? std::max(start + UP_LEAD, kids) + T.cost[i] : start + T.cost[i];
+        last[c] = start; slots[c].replace_top(end[i]); span = std::max(span, end[i]);
+    }
+    return span;
+}
+
+std::vector<int> up_schedule(const std::vector<int> &base, const int *parent, const int *nsb, int nF, int cap, int mode) {
+    const UpTree T(base, parent, nsb, nF);
+    if (mode < 2 || T.n == 0 || T.n > 20000) return base;
+    std::vector<int> seq;
+    seq.reserve(T.n);
+    if (mode == 2) {
+        // descending priority: a child's path is longer than its parent's by its own cost, so every child comes first
+        for (int i = 0; i < T.n; i++) seq.push_back(i);
+        std::stable_sort(seq.begin(), seq.end(), [&](int a, int b) { return T.prio[a] > T.prio[b]; });
+    } else {
+        // list schedule on the slot model: a front is emitted at the clock when its class has a free slot, a front with children not before its
+        // last child's end minus the lead (it would only hold the slot and spin) -- unless the class frees no other slot before that time;
+        // highest priority first; nothing to emit: the clock advances
+        std::vector<SlotHeap> slots(UP_NX, SlotHeap(cap));
+        std::vector<int> left(T.n, 0), ready, dep(T.n, -1), cur(UP_NX, 0);      // (dep, cur: up_slots' rule run alongside, for the ids so far)
+        std::vector<double> kids_end(T.n, 0.0);
+        for (int i = 0; i < T.n; i++) { for (int k = T.first_kid[i]; k >= 0; k = T.next_kid[k]) left[i]++; if (!left[i]) ready.push_back(i); }
+        double clock = 0.0;
+        while ((int)seq.size() < T.n) {
+            int pick = -1; size_t where = 0;
+            bool pick_due = false;
+            double next = 1e300;
+            for (size_t r = 0; r < ready.size(); r++) {
+                const int i = ready[r], c = T.cls[i];
+                const SlotHeap &sl = slots[c];
+                // a front with children whose class has handed out a round of slots since its last child: the model's clock is a model, the ids
+                // are what the hardware follows -- it goes before anything else, no more than a round behind that child
+                const bool due = T.first_kid[i] >= 0 && UP_NX * (cur[c] + 1) + c > dep[i] + UP_NX * std::max(cap, 1);
+                double from = T.first_kid[i] >= 0 && !due ? kids_end[i] - UP_LEAD : 0.0;
+                if (from > clock && sl.second() > from) from = clock;      // (no other slot of its class frees before then: this one, or its prelude lands on the path)
+                from = std::max(from, sl.top());
+                if (from > clock) { next = std::min(next, from); continue; }
+                if (pick < 0 || (due && !pick_due) || (due == pick_due && (T.prio[i] > T.prio[pick] || (T.prio[i] == T.prio[pick] && i < pick)))) { pick = i; where = r; pick_due = due; }
+            }
+            if (pick < 0) { clock = next; continue; }
+            const double end = T.first_kid[pick] >= 0 ? std::max(clock + UP_LEAD, kids_end[pick]) + T.cost[pick] : clock + T.cost[pick];
+            const int c = T.cls[pick], need = dep[pick] + 1, k = std::max(cur[c], need > c ? (need - c + UP_NX - 1) / UP_NX : 0);
+            cur[c] = k + 1;
+            slots[c].replace_top(end);
+            seq.push_back(pick);
+            ready[where] = ready.back(); ready.pop_back();
+            const int p = T.par[pick];
+            if (p >= 0) { dep[p] = std::max(dep[p], UP_NX * k + c); kids_end[p] = std::max(kids_end[p], end); if (--left[p] == 0) ready.push_back(p); }
+        }
+    }
+    std::vector<int> list = up_slots(T, seq);
+    // never behind level order under the model (a list schedule carries no such promise of its own)
+    if (up_makespan(list, parent, nsb, nF, cap) > up_makespan(base, parent, nsb, nF, cap)) return base;
+    return list;
+}
+
+int up_schedule_check(const std::vector<int> &list, const std::vector<int> &base, const int *parent, int nF) {
+    if (list.size() % UP_NX) return -1;
+    std::vector<int> id((size_t)nF, -1), want((size_t)nF, -1);
+    size_t n = 0, nb = 0;
+    for (size_t b = 0; b < base.size(); b++) if (base[b] >= 0 && base[b] < nF) { want[base[b]] = (int)(b % UP_NX); nb++; }
+    for (size_t b = 0; b < list.size(); b++) {
+        const int t = list[b];
+        if (t == -1) continue;
+        if (t < 0 || t >= nF || id[t] >= 0 || want[t] < 0) return -2;            // exactly base's fronts, each once
+        id[t] = (int)b; n++;
+    }
+    if (n != nb) return -2;
+    for (int t = 0; t < nF; t++) {
+        if (id[t] < 0) continue;
+        if (id[t] % UP_NX != want[t]) return -3;                                // the class it was given
+        const int p = parent[t];
+        if (p >= 0 && id[p] >= 0 && id[t] >= id[p]) return -4;                   // every child below its parent
+    }
+    if (list.size() > (size_t)UP_NX * std::max<size_t>(n, 1)) return -5;         // the k-th front emitted lies in round k at the latest
+    return 0;
+}
+
 }  // namespace asam

@@ -243,6 +243,7 @@ typedef struct aprilsam_amd_stats {
     int    inc_fronts_updated; /* fronts whose factor took a low-rank update in this step (option "inc_update") instead of being re-assembled and
                                   re-factorised; reserved0 counts all fronts the step regenerated */
     int    dn_launch_fronts;   /* fronts in the step's multi-level back substitution launch (one workgroup each, x handed from parent to child inside the launch), 0: none */
+    int    up_launch_fronts;   /* fronts in the batch step's multi-level factorisation launch (level 0 included where option "persist_up" joined it), 0: none */
 } aprilsam_amd_stats_t;
 int aprilsam_amd_get_stats(const april_graph_cholesky_param_t *param, aprilsam_amd_stats_t *out);
 
@@ -349,6 +350,12 @@ void aprilsam_amd_clear_error(void);
  *                       fronts only, the launch still fits the LDS with them, every front keeps its kernel -- the leaves run as the last
  *                       workgroups of the back substitution's launch and take x from their parents inside it (M3500: one launch of 680
  *                       fronts instead of 201 + 479); speed only, results bitwise the same; 0 = level 0 keeps its own launch
+ *   "persist_up"        the factorisation's half of the same (APRILSAM_AMD_PERSIST_UP), under the same condition and only where no front changes
+ *                       between its full-LDS and its panel form: 0 = level 0 keeps its own launch; 1 = level 0 inside the multi-level
+ *                       launch, level order; 2 (default) = ... in descending order of the remaining path to the root under a cost model
+ *                       (M3500: resident step 0.1981 -> 0.1877 ms); 3 = ... in
+ *                       the order of a list schedule that knows how many workgroups an XCD holds at once (plan.h: up_schedule).  2 and 3 also
+ *                       order the launch of graphs that run one launch per sweep anyway.  Speed only, results bitwise the same
  *   "blk_backsolve"     1 (default): multi-workgroup fronts are back-substituted 128 columns at a time by a chain
  *                       workgroup + helper workgroups, with the inverse diagonal blocks the factorisation left behind; 0 = one
  *                       workgroup per front, 32 columns at a time
@@ -810,6 +817,12 @@ int aprilsam_amd_xcd_place(int nF, const int *parent, const int *level, const in
  * upper fronts' slots unchanged, then the leaves.  which: 0 level order, 1 XCD-placed (down-sweep list, then leaf list), 2 / 3 the self-check of
  * 0 / 1 (0 or a negative code); host logic only. */
 int aprilsam_amd_persist_leaves_list(int nF, const int *parent, const int *level, const int *nsb, int cap, int cap_leaf, int which, int *out, int out_cap);
+/* The order of the factorisation's one launch (option "persist_up").  base: the launch's list in level order, children before parents, -1 in
+ * empty slots, a front's class being its slot % 8 (for a tree whose multi-level launches start at level 1: aprilsam_amd_xcd_place's leaf list
+ * followed by its up-sweep list).  mode 0 / 1: base itself, 2: descending priority, 3: the slot-aware list schedule with cap slots per class.
+ * which: 0 the list (returns the length; fills out up to out_cap), 1 the self-check of the list against base (0 or a negative code).
+ * makespan (may be NULL) receives the cost model's makespan of the returned list in us, so mode 0 gives that of any list; host logic only. */
+int aprilsam_amd_up_schedule(int nF, const int *parent, const int *nsb, const int *base, int n_base, int cap, int mode, int which, int *out, int out_cap, double *makespan);
 void aprilsam_amd_free(void *p);
 
 /* Host logic behind the incremental path: the reference's elimination order (aprilsam.c:999-1249, restated
