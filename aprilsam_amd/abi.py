@@ -139,6 +139,8 @@ class ChordalReport(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+# (fixed nodes, include/aprilsam_amd.h: aprilsam_amd_node_set_fixed / _get_fixed; DESIGN.md section 20: the flag is a tagged block on Node.impl,
+# read through the two calls only -- host.Graph.set_fixed / get_fixed)
 # robust loss kinds of xyt / xytpos factors (include/aprilsam_amd.h: aprilsam_amd_factor_set_robust)
 ROBUST_NONE, ROBUST_HUBER, ROBUST_CAUCHY, ROBUST_DCS = 0, 1, 2, 3
 

@@ -10,6 +10,7 @@
 // (max_select) is the one the incremental path applies on the host and k_select_mixture restates on the device.  Robust losses on xyt /
 // xytpos factors are kept here as well: a tagged block hung off u.common.impl, applied by eval_finish.  Range, bearing
 // and range-bearing factors (type 4) are built here: true m-row factors on the host, xyt slots on the device (polar.h).
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <string>
@@ -188,13 +189,28 @@ void node_update(april_graph_node_t *n, double *d) {             // april_graph_
     n->state[2] = mod2pi_h(n->state[2]);
 }
 void node_relinearize(april_graph_node_t *n) { memcpy(n->l_point, n->state, 24); }    // april_graph_xyt.c:316-320
+// ---- fixed nodes ----------------------------------------------------------------------
+// The reference leaves node->impl unused (NULL) on its xyt nodes.  A node held constant points it at this block; the tag tells it apart from
+// anything a foreign library might keep there, and only nodes whose destroy is this library's are looked at (the block is freed there).
+constexpr unsigned long long FIXED_TAG = 0x66697865645f6e64ULL;        // "fixed_nd"
+struct FixedBlock { unsigned long long tag = FIXED_TAG; };
+std::atomic<bool> g_fixed_ever{ false };      // set by the first FixedBlock of the process (asam::fixed_ever)
+FixedBlock *new_fixed() { g_fixed_ever.store(true, std::memory_order_relaxed); return new FixedBlock(); }
+void node_destroy(april_graph_node_t *n);
+FixedBlock *own_fixed(const april_graph_node_t *n) {
+    if (n->type != APRIL_GRAPH_NODE_XYT_TYPE || n->destroy != node_destroy) return nullptr;
+    void *p = n->impl;
+    return (p && *(const unsigned long long *)p == FIXED_TAG) ? (FixedBlock *)p : nullptr;
+}
 void node_destroy(april_graph_node_t *n) {
+    delete own_fixed(n);
     free(n->state); free(n->init); free(n->truth); free(n->l_point); free(n->delta_X); attr_free(n->attr); free(n);
 }
 april_graph_node_t *node_copy(april_graph_node_t *n) {
     april_graph_node_t *c = april_graph_node_xyt_create(n->state, n->init, n->truth);
     memcpy(c->l_point, n->l_point, 24); memcpy(c->delta_X, n->delta_X, 24);
     c->attr = attr_clone(n->attr);
+    if (own_fixed(n)) c->impl = new_fixed();
     return c;
 }
 
@@ -405,6 +421,8 @@ bool polar_of(const april_graph_factor_t *f, int *kind) {
     *kind = pb->kind;
     return true;
 }
+bool node_fixed(const april_graph_node_t *n) { return n && own_fixed(n) != nullptr; }
+bool fixed_ever() { return g_fixed_ever.load(std::memory_order_relaxed); }
 bool plain_common_factor(const april_graph_factor_t *f) { return is_library_common(f) && f->u.common.W && f->u.common.z; }
 bool robust_of(const april_graph_factor_t *f, int *kind, double *c) {
     const RobustBlock *rb = own_robust(f);
@@ -446,6 +464,28 @@ int aprilsam_amd_factor_set_robust(april_graph_factor_t *f, int kind, double c) 
     rb->kind = kind; rb->c = c;
     return 0;
 }
+
+int aprilsam_amd_node_set_fixed(april_graph_node_t *node, int fixed) {
+    const char *who = "aprilsam_amd_node_set_fixed: ";
+    if (!node) { asam::set_last_error(asam::ERR_BAD_GRAPH, std::string(who) + "null node"); return asam::ERR_BAD_GRAPH; }
+    if (fixed != 0 && fixed != 1) {
+        asam::set_last_error(asam::ERR_BAD_GRAPH, std::string(who) + "fixed = " + std::to_string(fixed) + " (0 or 1)");
+        return asam::ERR_BAD_GRAPH;
+    }
+    if (node->type != APRIL_GRAPH_NODE_XYT_TYPE || node->destroy != node_destroy) {
+        asam::set_last_error(asam::ERR_UNSUPPORTED, std::string(who) + "not an xyt node of this library");
+        return asam::ERR_UNSUPPORTED;
+    }
+    if (node->impl && !own_fixed(node)) {
+        asam::set_last_error(asam::ERR_UNSUPPORTED, std::string(who) + "node->impl is in use by another library");
+        return asam::ERR_UNSUPPORTED;
+    }
+    if (!fixed) { delete own_fixed(node); node->impl = nullptr; return 0; }
+    if (!node->impl) node->impl = new_fixed();
+    return 0;
+}
+
+int aprilsam_amd_node_get_fixed(const april_graph_node_t *node) { return asam::node_fixed(node) ? 1 : 0; }
 
 int aprilsam_amd_factor_get_robust(const april_graph_factor_t *f, int *kind, double *c) {
     int k = APRILSAM_AMD_ROBUST_NONE; double cv = 0;

@@ -130,6 +130,9 @@ bool plain_common_factor(const april_graph_factor_t *f);           // an xyt / x
 double robust_host_s(const double *z, const double *w, const double *pa, const double *pb);      // r^T W r at pa (/ pb: xyt), eval_finish's association
 // range / bearing / range-bearing factors (host_objects.cpp): true for this library's polar factor, with its kind
 bool polar_of(const april_graph_factor_t *f, int *kind);
+// fixed nodes (host_objects.cpp): true for an xyt node of this library that is held constant
+bool node_fixed(const april_graph_node_t *n);
+bool fixed_ever();                                               // false until the process fixes its first node: graphs are not walked for flags before
 int robust_weights(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *factors, double *w);   // solver_calls.inc.h
 
 }  // namespace asam

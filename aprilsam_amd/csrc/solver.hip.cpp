@@ -31,6 +31,7 @@
 #include "maxmix.hip.h"
 #include "robust.hip.h"
 #include "polar.hip.h"
+#include "fixed.hip.h"
 #include "gnc.hip.h"
 #include "lm.hip.h"
 #include "chordal.hip.h"

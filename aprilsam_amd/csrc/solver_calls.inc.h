@@ -13,6 +13,7 @@ static void batch_impl(april_graph_t *g, april_graph_cholesky_param_t *param) {
     Context &c = ctx_for(param);
     GraphPack &gp = pack_for(g);
     const double t0 = now_ms();
+    sync_fixed(gp, g);                                // (nodes fixed or freed since the last call)
     // Warm call on an unchanged graph (same factor and node counts as packed, plan and device copies current): the pass over
     // the factor objects that finds what the caller edited in place -- reference semantics: every z / W is read on every call;
     // 26 us of pointer chasing on M3500 -- runs WHILE the GPU works on the step, launched on the packed copies.  If the pass
@@ -50,7 +51,8 @@ static void batch_impl(april_graph_t *g, april_graph_cholesky_param_t *param) {
     bool hybrid = false, reused = false;
     {
         const int patF = (int)c.pat.size() / 2;
-        bool ext = g_opt.batch_extend && !timing && c.have_plan && c.inc.ready && gp.host_idx.empty() && gp.n_asym == 0 && !c.wt_any && N >= c.patN && F >= patF &&
+        // (fixed nodes: the extended plan's step linearises on its own, without the mask -- such a graph is planned again)
+        bool ext = g_opt.batch_extend && !timing && c.have_plan && c.inc.ready && gp.host_idx.empty() && gp.n_asym == 0 && !c.wt_any && gp.n_fixed() == 0 && N >= c.patN && F >= patF &&
                    c.inc_N == c.patN && c.inc_F == patF && c.plan.leaf_nodes == g_opt.leaf_nodes && c.plan_pin == g_opt.pin_last &&
                    c.plan_persist == launch_table_key();
         for (int i = 0; i < patF && ext; i++) ext = c.pat[2 * i] == gp.h_fa.p[i] && c.pat[2 * i + 1] == gp.h_fb.p[i];
@@ -75,6 +77,7 @@ static void batch_impl(april_graph_t *g, april_graph_cholesky_param_t *param) {
     if (!hybrid && speculate) {
         speculate = prepare_plan(c, gp, g);             // (true: the cached plan fits the packed pattern -- it does, by the conditions above)
         if (speculate) {
+            upload_fixed(gp);
             set_lambda(c, gp, param->tikhanov);
             t2 = t3 = now_ms();                         // (stats: the pass over the factor objects below counts as device time -- it runs under it)
             c.h_bad.p[0] = c.h_bad.p[1] = c.h_bad.p[2] = c.h_bad.p[3] = 0;
@@ -97,6 +100,7 @@ static void batch_impl(april_graph_t *g, april_graph_cholesky_param_t *param) {
         flush_orientation(c, gp.stream);
         t2 = now_ms();
         upload_factors(gp);
+        upload_fixed(gp);
         set_lambda(c, gp, param->tikhanov);
         t3 = now_ms();
         // One graph launch: k_load_states pulls the packed states from the pinned mirror (state and, every node being
@@ -254,6 +258,19 @@ struct IncProf {
 };
 static IncProf g_incprof;
 
+// The incremental entry points take no fixed nodes: not in the graph, and not in the factorisation they would extend
+// or solve with.  They are void: the refusal is aprilsam_amd_last_error's -12; nothing is written, the param keeps its plan and factor.
+static bool inc_refuse_fixed(const char *who, const april_graph_t *g, const april_graph_cholesky_param_t *param) {
+    if (!fixed_ever()) return false;
+    if (refuse_fixed(who, g)) return true;
+    auto it = g_ctx.find(param);
+    if (it == g_ctx.end() || it->second->fact_fixed.empty()) return false;
+    char msg[320];
+    snprintf(msg, sizeof msg, "%s: the factorisation at hand was made with node %d fixed; call april_graph_cholesky first (DESIGN.md section 20)", who, it->second->fact_fixed[0]);
+    set_last_error(ERR_UNSUPPORTED, msg);
+    fprintf(stderr, "aprilsam_amd: ERROR %d: %s\n", (int)ERR_UNSUPPORTED, msg); fflush(stderr);
+    return true;
+}
 static void inc_impl(april_graph_t *g, april_graph_cholesky_param_t *param);
 static void apply_visits(Context &c, GraphPack &gp, april_graph_t *g, april_graph_cholesky_param_t *param, int N);
 void inc_step(april_graph_t *g, april_graph_cholesky_param_t *param) {
@@ -267,9 +284,11 @@ static void inc_impl(april_graph_t *g, april_graph_cholesky_param_t *param) {
         if (it == g_ctx.end() || !it->second->have_fact) return;         // aprilsam.c:382-383 (no prior chol)
     }
     if (param->factor_num == zsize(g->factors)) return;                  // aprilsam.c:384-385
+    if (inc_refuse_fixed("april_graph_cholesky_inc", g, param)) return;  // (-12 through aprilsam_amd_last_error, nothing written)
     ensure_device();
     Context &c = ctx_for(param);
     GraphPack &gp = pack_for(g);
+    sync_fixed(gp, g); upload_fixed(gp);                                 // (a set left behind by an earlier call is forgotten)
     c.want_inc = true; c.used_inc = true;
     const double t0 = now_ms();
     pack_factors(gp, g, false);
@@ -504,6 +523,7 @@ void inc_solve_only(april_graph_t *g, april_graph_cholesky_param_t *param) {
         SlotLock lk(param, g);
         auto it = g_ctx.find(param);
         if (it == g_ctx.end() || !it->second->have_fact || !param->nreordering) return;        // aprilsam.c:580
+        if (inc_refuse_fixed("april_graph_cholesky_inc_solver", g, param)) return;
         ensure_device();
         Context &c = *it->second;
         GraphPack &gp = pack_for(g);

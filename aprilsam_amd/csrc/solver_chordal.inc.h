@@ -78,6 +78,7 @@ static int initialize_chordal_impl(april_graph_t *g, april_graph_cholesky_param_
     {   // refusals before anything is uploaded: the param keeps whatever it had
         SlotLock lk(param, g);
         if (g_shard.find(param) != g_shard.end()) { snprintf(msg, sizeof msg, "%s: sharded params are not supported", who); return gate_refuse(ERR_UNSUPPORTED, msg); }
+        if (int rc = refuse_fixed(who, g)) return rc;          // (fixed nodes, DESIGN.md section 20: the two linear stages know no mask yet)
         GraphPack &gp = pack_for(g);
         pack_factors(gp, g);
         if (!gp.host_idx.empty()) { snprintf(msg, sizeof msg, "%s: the graph holds host-evaluated factors (foreign types): use april_graph_cholesky", who); return gate_refuse(-4, msg); }

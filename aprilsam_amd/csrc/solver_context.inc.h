@@ -173,13 +173,14 @@ struct Context {
     long long gexec_mx = -1;              // GraphPack::mx_gen it was captured with (max-mixture table)
     long long gexec_rb = -1;              // GraphPack::rb_gen it was captured with (robust table)
     long long gexec_pl = -1;              // GraphPack::pl_gen it was captured with (polar table)
+    long long gexec_fx = -1;              // GraphPack::fx_gen it was captured with (fixed nodes)
     // the same phase as the API call runs it: first kernel reads the caller's states from the pinned mirror, last kernel
     // writes new states / dx / pivot flag back to pinned mirrors -- one graph launch + one stream sync per call
     hipGraphExec_t gexec_api = nullptr;
-    const void *api_key[10] = {};
+    const void *api_key[11] = {};
     // Levenberg-Marquardt (solver_lm.inc.h): one iteration captured as its own graph, keyed like gexec plus the LM buffers it reads
     hipGraphExec_t gexec_lm = nullptr;
-    const void *lm_key[11] = {};
+    const void *lm_key[12] = {};
     DBuf<double> d_lm_trial, d_lm_hacc, d_lm_terms, d_lm_trace; DBuf<LmScalars> d_lm; HBuf<LmScalars> h_lm;
     // chordal initialisation (solver_chordal.inc.h): [scratch of the state update 3N][theta N][4 scalars]; the components chosen for the max factors
     DBuf<double> d_ch; HBuf<double> h_ch; DBuf<int> d_ch_sel;
@@ -215,6 +216,9 @@ struct Context {
         retired.push_back(r); g = nullptr;
     }
     double lambda_val = -1; int lambda_N = -1;     // what d_lambda currently holds (uniform batch value), -1: unknown
+    long long lambda_fx_gen = 0, lambda_fx_serial = 0;      // ... apart from the 1.0 of the fixed nodes of this pack at this fx_gen (k_fix_mask; set_lambda)
+    DBuf<int> d_fx_mask;                           // ... and which nodes of a covariance query are among them (k_fix_cov)
+    std::vector<int> fact_fixed;                   // the fixed nodes the retained factor was made with (record_factor)
     // marginal covariances (solver_marginals.inc.h): what the last successful solver call left in d_pool (FACT_*), at which value of
     // epoch_steps; the Sigma pool (front pool layout) and the step it was computed for; launch tables built per plan
     int fact_kind = 0; long long fact_epoch = -1; bool fact_asym = false;
@@ -231,7 +235,7 @@ struct Context {
     }
     void release() {
         release_sel();
-        d_i32.release(); d_fd.release(); d_dest.release(); d_child.release(); d_lambda.release(); d_tab.release(); d_swap.release(); d_pos.release();
+        d_i32.release(); d_fd.release(); d_dest.release(); d_child.release(); d_lambda.release(); d_fx_mask.release(); d_tab.release(); d_swap.release(); d_pos.release();
         d_pool.release(); d_H.release(); d_x.release(); d_diag.release(); d_bad.release(); h_bad.release(); patches.release();
         h_done.release(); h_kstamp.release(); d_prof.release(); d_upd.release(); d_wbuf.release(); d_flags.release(); d_flevel.release(); d_epoch.release(); d_marks.release(); d_perm.release(); d_solve_tab.release(); d_dinv.release(); d_bsb_far.release(); d_bsb_flags.release(); d_guard.release(); d_guard_cnt.release(); n_guard = 0;
         d_lm_trial.release(); d_lm_hacc.release(); d_lm_terms.release(); d_lm_trace.release(); d_lm.release(); h_lm.release();

@@ -162,6 +162,14 @@ static void ps_run(Context &c, hipStream_t s, int n, const int *qa, const int *q
         S.node_j.clear(); S.serial = -1;
         throw;
     }
+    std::vector<int> fmask;
+    if (fixed_query_mask(c, n, qa, qb, fmask)) {      // fixed nodes: their rows and columns are exact zeros before anything leaves or is gated (k_fix_cov)
+        c.d_fx_mask.need((size_t)n);
+        HIPCHECK(hipMemcpyAsync(c.d_fx_mask.p, fmask.data(), (size_t)4 * n, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_fix_cov, dim3((n + TPB - 1) / TPB), dim3(TPB), 0, s, n, (const int *)c.d_fx_mask.p, 36, S.d_cov.p, S.h_out.p);
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipStreamSynchronize(s));
+    }
     if (gate_in) {
         S.d_in.need((size_t)18 * n);
         HIPCHECK(hipMemcpyAsync(S.d_in.p, gate_in, (size_t)8 * 18 * n, hipMemcpyHostToDevice, s));
@@ -177,10 +185,11 @@ static int gate_refuse(int code, const char *msg) {
 }
 
 // the checks aprilsam_amd_marginals makes (solver_marginals.inc.h), in the same order; 0 and the context, or the code
-static int ps_context(april_graph_cholesky_param_t *param, const char *who, Context *&out) {
+static int ps_context(april_graph_cholesky_param_t *param, const char *who, Context *&out, const april_graph_t *g = nullptr) {
     char msg[256];
     if (g_shard.find(param) != g_shard.end()) { snprintf(msg, sizeof msg, "%s: sharded params are not supported", who); return gate_refuse(ERR_UNSUPPORTED, msg); }
     auto it = g_ctx.find(param);
+    if (it != g_ctx.end()) drop_factor_if_toggled(*it->second, g);
     if (it == g_ctx.end() || !it->second->have_fact || it->second->st.not_spd || it->second->fact_kind == FACT_NONE || it->second->fact_epoch != it->second->epoch_steps) {
         snprintf(msg, sizeof msg, "%s: no retained factor (no successful solver call since the param was created or last failed)", who);
         return gate_refuse(-1, msg);
@@ -200,7 +209,7 @@ static int joint_any_impl(april_graph_t *g, april_graph_cholesky_param_t *param,
     ensure_device();
     SlotLock lk(param, g);
     Context *cp = nullptr;
-    if (int rc = ps_context(param, who, cp)) return rc;
+    if (int rc = ps_context(param, who, cp, g)) return rc;
     Context &c = *cp;
     const int N = c.fact_kind == FACT_EXTENDED ? c.inc_N : c.plan.N;
     for (int i = 0; i < n; i++)
@@ -221,7 +230,7 @@ static int gate_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int 
     ensure_device();
     SlotLock lk(param, g);
     Context *cp = nullptr;
-    if (int rc = ps_context(param, who, cp)) return rc;
+    if (int rc = ps_context(param, who, cp, g)) return rc;
     Context &c = *cp;
     const int N = c.fact_kind == FACT_EXTENDED ? c.inc_N : c.plan.N, Ng = zsize(g->nodes);
     for (int i = 0; i < n; i++) {

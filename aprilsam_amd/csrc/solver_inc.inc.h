@@ -852,6 +852,8 @@ static bool check_bad(Context &c) {
 
 static void set_lambda(Context &c, GraphPack &gp, double lambda) {
     const int N = c.plan.N;
+    // (fixed nodes, DESIGN.md section 20: k_fix_mask leaves 1.0 at their positions -- another set, or another graph's, and the array is written again)
+    if (gp.fx_gen != c.lambda_fx_gen || (gp.fx_gen != 0 && gp.serial != c.lambda_fx_serial)) { c.lambda_N = -1; c.lambda_fx_gen = gp.fx_gen; c.lambda_fx_serial = gp.serial; }
     if (c.lambda_N == N && c.lambda_val == lambda) return;       // d_lambda already holds it (warm calls)
     c.lambda_N = N; c.lambda_val = lambda;
     c.h_lambda.assign(N, lambda > 0 ? lambda : 0.0);            // aprilsam.c:197-204

@@ -200,6 +200,20 @@ static void enqueue_polar(GraphPack &gp, hipStream_t s) { launch_polar(s, gp, k_
 // ... and every chi^2 is followed by their true terms at the states, in place of what k_chi2 made of the slot
 static void enqueue_chi2_polar(GraphPack &gp, hipStream_t s) { launch_polar(s, gp, k_chi2_polar, (const double *)gp.d_state.p, gp.d_chi2f.p); }
 
+// The kernel of fixed.hip.h that runs one thread per record of the pack's fixed table and one per fixed node: the
+// slots of d_H named by the records become zero, d_lambda at the fixed nodes' positions 1.0.  None for a pack without fixed nodes.  It
+// follows whatever wrote the slots and d_lambda for the step and precedes the first assembly kernel, inside every captured graph
+static void launch_fixed(hipStream_t s, Context &c, GraphPack &gp) {
+    const int NF = gp.n_fixed();
+    if (NF == 0) return;
+    const int R = (int)gp.fx_rec.size();
+    // (the kernel indexes the plan's tables with what the pack holds: both were made from the same packed graph)
+    if (gp.fx_dirty || gp.fx_topo != gp.topo_version || gp.fx_nodes.back() >= c.plan.N || (R > 0 && gp.fx_rec.back().x >= c.plan.F))
+        fail(ERR_INTERNAL, "fixed table out of step with the plan (%d nodes of %d, %d records, entries < %d)", NF, c.plan.N, R, c.plan.F);
+    hipLaunchKernelGGL(k_fix_mask, dim3((R + NF + TPB - 1) / TPB), dim3(TPB), 0, s, R, (const int2 *)gp.d_fx_rec.p, NF, (const int *)gp.d_fx_nodes.p, (const int *)c.d_pos.p,
+                       c.dp.slot_blk, c.dp.slot_rhs, c.d_H.p, c.d_lambda.p);
+}
+
 // what fills the contribution slots of a Gauss-Newton step: selection, robust weights, linearisation (+ the host-evaluated factors' blocks)
 static void enqueue_linearise(Context &c, GraphPack &gp, hipStream_t s, bool unary_at_lp) {
     const int F = c.plan.F;
@@ -220,6 +234,7 @@ static void enqueue_linearise(Context &c, GraphPack &gp, hipStream_t s, bool una
         hipLaunchKernelGGL(k_scatter_host, dim3((nh + TPB - 1) / TPB), dim3(TPB), 0, s, nh, gp.d_host_idx.p, gp.d_hostH.p, gp.d_fb.p, c.d_swap.p,
                            c.dp.slot_blk, c.dp.slot_rhs, c.d_H.p);
     }
+    launch_fixed(s, c, gp);                          // fixed nodes: their slots zeroed, their diagonal 1.0 -- last, after everything that writes a slot
 }
 
 // what a caller of the numeric phase asks for beyond the plain step; everything is off unless named
@@ -326,17 +341,17 @@ static void run_numeric(Context &c, GraphPack &gp, const RunArgs &r = RunArgs{})
     if (!r.io_host) a.relin = r.relin;
     const bool graph = g_opt.use_graph && !r.timing && gp.host_idx.empty();      // (host-evaluated factors: staging buffers may move)
     if (r.io_host && graph) {
-        const void *key[10] = { gp.d_state.p, gp.h_state.p, gp.h_lp.p, gp.h_dx.p, c.h_bad.p, (const void *)(size_t)gp.N, (const void *)(size_t)gp.serial, (const void *)(size_t)gp.mx_gen,
-                                (const void *)(size_t)gp.rb_gen, (const void *)(size_t)gp.pl_gen };
+        const void *key[11] = { gp.d_state.p, gp.h_state.p, gp.h_lp.p, gp.h_dx.p, c.h_bad.p, (const void *)(size_t)gp.N, (const void *)(size_t)gp.serial, (const void *)(size_t)gp.mx_gen,
+                                (const void *)(size_t)gp.rb_gen, (const void *)(size_t)gp.pl_gen, (const void *)(size_t)gp.fx_gen };
         // A graph is worth its capture, instantiation and destruction (0.3 ms together) only if the configuration comes back:
         // the first call with a new key -- every fall-back of an incremental run, every cold call -- enqueues its kernels directly.
         if (memcmp(key, c.api_key, sizeof(key)) != 0) { c.retire(c.gexec_api); memcpy(c.api_key, key, sizeof(key)); c.api_key_runs = 0; }
         if (c.api_key_runs++ == 0) enqueue_numeric(c, gp, s, a);
         else replay_captured(c, c.gexec_api, s, [&] { enqueue_numeric(c, gp, s, a); });
     } else if (!r.io_host && graph && !r.unary_at_lp) {
-        if (c.gexec_key != (const void *)gp.d_state.p || c.gexec_serial != gp.serial || c.gexec_mx != gp.mx_gen || c.gexec_rb != gp.rb_gen || c.gexec_pl != gp.pl_gen) {
+        if (c.gexec_key != (const void *)gp.d_state.p || c.gexec_serial != gp.serial || c.gexec_mx != gp.mx_gen || c.gexec_rb != gp.rb_gen || c.gexec_pl != gp.pl_gen || c.gexec_fx != gp.fx_gen) {
             c.retire(c.gexec);
-            c.gexec_key = (const void *)gp.d_state.p; c.gexec_serial = gp.serial; c.gexec_mx = gp.mx_gen; c.gexec_rb = gp.rb_gen; c.gexec_pl = gp.pl_gen;
+            c.gexec_key = (const void *)gp.d_state.p; c.gexec_serial = gp.serial; c.gexec_mx = gp.mx_gen; c.gexec_rb = gp.rb_gen; c.gexec_pl = gp.pl_gen; c.gexec_fx = gp.fx_gen;
         }
         replay_captured(c, c.gexec, s, [&] { enqueue_numeric(c, gp, s, a); });
     } else {

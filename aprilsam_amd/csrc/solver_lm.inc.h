@@ -72,8 +72,9 @@ static void lm_enqueue_iteration(Context &c, GraphPack &gp, hipStream_t s) {
 static void lm_run_iteration(Context &c, GraphPack &gp, hipStream_t s) {
     rewind_epoch(c, s, 1);
     if (!g_opt.use_graph) { lm_enqueue_iteration(c, gp, s); return; }
-    const void *key[11] = { gp.d_state.p, (const void *)(size_t)gp.serial, (const void *)(size_t)gp.mx_gen, (const void *)(size_t)gp.N,
-                           c.d_lm_trial.p, c.d_lm_terms.p, c.d_lm_trace.p, c.d_lm.p, (const void *)(size_t)gp.rb_gen, (const void *)(size_t)gp.gc_gen, (const void *)(size_t)gp.pl_gen };
+    const void *key[12] = { gp.d_state.p, (const void *)(size_t)gp.serial, (const void *)(size_t)gp.mx_gen, (const void *)(size_t)gp.N,
+                           c.d_lm_trial.p, c.d_lm_terms.p, c.d_lm_trace.p, c.d_lm.p, (const void *)(size_t)gp.rb_gen, (const void *)(size_t)gp.gc_gen, (const void *)(size_t)gp.pl_gen,
+                           (const void *)(size_t)gp.fx_gen };
     if (memcmp(key, c.lm_key, sizeof(key)) != 0) { c.retire(c.gexec_lm); memcpy(c.lm_key, key, sizeof(key)); }
     replay_captured(c, c.gexec_lm, s, [&] { lm_enqueue_iteration(c, gp, s); });
 }

@@ -125,6 +125,24 @@ static void enqueue_selinv(Context &c, hipStream_t s) {
 // kept against it.
 static void record_factor(Context &c, int kind, const GraphPack &gp) {
     c.fact_kind = kind; c.fact_epoch = c.epoch_steps; c.fact_asym = gp.n_asym > 0 || c.wt_any; c.fact_serial++;
+    c.fact_fixed = gp.fx_nodes;
+}
+// Fixed nodes: the consumers of the retained factor describe the system it was made from, identity blocks
+// included.  A node fixed or freed since then makes that system another one: the factor is dropped, and the consumer answers as without.
+static void drop_factor_if_toggled(Context &c, const april_graph_t *g) {
+    if (!g || (c.fact_fixed.empty() && !fixed_ever())) return;
+    std::vector<int> now;
+    scan_fixed(g, now);
+    if (now != c.fact_fixed) { c.have_fact = false; c.fact_kind = FACT_NONE; }
+}
+// per query i of n: bit 0 = qa[i] is among the fixed nodes of the retained factor, bit 1 = qb[i] (qb may be null); false when no bit is set
+static bool fixed_query_mask(const Context &c, int n, const int *qa, const int *qb, std::vector<int> &mask) {
+    if (c.fact_fixed.empty()) return false;
+    bool any = false;
+    mask.assign((size_t)n, 0);
+    auto is = [&](int q) { return std::binary_search(c.fact_fixed.begin(), c.fact_fixed.end(), q); };
+    for (int i = 0; i < n; i++) { mask[i] = (is(qa[i]) ? 1 : 0) | (qb && is(qb[i]) ? 2 : 0); any = any || mask[i]; }
+    return any;
 }
 
 // Sigma of the retained factor on stream s, unless it is there already; the caller stamps c.sel_serial = c.fact_serial once the stream has
@@ -147,6 +165,7 @@ static int marginals_impl(april_graph_t *g, april_graph_cholesky_param_t *param,
     SlotLock lk(param, g);
     if (g_shard.find(param) != g_shard.end()) return refuse(ERR_UNSUPPORTED, "aprilsam_amd_marginals: sharded params are not supported");
     auto it = g_ctx.find(param);
+    if (it != g_ctx.end()) drop_factor_if_toggled(*it->second, g);
     if (it == g_ctx.end() || !it->second->have_fact || it->second->st.not_spd || it->second->fact_kind == FACT_NONE || it->second->fact_epoch != it->second->epoch_steps)
         return refuse(-1, "aprilsam_amd_marginals: no retained factor (no successful solver call since the param was created or last failed)");
     Context &c = *it->second;
@@ -177,6 +196,12 @@ static int marginals_impl(april_graph_t *g, april_graph_cholesky_param_t *param,
     hipLaunchKernelGGL(k_marginal_extract, dim3((unsigned)((nv + TPB - 1) / TPB)), dim3(TPB), 0, s, n, (const int *)c.d_sel_q.p,
                        joint ? (const int *)c.d_sel_q.p + n : (const int *)nullptr, (const int *)c.d_sel_i32.p, (const int *)c.d_sel_i32.p + c.sel_N,
                        (const SelFront *)c.d_sel_fd.p, (const int *)c.d_i32.p, (const double *)c.d_sigma.p, c.h_cov.p);
+    std::vector<int> fmask;
+    if (fixed_query_mask(c, n, qa, joint ? qb : nullptr, fmask)) {      // fixed nodes: their rows and columns leave as exact zeros (k_fix_cov, on the pinned result)
+        c.d_fx_mask.need((size_t)n);
+        HIPCHECK(hipMemcpyAsync(c.d_fx_mask.p, fmask.data(), (size_t)4 * n, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_fix_cov, dim3((n + TPB - 1) / TPB), dim3(TPB), 0, s, n, (const int *)c.d_fx_mask.p, per, c.h_cov.p, (double *)nullptr);
+    }
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(s));
     c.sel_serial = c.fact_serial;

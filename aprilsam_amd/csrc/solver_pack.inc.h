@@ -96,6 +96,14 @@ struct GraphPack {
     void pl_clear() {
         if (!pl_f.empty() || pl_on_device) pl_gen++;      // (a pack that never held polar factors keeps its captured graphs)
         pl_f.clear(); pl_kind.clear(); pl_of.clear(); pl_z.clear(); pl_W.clear(); pl_on_device = 0; pl_dirty = false; }
+    // fixed nodes (fixed.hip.h): fx_nodes: the ids of the nodes held constant, ascending, as the last call's walk over
+    // the node objects found them (sync_fixed); fx_rec: one record per packed entry with a fixed endpoint (.x the entry, .y the FX_* bits of
+    // the slots k_fix_mask zeroes), built from the PACKED entries -- the pairs of a host-evaluated clique included -- at fx_topo =
+    // topo_version.  fx_gen changes whenever the set or the records do: captured graphs are keyed by it, and d_lambda's host cache
+    std::vector<int> fx_nodes; std::vector<int2> fx_rec; long long fx_topo = -1;
+    DBuf<int> d_fx_nodes; DBuf<int2> d_fx_rec;
+    bool fx_dirty = false; long long fx_gen = 0;
+    int n_fixed() const { return (int)fx_nodes.size(); }
     // GNC candidates (gnc.hip.h): a table that exists on the device for the length of ONE aprilsam_amd_optimize_gnc
     // call -- gc_n > 0 only inside it.  d_gc_f / d_gc_W0 / d_gc_w: packed entry, plain W and last weight per candidate, d_gc_par: loss, c
     // and mu; d_gc_out / gc_stage: results and their pinned staging.  gc_gen changes with every run: captured LM iterations are keyed by it
@@ -115,6 +123,7 @@ struct GraphPack {
         d_mx_f.release(); d_mx_k.release(); d_sel.release(); d_mx_z.release(); d_mx_W.release(); d_mx_c.release(); mx_stage.release(); mx_clear();
         d_rb_f.release(); d_rb_kind.release(); d_rb_c.release(); d_rb_W0.release(); d_rb_w.release(); rb_stage.release(); rb_clear();
         d_pl_f.release(); d_pl_kind.release(); d_pl_z.release(); d_pl_W.release(); pl_stage.release(); pl_clear();
+        d_fx_nodes.release(); d_fx_rec.release(); fx_nodes.clear(); fx_rec.clear(); fx_topo = -1; fx_dirty = false;
         d_gc_f.release(); d_gc_W0.release(); d_gc_w.release(); d_gc_out.release(); d_gc_par.release(); gc_stage.release(); gc_n = 0;
         if (stream) { forget_stream(stream); park_stream(slot, stream); }
         stream = nullptr;
@@ -534,6 +543,61 @@ static void select_new_polar(GraphPack &gp, int f_from) {
         polar_host_slot(gp.pl_kind[q], gp.pl_z.data() + (size_t)2 * q, gp.pl_W.data() + (size_t)4 * q, gp.h_lp.p + (size_t)3 * a, gp.h_lp.p + (size_t)3 * b,
                         gp.h_z.p + (size_t)3 * p, gp.h_W.p + (size_t)9 * p);
     }
+}
+// ---- fixed nodes -------------------------------------------------------------------------------------
+// the first fixed node of a graph, -1 when it has none (a process that never fixed a node does not walk)
+static int first_fixed(const april_graph_t *g) {
+    if (!g || !fixed_ever()) return -1;
+    april_graph_node_t **ns = (april_graph_node_t **)g->nodes->data;
+    for (int i = 0, N = zsize(g->nodes); i < N; i++) if (node_fixed(ns[i])) return i;
+    return -1;
+}
+static void scan_fixed(const april_graph_t *g, std::vector<int> &out) {
+    out.clear();
+    if (!g || !fixed_ever()) return;
+    april_graph_node_t **ns = (april_graph_node_t **)g->nodes->data;
+    for (int i = 0, N = zsize(g->nodes); i < N; i++) if (node_fixed(ns[i])) out.push_back(i);
+}
+// The entry points that do not take fixed nodes: 0, or -12 with a message that names the first fixed node.  Nothing was read or written
+// before; the param keeps its plan and factor (the refusal is recorded, not thrown).
+static int refuse_fixed(const char *who, const april_graph_t *g) {
+    const int i = first_fixed(g);
+    if (i < 0) return 0;
+    char msg[320];
+    snprintf(msg, sizeof msg, "%s: node %d is fixed (aprilsam_amd_node_set_fixed); this entry point does not take fixed nodes yet (DESIGN.md section 20)", who, i);
+    set_last_error(ERR_UNSUPPORTED, msg);
+    fprintf(stderr, "aprilsam_amd: ERROR %d: %s\n", (int)ERR_UNSUPPORTED, msg); fflush(stderr);
+    return ERR_UNSUPPORTED;
+}
+// the content check of the nodes' flags, once per call that linearises: a node fixed or freed since the last call is seen here
+static void sync_fixed(GraphPack &gp, const april_graph_t *g) {
+    if (gp.fx_nodes.empty() && !fixed_ever()) return;
+    std::vector<int> now;
+    scan_fixed(g, now);
+    if (now != gp.fx_nodes) { gp.fx_nodes.swap(now); gp.fx_gen++; gp.fx_dirty = true; }
+}
+// the table -> device, after pack_factors: the records are rebuilt when the set or the packed endpoints changed
+static void upload_fixed(GraphPack &gp) {
+    if (gp.fx_nodes.empty()) { gp.fx_rec.clear(); gp.fx_dirty = false; return; }
+    if (!gp.fx_dirty && gp.fx_topo == gp.topo_version) return;
+    if (gp.fx_nodes.back() >= gp.N) fail(ERR_INTERNAL, "fixed node %d of %d packed nodes", gp.fx_nodes.back(), gp.N);
+    std::vector<char> fx((size_t)gp.N, 0);
+    for (int i : gp.fx_nodes) fx[i] = 1;
+    std::vector<int2> rec;
+    for (int f = 0; f < gp.F; f++) {
+        const int a = gp.h_fa.p[f], b = gp.h_fb.p[f];
+        const int m = (fx[a] ? FX_AA | FX_AB | FX_GA : 0) | (b >= 0 && fx[b] ? FX_AB | FX_BB | FX_GB : 0);
+        if (m) rec.push_back(int2{ f, b >= 0 ? m : m & (FX_AA | FX_GA) });
+    }
+    if (!gp.fx_dirty && rec.size() == gp.fx_rec.size() && (rec.empty() || memcmp(rec.data(), gp.fx_rec.data(), rec.size() * sizeof(int2)) == 0)) { gp.fx_topo = gp.topo_version; return; }
+    if (!gp.fx_dirty) gp.fx_gen++;
+    gp.fx_rec.swap(rec);
+    HIPCHECK(hipStreamSynchronize(gp.stream));      // (no launch that reads the old table is in flight when it is overwritten)
+    gp.d_fx_nodes.need(gp.fx_nodes.size()); gp.d_fx_rec.need(std::max<size_t>(1, gp.fx_rec.size()));
+    HIPCHECK(hipMemcpyAsync(gp.d_fx_nodes.p, gp.fx_nodes.data(), gp.fx_nodes.size() * 4, hipMemcpyHostToDevice, gp.stream));
+    if (!gp.fx_rec.empty()) HIPCHECK(hipMemcpyAsync(gp.d_fx_rec.p, gp.fx_rec.data(), gp.fx_rec.size() * sizeof(int2), hipMemcpyHostToDevice, gp.stream));
+    HIPCHECK(hipStreamSynchronize(gp.stream));      // (the sources are pageable)
+    gp.fx_dirty = false; gp.fx_topo = gp.topo_version;
 }
 static void upload_factors(GraphPack &gp) {
     const int F = gp.F;

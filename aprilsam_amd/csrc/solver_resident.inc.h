@@ -14,11 +14,13 @@ static int resident_begin_impl(april_graph_t *g, april_graph_cholesky_param_t *p
     pack_factors(gp, g);
     if (!gp.host_idx.empty()) return -4;          // host-evaluated factors need the host in the loop: use april_graph_cholesky
     pack_states(gp, g, false);
+    sync_fixed(gp, g);                            // (fixed nodes, DESIGN.md section 20: the set of the loop is the one found here)
     gp.lp_last_valid = false;
     orient_asymmetric(c, gp);
     const bool reused = prepare_plan(c, gp, g);
     flush_orientation(c, gp.stream);
     upload_factors(gp);
+    upload_fixed(gp);
     set_lambda(c, gp, param->tikhanov);
     if (!c.have_events) { for (auto &e : c.ev) HIPCHECK(hipEventCreate(&e)); c.have_events = true; }
     for (int k = 0; k < NKERN; k++) { c.k_ms[k] = 0; c.k_calls[k] = 0; }
@@ -249,10 +251,12 @@ static int debug_stage_impl(april_graph_t *g, april_graph_cholesky_param_t *para
     pack_factors(gp, g);
     if (!gp.host_idx.empty()) return -4;
     pack_states(gp, g, false);
+    sync_fixed(gp, g);
     orient_asymmetric(c, gp);
     prepare_plan(c, gp, g);
     flush_orientation(c, gp.stream);
     upload_factors(gp);
+    upload_fixed(gp);
     const Plan &P = c.plan;
     const int N = gp.N, F = gp.F;
     hipStream_t s = gp.stream;
@@ -263,6 +267,11 @@ static int debug_stage_impl(april_graph_t *g, april_graph_cholesky_param_t *para
     enqueue_polar(gp, s);
     hipLaunchKernelGGL((k_linearize_t<false>), dim3((F + TPB - 1) / TPB), dim3(TPB), 0, s, 0, F, (const int *)nullptr, gp.d_fa.p, gp.d_fb.p, gp.d_z.p, gp.d_W.p,
                        gp.d_lp.p, gp.d_state.p, c.d_swap.p, c.dp.slot_blk, c.dp.slot_rhs, c.d_H.p, c.d_bad.p, (const double *)nullptr);
+    if (gp.n_fixed() > 0) {                       // (the mask writes d_lambda as every step's does: whatever runs next on this param rewrites it)
+        set_lambda(c, gp, param->tikhanov);
+        launch_fixed(s, c, gp);
+        c.lambda_N = -1;
+    }
     if (what == 0) {
         std::vector<double> H((size_t)9 * std::max(1, P.n_slots));
         HIPCHECK(hipMemcpyAsync(H.data(), c.d_H.p, H.size() * 8, hipMemcpyDeviceToHost, s));
@@ -309,6 +318,7 @@ static int debug_stage_impl(april_graph_t *g, april_graph_cholesky_param_t *para
         }
     }
     for (size_t i = 0; i < n; i++) A[i * n + i] += param->tikhanov > 0 ? param->tikhanov : 0.0;      // aprilsam.c:197-204
+    for (int i : gp.fx_nodes) for (int k = 0; k < 3; k++) A[((size_t)3 * i + k) * n + 3 * i + k] = 1.0;      // (a fixed node's diagonal is lambda = 1.0 on zeroed blocks: k_fix_mask)
     return 0;
 }
 

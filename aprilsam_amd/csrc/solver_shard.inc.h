@@ -190,6 +190,7 @@ static int shard_begin_impl(april_graph_t *g, april_graph_cholesky_param_t *para
 int shard_begin(april_graph_t *g, april_graph_cholesky_param_t *param, int rank, int world) { return guarded_rc(param, g, [&] { return shard_begin_impl(g, param, rank, world); }); }
 static int shard_begin_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int rank, int world) {
     if (zsize(g->nodes) == 0 || zsize(g->factors) == 0 || world < 1 || rank < 0 || rank >= world) return -1;
+    if (int rc = refuse_fixed("aprilsam_amd_shard_begin", g)) return rc;      // (fixed nodes, DESIGN.md section 20: a rank's linearisation knows no mask yet)
     ensure_device();
     SlotLock lk(param, g);
     Context &c = ctx_for(param);

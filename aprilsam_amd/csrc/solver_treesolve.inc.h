@@ -169,7 +169,7 @@ static int solve_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int
     ensure_device();
     SlotLock lk(param, g);
     Context *cp = nullptr;
-    if (int rc = ps_context(param, who, cp)) return rc;
+    if (int rc = ps_context(param, who, cp, g)) return rc;
     Context &c = *cp;
     hipStream_t s = take_stream(t_slot);
     struct Park { int slot; hipStream_t s; ~Park() { park_stream(slot, s); } } park{ t_slot, s };
@@ -204,8 +204,14 @@ static int solve_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int
 static int ts_anchor(april_graph_t *g, april_graph_cholesky_param_t *param, const char *who, int anchor, int &n, const int *nodes, bool need_graph,
                      Context *&cp, hipStream_t s) {
     char msg[256];
-    if (int rc = ps_context(param, who, cp)) return rc;
+    // fixed nodes: not taken yet, neither in the graph nor in the factor at hand
+    if (int rc = refuse_fixed(who, g)) return rc;
+    if (int rc = ps_context(param, who, cp, g)) return rc;
     Context &c = *cp;
+    if (!c.fact_fixed.empty()) {
+        snprintf(msg, sizeof msg, "%s: the retained factor was made with node %d fixed; this entry point does not take fixed nodes yet (DESIGN.md section 20)", who, c.fact_fixed[0]);
+        return gate_refuse(ERR_UNSUPPORTED, msg);
+    }
     const int N = c.fact_kind == FACT_EXTENDED ? c.inc_N : c.plan.N, Ng = need_graph ? zsize(g->nodes) : N;
     bool ok = anchor >= 0 && anchor < N && anchor < Ng && (nodes || N <= Ng) && (!nodes || n >= 0);
     if (!nodes) n = N;

@@ -171,6 +171,9 @@ class SolverLib:
             if hasattr(d, "aprilsam_amd_factor_set_robust"):
                 d.aprilsam_amd_factor_set_robust.argtypes = [C.POINTER(abi.Factor), C.c_int, C.c_double]
                 d.aprilsam_amd_factor_get_robust.argtypes = [C.POINTER(abi.Factor), C.POINTER(C.c_int), C.POINTER(C.c_double)]
+            if hasattr(d, "aprilsam_amd_node_set_fixed"):
+                d.aprilsam_amd_node_set_fixed.argtypes = [C.POINTER(abi.Node), C.c_int]
+                d.aprilsam_amd_node_get_fixed.argtypes = [C.POINTER(abi.Node)]
             if hasattr(d, "aprilsam_amd_robust_weights"):    # (defined in the HIP translation unit)
                 d.aprilsam_amd_robust_weights.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.c_int, _ip, _dp]
             if hasattr(d, "aprilsam_amd_factor_polar_create"):
@@ -483,6 +486,22 @@ class Graph:
     def node(self, i):
         arr = C.cast(self.ptr.contents.nodes.contents.data, C.POINTER(C.POINTER(abi.Node)))
         return arr[i].contents
+
+    def node_ptr(self, i):
+        """the node object pointer of node i (what the C entry points that take one node expect)"""
+        if not 0 <= int(i) < self.n_nodes:
+            raise IndexError(f"node {i} out of range ({self.n_nodes} nodes)")
+        arr = C.cast(self.ptr.contents.nodes.contents.data, C.POINTER(C.POINTER(abi.Node)))
+        return arr[int(i)]
+
+    def set_fixed(self, i, fixed=True):
+        """hold node i constant, or free it again (include/aprilsam_amd.h: aprilsam_amd_node_set_fixed).  Returns
+        the library's code (0, -12, -13)."""
+        return int(self.lib.dll.aprilsam_amd_node_set_fixed(self.node_ptr(i), int(fixed)))
+
+    def get_fixed(self, i):
+        """True when node i is held constant"""
+        return bool(self.lib.dll.aprilsam_amd_node_get_fixed(self.node_ptr(i)))
 
     def factor(self, i):
         arr = C.cast(self.ptr.contents.factors.contents.data, C.POINTER(C.POINTER(abi.Factor)))

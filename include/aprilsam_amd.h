@@ -684,6 +684,31 @@ int aprilsam_amd_factor_get_polar(const april_graph_factor_t *factor, int *kind)
  * share.  0, or -13 on a bad argument */
 int aprilsam_amd_debug_polar_slot(int kind, const double *pa, const double *pb, const double *z, const double *W, double *z_eff3, double *W_eff9);
 
+/* ---- fixed nodes: poses held constant ------------------------------------------------------------------------------
+ * A library-made xyt node (april_graph_node_xyt_create) is free or FIXED.  With Phi the fixed set, a step solves the normal equations with
+ * the rows and columns of Phi removed: in the assembled system every block (i, j) with i or j in Phi is zero, every right-hand-side segment
+ * of a node in Phi is zero and its diagonal block is exactly 1.0 * I (not 1 + tikhanov, not LM's lambda); a free node b keeps the whole
+ * H_bb and g_b of a factor it shares with a fixed node.  dx and delta_X of a fixed node are +-0, its x and y come back bitwise unchanged.
+ * Its heading passes through the state update's mod2pi like any other node's, (v + pi - 2 pi floor((v + pi) / 2 pi)) - pi: it is bitwise
+ * unchanged exactly when that wrap returns it bitwise (true for most, not all, v in [-pi, pi)), and a heading outside [-pi, pi) comes
+ * back wrapped.  With one node fixed a relative-only graph is regular at tikhanov = 0.  april_graph_chi2 and the LM / GNC objectives
+ * still count every factor.
+ * The flag lives in a tagged block on node->impl, which the reference leaves NULL on xyt nodes; the node's copy is deep, its destroy frees
+ * the block.  .graph files do not store the flag: save ignores it, load returns free nodes.  A node keeps its place in the elimination
+ * order, so fixing or freeing a node between two calls never re-plans; the next call of any kind sees the change.
+ * Open to fixed nodes: april_graph_cholesky, aprilsam_amd_batch_resident and the resident loop, aprilsam_amd_optimize_lm and _gnc (their
+ * damping never reaches a fixed node), aprilsam_amd_debug_stage, aprilsam_amd_solve (it solves the system that was factorised, identity
+ * blocks included: x of a fixed node is its right-hand side), aprilsam_amd_marginals, _marginals_joint, _marginals_joint_any and
+ * aprilsam_amd_gate_xyt: covariances of the free nodes are conditional on Phi, every row and column of a fixed node is exact zeros, so a
+ * candidate between a new pose and a fixed map pose is gated with the new pose's covariance alone.  These consumers use the fixed set
+ * the retained factor was made with; a toggle after the factorisation drops the retained factor and they answer as without one.
+ * Refused with -12, nothing written: april_graph_cholesky_inc and _inc_solver (void: see aprilsam_amd_last_error),
+ * aprilsam_amd_initialize_chordal, sharded params, aprilsam_amd_marginals_cross and aprilsam_amd_relative_covariances.
+ * set_fixed: 0; -13 for a NULL node or a value other than 0 / 1; -12 when the node is not an xyt node of this library or node->impl is
+ * in use by something else (node unchanged then).  set_fixed(node, 0) frees the block and leaves impl NULL. */
+int aprilsam_amd_node_set_fixed(april_graph_node_t *node, int fixed);   /* 0 / 1 */
+int aprilsam_amd_node_get_fixed(const april_graph_node_t *node);        /* 0 for any other node */
+
 /* ---- graduated non-convexity: outlier-robust optimisation (Yang et al., RA-L 2020) ---------------------------
  * The robust losses above are non-convex and help only from a start near the optimum.  aprilsam_amd_optimize_gnc optimises a sequence of
  * surrogate losses on a list of CANDIDATE factors (typically every loop closure): the first almost quadratic, so the start does not
