@@ -555,6 +555,17 @@ int aprilsam_amd_debug_polar_slot(int kind, const double *pa, const double *pb, 
     return 0;
 }
 
+int aprilsam_amd_debug_polar_gate(int kind, const double *pa, const double *pb, const double *z, const double *W, const double *cov36, double *d2, double *S4) {
+    if (kind < APRILSAM_AMD_POLAR_RANGE || kind > APRILSAM_AMD_POLAR_RANGE_BEARING || !pa || !pb || !z || !W || !cov36 || !d2 || !S4) {
+        asam::set_last_error(asam::ERR_BAD_GRAPH, "aprilsam_amd_debug_polar_gate: kind out of range (1 to 3) or a null argument");
+        return asam::ERR_BAD_GRAPH;
+    }
+    double S[4] = { 0.0, 0.0, 0.0, 0.0 };
+    const bool ok = asam::polar_gate(kind, z, W, pa, pb, cov36, d2, S);
+    for (int i = 0; i < 4; i++) S4[i] = S[i];
+    return ok ? 0 : 1;
+}
+
 april_graph_t *april_graph_create(void) {
     april_graph_t *g = (april_graph_t *)calloc(1, sizeof(april_graph_t));
     g->factors = zarray_new(sizeof(april_graph_factor_t *));

@@ -111,4 +111,74 @@ inline bool polar_spd(int kind, const double *w) {
     return w[1] == w[2] && w[0] > 0 && w[0] * w[3] - w[1] * w[2] > 0;
 }
 
+// ---- gating of a candidate polar measurement -------------------------------------------------------------------
+// The Mahalanobis test of the m-row innovation of a candidate (kind, z, Wp) between a and b at their states pa, pb, with C the 6 x 6 joint
+// covariance of (a, b), a's unknowns first, row-major:
+//   q, r      position of b in a's frame and r = z - h(q), the bearing row wrapped (polar_residual); the expressions of factor_residual
+//   J_q       rows 0 and 1 of the xyt factor's [J_a J_b] (2 x 6; b's heading column is zero, so pb[2] and row / column 5 of C are never read)
+//   J_p = G J_q,   S = J_p C J_p' + Wp^-1 (2 x 2: the adjugate; one row: 1 / w),   d2 = r' S^-1 r (a 2 x 2 Cholesky, or a division)
+// S: m x m row-major, the upper triangle computed and mirrored.  rho^2 == 0: G does not exist -- false, d2 and the m x m entries of S NaN.
+// No threshold, as for the slot.
+inline POLAR_HD bool polar_gate(int kind, const double *z, const double *Wp, const double *pa, const double *pb, const double *C, double *d2, double *S) {
+    const int m = polar_rows(kind);
+    double sa, ca;
+#ifdef __HIP_DEVICE_COMPILE__
+    sincos(pa[2], &sa, &ca);
+#else
+    sa = sin(pa[2]); ca = cos(pa[2]);
+#endif
+    const double dx = pb[0] - pa[0], dy = pb[1] - pa[1];
+    const double q0 = ca * dx + sa * dy, q1 = -sa * dx + ca * dy;
+    double G[4];
+    if (!polar_G(kind, q0, q1, G)) {
+        *d2 = NAN;
+        for (int i = 0; i < m * m; i++) S[i] = NAN;
+        return false;
+    }
+    double r[2];
+    polar_residual(kind, z, q0, q1, r);
+    const double Jq[10] = { -ca, -sa, -sa * dx + ca * dy, ca, sa,             // (column 5 is zero: left out)
+                            sa, -ca, -ca * dx - sa * dy, -sa, ca };
+    double Jp[10], JC[10];                                                    // m x 5
+    for (int i = 0; i < m; i++)
+        for (int k = 0; k < 5; k++) Jp[5 * i + k] = G[2 * i] * Jq[k] + G[2 * i + 1] * Jq[5 + k];
+    for (int i = 0; i < m; i++)
+        for (int j = 0; j < 5; j++) {
+            double v = 0.0;
+            for (int k = 0; k < 5; k++) v += Jp[5 * i + k] * C[6 * k + j];
+            JC[5 * i + j] = v;
+        }
+    double P[3] = { 0.0, 0.0, 0.0 };                                          // J_p C J_p': (0,0), (0,1), (1,1)
+    for (int k = 0; k < 5; k++) P[0] += JC[k] * Jp[k];
+    if (m == 1) {
+        const double s = P[0] + 1.0 / Wp[0];
+        S[0] = s;
+        *d2 = r[0] * r[0] / s;
+        return true;
+    }
+    for (int k = 0; k < 5; k++) { P[1] += JC[k] * Jp[5 + k]; P[2] += JC[5 + k] * Jp[5 + k]; }
+    const double det = Wp[0] * Wp[3] - Wp[1] * Wp[2];
+    const double s00 = P[0] + Wp[3] / det, s01 = P[1] + -Wp[1] / det, s11 = P[2] + Wp[0] / det;
+    S[0] = s00; S[1] = s01; S[2] = s01; S[3] = s11;
+    const double l00 = sqrt(s00), l10 = s01 / l00, l11 = sqrt(s11 - l10 * l10);
+    const double y0 = r[0] / l00, y1 = (r[1] - l10 * y0) / l11;
+    *d2 = y0 * y0 + y1 * y1;
+    return true;
+}
+
+// host: what aprilsam_amd_gate_polar and aprilsam_amd_associate_polar can judge of n measurements (kind[i], z[2 i..], W[4 i..]) without a
+// graph or a device: 0, or the refusal's code with its reason in *why.  Only the entries a kind reads are looked at: z[2 i] and W[4 i] for
+// one row, all of both for two.
+inline int polar_gate_args(int n, const int *kind, const double *z, const double *W, const char **why) {
+    for (int i = 0; i < n; i++) {
+        if (kind[i] < POLAR_RANGE || kind[i] > POLAR_RANGE_BEARING) { *why = "a kind outside RANGE, BEARING, RANGE_BEARING"; return -13; }
+        const int m = polar_rows(kind[i]);
+        for (int k = 0; k < m; k++) if (!std::isfinite(z[2 * i + k])) { *why = "a non-finite measurement"; return -13; }
+        for (int k = 0; k < m * m; k++) if (!std::isfinite(W[4 * i + k])) { *why = "a non-finite information matrix"; return -13; }
+    }
+    for (int i = 0; i < n; i++)
+        if (!polar_spd(kind[i], W + 4 * i)) { *why = "an information matrix that is not symmetric positive definite"; return -12; }
+    return 0;
+}
+
 }  // namespace asam

@@ -102,6 +102,10 @@ int marginals(april_graph_t *g, april_graph_cholesky_param_t *param, int n, cons
 long long selinv_runs(const april_graph_cholesky_param_t *param);
 int marginals_joint_any(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, double *cov);      // solver_gating.inc.h
 int gate_xyt(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, const double *z, const double *W, double *d2, double *S);
+int gate_polar(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, const int *kind, const double *z, const double *W,
+               double *d2, double *S);
+int associate_polar(april_graph_t *g, april_graph_cholesky_param_t *param, int observer, int m, const int *kind, const double *z, const double *W, int L,
+                    const int *landmarks, double gate1, double gate2, double *d2, int *best, double *d2_best, double *d2_second);
 long long path_solve_bytes(const april_graph_cholesky_param_t *param);
 int tree_solve(april_graph_t *g, april_graph_cholesky_param_t *param, int mode, int nrhs, const double *B, double *X);                // solver_treesolve.inc.h
 int marginals_cross(april_graph_t *g, april_graph_cholesky_param_t *param, int anchor, int n, const int *nodes, double *cov);

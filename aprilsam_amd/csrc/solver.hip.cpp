@@ -37,6 +37,7 @@
 #include "chordal.hip.h"
 #include "selinv.hip.h"
 #include "pathsolve.hip.h"
+#include "polargate.hip.h"
 #include "treesolve.hip.h"
 #include "plan.h"
 #include "refmodel.h"
@@ -524,6 +525,15 @@ extern "C" int aprilsam_amd_marginals_joint_any(april_graph_t *graph, april_grap
 extern "C" int aprilsam_amd_gate_xyt(april_graph_t *graph, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, const double *z,
                                      const double *W, double *d2, double *S) {
     return asam::gate_xyt(graph, param, n, a, b, z, W, d2, S);
+}
+extern "C" int aprilsam_amd_gate_polar(april_graph_t *graph, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, const int *kind,
+                                       const double *z, const double *W, double *d2, double *S) {
+    return asam::gate_polar(graph, param, n, a, b, kind, z, W, d2, S);
+}
+extern "C" int aprilsam_amd_associate_polar(april_graph_t *graph, april_graph_cholesky_param_t *param, int observer, int m, const int *kind, const double *z,
+                                            const double *W, int L, const int *landmarks, double gate1, double gate2, double *d2, int *best,
+                                            double *d2_best, double *d2_second) {
+    return asam::associate_polar(graph, param, observer, m, kind, z, W, L, landmarks, gate1, gate2, d2, best, d2_best, d2_second);
 }
 extern "C" long long aprilsam_amd_debug_path_solve_bytes(const april_graph_cholesky_param_t *param) { return asam::path_solve_bytes(param); }
 extern "C" int aprilsam_amd_solve(april_graph_t *graph, april_graph_cholesky_param_t *param, int mode, int nrhs, const double *B, double *X) {

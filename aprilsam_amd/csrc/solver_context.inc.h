@@ -71,9 +71,10 @@ struct PathState {
     std::vector<SelFront> fr; std::vector<int> depth, i32, rec, node_j;      // rec: front -> record, node_j: node -> column group (-1 between calls)
     DBuf<PsFront> d_fr; DBuf<int4> d_ent; DBuf<int> d_cmap; DBuf<long long> d_at; DBuf<PsPath> d_path; DBuf<PsPair> d_pair;
     DBuf<double> d_buf, d_cov, d_in; HBuf<double> h_out;
+    DBuf<int> d_pidx;                      // k_gate_polar: candidate -> its pair's block in d_cov
     long long peak_doubles = 0;            // the largest work buffer a chunk has used
     void release() {
-        d_fr.release(); d_ent.release(); d_cmap.release(); d_at.release(); d_path.release(); d_pair.release(); d_buf.release(); d_cov.release(); d_in.release(); h_out.release();
+        d_fr.release(); d_ent.release(); d_cmap.release(); d_at.release(); d_path.release(); d_pair.release(); d_buf.release(); d_cov.release(); d_in.release(); h_out.release(); d_pidx.release();
         fr.clear(); depth.clear(); i32.clear(); rec.clear(); node_j.clear(); serial = -1;
     }
 };

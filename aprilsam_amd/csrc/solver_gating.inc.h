@@ -1,7 +1,8 @@
 // solver_gating.inc.h -- part of solver.hip.cpp (ONE translation unit); included from there, inside namespace asam.
 // Contents: aprilsam_amd_marginals_joint_any / aprilsam_amd_gate_xyt: joint covariances of any pose pairs from the retained factor
 // by triangular solves along assembly-tree paths (pathsolve.hip.h), and the Mahalanobis gating of candidate xyt measurements.
-// DESIGN.md section 13.
+// DESIGN.md section 13.  aprilsam_amd_gate_polar / aprilsam_amd_associate_polar: the same for range / bearing / range-bearing measurements,
+// and their nearest-neighbour association against landmarks (polargate.hip.h).  DESIGN.md section 21.
 // ------------------------------------------------------------------------------------------------------
 // The fronts of the factor's structure (sel_fronts, solver_marginals.inc.h: the plan or the incremental path's extended structure),
 // kept against the factorisation counter.
@@ -130,13 +131,17 @@ static long long ps_budget() {
     return g_opt.mem_cap_mb > 0 ? std::min(dflt, ((long long)g_opt.mem_cap_mb << 20) / 8) : dflt;
 }
 
+// what a caller of ps_run runs behind the blocks in place of k_gate_xyt (the polar gates): `extra` doubles of S.h_out
+// behind the 36 n of the blocks, and what enqueues its copies and its kernel on the stream, which is synchronised after it
+struct PsTail { size_t extra = 0; std::function<void(hipStream_t)> enqueue; };
+
 // joint blocks of the n pairs (qa, qb) into S.d_cov / S.h_out (36 per pair); gate != null: then the gate of candidate i, in = 18
-// doubles each (k_gate_xyt), its d2 and S behind the blocks in S.h_out.
-static void ps_run(Context &c, hipStream_t s, int n, const int *qa, const int *qb, const double *gate_in) {
+// doubles each (k_gate_xyt), its d2 and S behind the blocks in S.h_out; tail != null (and gate_in null): the caller's kernel instead.
+static void ps_run(Context &c, hipStream_t s, int n, const int *qa, const int *qb, const double *gate_in, const PsTail *tail = nullptr) {
     ps_fronts(c);
     PathState &S = c.ps;
     S.d_cov.need((size_t)36 * n);
-    S.h_out.need((size_t)(gate_in ? 46 : 36) * n);
+    S.h_out.need((size_t)(gate_in ? 46 : 36) * n + (tail ? tail->extra : 0));
     const long long budget = ps_budget();
     if ((int)S.node_j.size() != S.N) S.node_j.assign((size_t)S.N, -1);
     std::vector<int> nodes; std::vector<int2> pj;
@@ -175,6 +180,11 @@ static void ps_run(Context &c, hipStream_t s, int n, const int *qa, const int *q
         HIPCHECK(hipMemcpyAsync(S.d_in.p, gate_in, (size_t)8 * 18 * n, hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(k_gate_xyt, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, (const double *)S.d_in.p, (const double *)S.d_cov.p,
                            S.h_out.p + (size_t)36 * n);
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipStreamSynchronize(s));
+    }
+    if (tail) {
+        tail->enqueue(s);
         HIPCHECK(hipGetLastError());
         HIPCHECK(hipStreamSynchronize(s));
     }
@@ -268,6 +278,131 @@ static int gate_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int 
     return 0;
 }
 
+// ---- polar gates ----------------------------------------------------------------------------------------------
+static int polar_refuse(int code, const char *who, const char *why) {
+    char msg[256];
+    snprintf(msg, sizeof msg, "%s: %s", who, why);
+    return gate_refuse(code, msg);
+}
+// node ids against the factorised system and the graph, as gate_xyt checks them
+static bool ps_ids_ok(const Context &c, const april_graph_t *g, int n, const int *q) {
+    const int N = c.fact_kind == FACT_EXTENDED ? c.inc_N : c.plan.N, Ng = zsize(g->nodes);
+    for (int i = 0; i < n; i++) if (q[i] < 0 || q[i] >= N || q[i] >= Ng) return false;
+    return true;
+}
+static const char *const PS_RANGE_MSG = "node id out of range of the factorised system (nodes added since the last solver call?)";
+
+// n candidates (kind, z, W) between a[i] and b[i]: every DISTINCT pair (a, b) is solved once, k_gate_polar reads a candidate's block through
+// its pair index.  What the checks can judge without the graph comes before the device is asked for.
+static int gate_polar_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *qa, const int *qb, const int *kind, const double *z,
+                           const double *W, double *d2, double *Sout) {
+    const char *who = "aprilsam_amd_gate_polar", *why = nullptr;
+    if (!g || !param || !qa || !qb || !kind || !z || !W || !d2 || n < 0) return polar_refuse(ERR_BAD_GRAPH, who, "null argument or negative count");
+    for (int i = 0; i < n; i++) if (qa[i] == qb[i]) return polar_refuse(ERR_BAD_GRAPH, who, "a candidate joins a node to itself");
+    if (int rc = polar_gate_args(n, kind, z, W, &why)) return polar_refuse(rc, who, why);
+    ensure_device();
+    SlotLock lk(param, g);
+    Context *cp = nullptr;
+    if (int rc = ps_context(param, who, cp, g)) return rc;
+    Context &c = *cp;
+    if (!ps_ids_ok(c, g, n, qa) || !ps_ids_ok(c, g, n, qb)) return polar_refuse(ERR_BAD_GRAPH, who, PS_RANGE_MSG);
+    if (n == 0) return 0;
+    std::vector<int> ua, ub, pidx((size_t)n);
+    std::unordered_map<long long, int> seen;
+    for (int i = 0; i < n; i++) {
+        auto r = seen.emplace(((long long)qa[i] << 32) | (unsigned)qb[i], (int)ua.size());
+        if (r.second) { ua.push_back(qa[i]); ub.push_back(qb[i]); }
+        pidx[i] = r.first->second;
+    }
+    const int np = (int)ua.size();
+    std::vector<double> in((size_t)PG_IN * n, 0.0);
+    april_graph_node_t **ns = (april_graph_node_t **)g->nodes->data;
+    for (int i = 0; i < n; i++) {
+        double *q = in.data() + (size_t)PG_IN * i;
+        const int m = polar_rows(kind[i]);
+        for (int k = 0; k < 3; k++) { q[k] = ns[qa[i]]->state[k]; q[3 + k] = ns[qb[i]]->state[k]; }
+        q[6] = kind[i];
+        for (int k = 0; k < m; k++) q[7 + k] = z[2 * i + k];
+        for (int k = 0; k < m * m; k++) q[9 + k] = W[4 * i + k];
+    }
+    hipStream_t s = take_stream(t_slot);
+    struct Park { int slot; hipStream_t s; ~Park() { park_stream(slot, s); } } park{ t_slot, s };
+    PathState &S = c.ps;
+    PsTail tail;
+    tail.extra = (size_t)6 * n;
+    tail.enqueue = [&](hipStream_t st) {
+        S.d_in.need(in.size()); S.d_pidx.need((size_t)n);
+        HIPCHECK(hipMemcpyAsync(S.d_in.p, in.data(), in.size() * 8, hipMemcpyHostToDevice, st));
+        HIPCHECK(hipMemcpyAsync(S.d_pidx.p, pidx.data(), (size_t)4 * n, hipMemcpyHostToDevice, st));
+        launch_polar_gate(st, k_gate_polar, n, false, n, (const double *)S.d_in.p, (const int *)S.d_pidx.p, (const double *)S.d_cov.p, S.h_out.p + (size_t)36 * np);
+    };
+    ps_run(c, s, np, ua.data(), ub.data(), nullptr, &tail);
+    const double *o = S.h_out.p + (size_t)36 * np;
+    memcpy(d2, o, (size_t)8 * n);
+    if (Sout) memcpy(Sout, o + n, (size_t)8 * 4 * n);
+    int unavailable = 0;
+    for (int i = 0; i < n; i++) unavailable += o[(size_t)5 * n + i] == 0.0;
+    return unavailable;
+}
+
+// m observations (kind, z, W) made from `observer` against the L nodes `landmarks`: the L pairs (observer, landmarks[l]) are solved once,
+// k_associate_polar gates every observation against every pair and reduces on the device.
+static int associate_polar_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int observer, int m, const int *kind, const double *z, const double *W,
+                                int L, const int *landmarks, double gate1, double gate2, double *d2, int *best, double *d2_best, double *d2_second) {
+    const char *who = "aprilsam_amd_associate_polar", *why = nullptr;
+    if (!g || !param || !kind || !z || !W || !landmarks || !best || !d2_best || !d2_second || m < 0 || L < 0)
+        return polar_refuse(ERR_BAD_GRAPH, who, "null argument or negative count");
+    for (int l = 0; l < L; l++) if (landmarks[l] == observer) return polar_refuse(ERR_BAD_GRAPH, who, "the observer is among the landmarks");
+    if (!std::isfinite(gate1) || !std::isfinite(gate2)) return polar_refuse(ERR_BAD_GRAPH, who, "a non-finite gate");
+    if (int rc = polar_gate_args(m, kind, z, W, &why)) return polar_refuse(rc, who, why);
+    ensure_device();
+    SlotLock lk(param, g);
+    Context *cp = nullptr;
+    if (int rc = ps_context(param, who, cp, g)) return rc;
+    Context &c = *cp;
+    if (!ps_ids_ok(c, g, 1, &observer) || !ps_ids_ok(c, g, L, landmarks)) return polar_refuse(ERR_BAD_GRAPH, who, PS_RANGE_MSG);
+    if (m == 0) return 0;
+    if (L == 0) {
+        for (int i = 0; i < m; i++) { best[i] = -1; d2_best[i] = INFINITY; d2_second[i] = INFINITY; }
+        return 0;
+    }
+    const std::vector<int> qa((size_t)L, observer);
+    std::vector<double> in((size_t)PG_OBS * m + 3 + (size_t)3 * L, 0.0);       // the observations, then the states: the observer's, the landmarks'
+    for (int i = 0; i < m; i++) {
+        double *q = in.data() + (size_t)PG_OBS * i;
+        const int r = polar_rows(kind[i]);
+        q[0] = kind[i];
+        for (int k = 0; k < r; k++) q[1 + k] = z[2 * i + k];
+        for (int k = 0; k < r * r; k++) q[3 + k] = W[4 * i + k];
+    }
+    april_graph_node_t **ns = (april_graph_node_t **)g->nodes->data;
+    double *st = in.data() + (size_t)PG_OBS * m;
+    for (int k = 0; k < 3; k++) st[k] = ns[observer]->state[k];
+    for (int l = 0; l < L; l++) for (int k = 0; k < 3; k++) st[3 + 3 * (size_t)l + k] = ns[landmarks[l]]->state[k];
+    hipStream_t s = take_stream(t_slot);
+    struct Park { int slot; hipStream_t s; ~Park() { park_stream(slot, s); } } park{ t_slot, s };
+    PathState &S = c.ps;
+    const size_t nmat = d2 ? (size_t)m * L : 0;
+    PsTail tail;
+    tail.extra = nmat + (size_t)3 * m;             // the matrix, d2_best, d2_second, then (best, unavailable) as two ints per observation
+    tail.enqueue = [&](hipStream_t sq) {
+        S.d_in.need(in.size());
+        HIPCHECK(hipMemcpyAsync(S.d_in.p, in.data(), in.size() * 8, hipMemcpyHostToDevice, sq));
+        double *o = S.h_out.p + (size_t)36 * L;
+        launch_polar_gate(sq, k_associate_polar, m, true, L, (const double *)S.d_in.p, (const double *)S.d_in.p + (size_t)PG_OBS * m, (const double *)S.d_cov.p,
+                          gate1, gate2, d2 ? o : (double *)nullptr, (int2 *)(o + nmat + (size_t)2 * m), o + nmat, o + nmat + m);
+    };
+    ps_run(c, s, L, qa.data(), landmarks, nullptr, &tail);
+    const double *o = S.h_out.p + (size_t)36 * L;
+    if (d2) memcpy(d2, o, 8 * nmat);
+    memcpy(d2_best, o + nmat, (size_t)8 * m);
+    memcpy(d2_second, o + nmat + m, (size_t)8 * m);
+    const int2 *res = (const int2 *)(o + nmat + (size_t)2 * m);
+    long long unavailable = 0;
+    for (int i = 0; i < m; i++) { best[i] = res[i].x; unavailable += res[i].y; }
+    return (int)std::min<long long>(unavailable, 0x7fffffff);
+}
+
 // As marginals: a failed call only reads the param's plan and factor, records the error and leaves both in place.
 template <class F> static int ps_guard(F f) {
     try { return f(); }
@@ -280,6 +415,14 @@ int marginals_joint_any(april_graph_t *g, april_graph_cholesky_param_t *param, i
 }
 int gate_xyt(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, const double *z, const double *W, double *d2, double *S) {
     return ps_guard([&] { return gate_impl(g, param, n, a, b, z, W, d2, S); });
+}
+int gate_polar(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, const int *kind, const double *z, const double *W,
+               double *d2, double *S) {
+    return ps_guard([&] { return gate_polar_impl(g, param, n, a, b, kind, z, W, d2, S); });
+}
+int associate_polar(april_graph_t *g, april_graph_cholesky_param_t *param, int observer, int m, const int *kind, const double *z, const double *W, int L,
+                    const int *landmarks, double gate1, double gate2, double *d2, int *best, double *d2_best, double *d2_second) {
+    return ps_guard([&] { return associate_polar_impl(g, param, observer, m, kind, z, W, L, landmarks, gate1, gate2, d2, best, d2_best, d2_second); });
 }
 long long path_solve_bytes(const april_graph_cholesky_param_t *param) {
     SlotLock lk(param, nullptr);

@@ -200,6 +200,14 @@ static void enqueue_polar(GraphPack &gp, hipStream_t s) { launch_polar(s, gp, k_
 // ... and every chi^2 is followed by their true terms at the states, in place of what k_chi2 made of the slot
 static void enqueue_chi2_polar(GraphPack &gp, hipStream_t s) { launch_polar(s, gp, k_chi2_polar, (const double *)gp.d_state.p, gp.d_chi2f.p); }
 
+// The kernels of polargate.hip.h, behind the path solves of a gating call: k_gate_polar runs one thread per candidate
+// (per_item = false: `work` candidates), k_associate_polar one workgroup per observation (per_item = true: `work` observations); `a` are the
+// kernel's arguments.  Nothing to gate: no launch
+template <class K, class... Args> static void launch_polar_gate(hipStream_t s, K kern, int work, bool per_item, const Args &...a) {
+    if (work <= 0) return;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(per_item ? work : (work + PG_T - 1) / PG_T)), dim3(PG_T), 0, s, a...);
+}
+
 // The kernel of fixed.hip.h that runs one thread per record of the pack's fixed table and one per fixed node: the
 // slots of d_H named by the records become zero, d_lambda at the fixed nodes' positions 1.0.  None for a pack without fixed nodes.  It
 // follows whatever wrote the slots and d_lambda for the step and precedes the first assembly kernel, inside every captured graph

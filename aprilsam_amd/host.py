@@ -34,6 +34,22 @@ def _np_i(a):
     return a.ctypes.data_as(_ip)
 
 
+def _polar_pad(m, z, W):
+    """z [2] and W [4] as the C interface lays a polar measurement of m rows out"""
+    zz = np.zeros(2); zz[:m] = np.asarray(z, float).ravel()[:m]
+    WW = np.zeros(4); WW[:m * m] = np.asarray(W, float).ravel()[:m * m]
+    return zz, WW
+
+
+def polar_candidates(cands):
+    """(kind [n], z [n, 2], W [n, 4]) of a list of (kind, z [m], W [m, m]) in the layout of aprilsam_amd_gate_polar / _associate_polar"""
+    kind = np.array([c[0] for c in cands], np.int32)
+    z = np.zeros((len(cands), 2)); W = np.zeros((len(cands), 4))
+    for i, (k, zz, WW) in enumerate(cands):
+        z[i], W[i] = _polar_pad(2 if int(k) == abi.POLAR_RANGE_BEARING else 1, zz, WW)
+    return kind, z, W
+
+
 class MarginalsError(RuntimeError):
     """a negative return of aprilsam_amd_marginals / _joint: .code is the return value"""
 
@@ -181,6 +197,12 @@ class SolverLib:
                 d.aprilsam_amd_factor_polar_create.argtypes = [C.c_int, C.c_int, C.c_int, _dp, _dp]
                 d.aprilsam_amd_factor_get_polar.argtypes = [C.POINTER(abi.Factor), C.POINTER(C.c_int)]
                 d.aprilsam_amd_debug_polar_slot.argtypes = [C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]
+            if hasattr(d, "aprilsam_amd_debug_polar_gate"):
+                d.aprilsam_amd_debug_polar_gate.argtypes = [C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]
+            if hasattr(d, "aprilsam_amd_gate_polar"):             # (defined in the HIP translation unit)
+                d.aprilsam_amd_gate_polar.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.c_int, _ip, _ip, _ip, _dp, _dp, _dp, _dp]
+                d.aprilsam_amd_associate_polar.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.c_int, C.c_int, _ip, _dp, _dp, C.c_int, _ip,
+                                                           C.c_double, C.c_double, _dp, _ip, _dp, _dp]
             d.aprilsam_amd_graph_save_ex.argtypes = [C.POINTER(abi.Graph), C.c_char_p, C.c_ulonglong]
             d.aprilsam_amd_graph_load.restype = C.POINTER(abi.Graph)
             d.aprilsam_amd_graph_load.argtypes = [C.c_char_p]
@@ -267,6 +289,18 @@ class SolverLib:
         if rc != 0:
             raise ValueError(f"aprilsam_amd_debug_polar_slot failed rc={rc}: {self.last_error()}")
         return ze, We.reshape(3, 3)
+
+    def polar_gate(self, kind, pa, pb, z, W, cov):
+        """(ok, d2, S [m, m]): the gate of one polar candidate at poses pa, pb with the 6 x 6 joint block cov (aprilsam_amd_debug_polar_gate:
+        host only); ok is False, d2 and S NaN when rho^2 == 0"""
+        m = 2 if int(kind) == abi.POLAR_RANGE_BEARING else 1
+        zz, WW = _polar_pad(m, z, W)
+        d2 = C.c_double(); S = np.zeros(4)
+        rc = self.dll.aprilsam_amd_debug_polar_gate(int(kind), _np_d(np.ascontiguousarray(pa, float)), _np_d(np.ascontiguousarray(pb, float)), _np_d(zz), _np_d(WW),
+                                                    _np_d(np.ascontiguousarray(cov, float).reshape(36)), C.byref(d2), _np_d(S))
+        if rc < 0:
+            raise ValueError(f"aprilsam_amd_debug_polar_gate failed rc={rc}: {self.last_error()}")
+        return rc == 0, d2.value, S[:m * m].reshape(m, m).copy()
 
     def load_graph(self, path):
         """april_graph_create_from_file (april_graph.c:398-426); None when the file cannot be read"""
@@ -629,6 +663,38 @@ class Graph:
         if rc < 0:
             raise MarginalsError(rc, self.lib.last_error())
         return d2, S
+
+    def gate_polar(self, param, a, b, kind, z, W):
+        """Mahalanobis gating of candidate polar measurements (include/aprilsam_amd.h: aprilsam_amd_gate_polar): kind [n], z [n, 2], W [n, 4]
+        (a 1-row kind uses z[i, 0] and W[i, 0]; see polar_candidates).  Returns (unavailable, d2 [n], S [n, 2, 2]).  Raises
+        MarginalsError(rc) on a negative return."""
+        a = np.ascontiguousarray(a, dtype=np.int32).ravel(); b = np.ascontiguousarray(b, dtype=np.int32).ravel()
+        kind = np.ascontiguousarray(kind, dtype=np.int32).ravel()
+        n = len(a)
+        if b.shape != a.shape or kind.shape != a.shape:
+            raise ValueError("a, b and kind must have the same length")
+        z = np.ascontiguousarray(z, dtype=float).reshape(n, 2); W = np.ascontiguousarray(W, dtype=float).reshape(n, 4)
+        d2 = np.empty(n); S = np.empty((n, 2, 2))
+        rc = self.lib.dll.aprilsam_amd_gate_polar(self.ptr, param.ptr, n, _np_i(a), _np_i(b), _np_i(kind), _np_d(z), _np_d(W), _np_d(d2), _np_d(S))
+        if rc < 0:
+            raise MarginalsError(rc, self.lib.last_error())
+        return rc, d2, S
+
+    def associate_polar(self, param, observer, kind, z, W, landmarks, gate1, gate2, matrix=True):
+        """Nearest-neighbour association of m polar observations made from `observer` against the nodes `landmarks`
+        (include/aprilsam_amd.h: aprilsam_amd_associate_polar).  Returns dict(unavailable, best [m] (index into landmarks or -1), d2_best [m],
+        d2_second [m], d2 [m, L] or None).  Raises MarginalsError(rc) on a negative return."""
+        kind = np.ascontiguousarray(kind, dtype=np.int32).ravel()
+        lm = np.ascontiguousarray(landmarks, dtype=np.int32).ravel()
+        m, L = len(kind), len(lm)
+        z = np.ascontiguousarray(z, dtype=float).reshape(m, 2); W = np.ascontiguousarray(W, dtype=float).reshape(m, 4)
+        d2 = np.empty((m, L)) if matrix else None
+        best = np.empty(m, np.int32); d2b = np.empty(m); d2s = np.empty(m)
+        rc = self.lib.dll.aprilsam_amd_associate_polar(self.ptr, param.ptr, int(observer), m, _np_i(kind), _np_d(z), _np_d(W), L, _np_i(lm), float(gate1), float(gate2),
+                                                       _np_d(d2) if matrix else None, _np_i(best), _np_d(d2b), _np_d(d2s))
+        if rc < 0:
+            raise MarginalsError(rc, self.lib.last_error())
+        return dict(unavailable=rc, best=best, d2_best=d2b, d2_second=d2s, d2=d2)
 
     SOLVE_MODES = {"full": 0, "forward": 1, "backward": 2}
 

@@ -684,6 +684,47 @@ int aprilsam_amd_factor_get_polar(const april_graph_factor_t *factor, int *kind)
  * share.  0, or -13 on a bad argument */
 int aprilsam_amd_debug_polar_slot(int kind, const double *pa, const double *pb, const double *z, const double *W, double *z_eff3, double *W_eff9);
 
+/* ---- gating and association of range / bearing observations against landmarks ------------------------------------
+ * The step before aprilsam_amd_factor_polar_create: does a candidate measurement (kind, z, W as above; node a observes node b) agree
+ * with what the solved graph predicts?  Per candidate, on the GPU right after the path solves of aprilsam_amd_marginals_joint_any:
+ *     q, r    the position of b in a's frame and r = z - h(q), the bearing wrapped, at the nodes' CURRENT states (as aprilsam_amd_gate_xyt)
+ *     J_p     G J_q: G = dh/dq (m x 2), J_q = rows 0 and 1 of the xyt factor's [J_a J_b] (2 x 6; b's heading column is zero)
+ *     S  = J_p Sigma_ab J_p' + W^-1       Sigma_ab: aprilsam_amd_marginals_joint_any's block, at the l_points of the last solver call
+ *     d2 = r' S^-1 r                      m = 1 (RANGE, BEARING) or 2 (RANGE_BEARING) degrees of freedom: chi^2 0.999 quantiles 10.83 / 13.82
+ * A range-bearing candidate and its xyt twin (W_xyt = blockdiag(G' W G, w_theta), a zero heading residual) agree: S = G S_xyt[:2, :2] G'
+ * exactly, so d2 is the d2 of the first two rows of aprilsam_amd_gate_xyt's S with the residual in polar coordinates; with the xyt
+ * residual itself for the twin whose z is (q + G^-1 r, predicted heading) -- the same z in Cartesian form to first order in r.
+ * Layout: z[2 i ..], W[4 i ..] (row-major 2 x 2), S[4 i ..] (row-major 2 x 2, or NULL).  A 1-row kind reads z[2 i] and W[4 i] only and
+ * writes S[4 i], with 0 in the three entries behind it.  If rho^2 == 0 at the current states G does not exist: d2 and the m x m entries
+ * of S are NaN for that candidate (no threshold, as for the factor).  Every distinct pair (a, b) is solved once, however many candidates
+ * name it.  With fixed nodes (section 20) a fixed landmark is gated with the observer's covariance alone.
+ *
+ * aprilsam_amd_associate_polar: m observations made from node `observer` against the L nodes landmarks[0..L): the L pairs are solved once
+ * (not m times), every (observation, landmark) entry is gated and reduced on the GPU.  Per observation i:
+ *     best[i]        the index INTO landmarks of the smallest d2 if that d2 <= gate1 (1-row kind) / gate2 (2-row kind), else -1: a new
+ *                    landmark.  Ties go to the lower index, so a landmark listed twice resolves to its first listing.
+ *     d2_best[i], d2_second[i]   the two smallest d2 over all L whatever the gate says (NaN entries skipped); +inf where fewer than one /
+ *                    two exist: the caller's ambiguity test
+ *     d2[i L + l]    the whole matrix, or NULL
+ * This is nearest-neighbour association: two observations may choose the same landmark.
+ * Both return >= 0: the number of candidates / of (observation, landmark) entries that were unavailable because rho^2 == 0; or the codes
+ * of aprilsam_amd_gate_xyt: -1 no retained factor; -12 sharded param, asymmetric W in the factorised graph, a W that is not symmetric
+ * positive definite; -13 a null argument, a negative count, a kind outside the three, a == b or the observer among the
+ * landmarks, a non-finite z or W entry that is read, a non-finite gate, a node id out of range of the factorised system or of graph;
+ * -14 no HIP device.  What can be judged without the graph (null, counts, kinds, a == b, z, W, gates) is judged before a device is asked
+ * for.  A refusal writes nothing and leaves plan, factor and Sigma alone.  n == 0, m == 0 or L == 0 return 0; with L == 0 every best is
+ * -1 and d2_best, d2_second are +inf.  Two calls give the same bits, and the matrix equals aprilsam_amd_gate_polar on the expanded list
+ * bit for bit. */
+int aprilsam_amd_gate_polar(april_graph_t *graph, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, const int *kind,
+                            const double *z, const double *W, double *d2, double *S);
+int aprilsam_amd_associate_polar(april_graph_t *graph, april_graph_cholesky_param_t *param, int observer, int m, const int *kind, const double *z,
+                                 const double *W, int L, const int *landmarks, double gate1, double gate2, double *d2, int *best,
+                                 double *d2_best, double *d2_second);
+/* debug, host only, no device: d2 and S (4 doubles, laid out as above) of one candidate at poses pa, pb with the 6 x 6 joint block cov36
+ * (row-major, a's unknowns first) -- the function host and kernels share.  0; 1 when rho^2 == 0 (NaN written); -13 on a bad argument */
+int aprilsam_amd_debug_polar_gate(int kind, const double *pa, const double *pb, const double *z, const double *W, const double *cov36,
+                                  double *d2, double *S4);
+
 /* ---- fixed nodes: poses held constant ------------------------------------------------------------------------------
  * A library-made xyt node (april_graph_node_xyt_create) is free or FIXED.  With Phi the fixed set, a step solves the normal equations with
  * the rows and columns of Phi removed: in the assembled system every block (i, j) with i or j in Phi is zero, every right-hand-side segment
