@@ -135,6 +135,7 @@ static void batch_impl(april_graph_t *g, april_graph_cholesky_param_t *param) {
     c.st.error_code = 0;
     if (c.st.not_spd) {
         c.model.valid = false;
+        forget_factor_after_bad_pivot(c, "april_graph_cholesky");
         static bool warned = false;
         if (!warned) { fprintf(stderr, "aprilsam_amd: information matrix not positive definite; node states left untouched\n"); warned = true; }
     } else {
@@ -393,8 +394,7 @@ static void inc_impl(april_graph_t *g, april_graph_cholesky_param_t *param) {
     if (c.st.not_spd) {
         static bool warned = false;
         if (!warned) { fprintf(stderr, "aprilsam_amd: incremental system not positive definite; node states left untouched\n"); warned = true; }
-        c.inc.tail_ok = -1;                          // (a front stopped half-way: nothing to refactorise from)
-        c.inc.upd_ok = false;                        // (... nor to update)
+        forget_factor_after_bad_pivot(c, "april_graph_cholesky_inc");      // (a front stopped half-way: nothing to refactorise from, to update, or to solve with)
         return;
     }
     record_factor(c, reused ? FACT_EXTENDED : FACT_PLAN, gp);

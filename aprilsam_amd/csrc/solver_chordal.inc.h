@@ -96,7 +96,7 @@ static int initialize_chordal_impl(april_graph_t *g, april_graph_cholesky_param_
     const bool reused = prepare_plan(c, gp, g, true, false);
     flush_orientation(c, s);
     upload_factors(gp);
-    c.st.n_nodes = gp.N; c.st.n_factors = gp.F; c.st.symbolic_reused = reused; c.st.not_spd = 0;
+    c.st.n_nodes = gp.N; c.st.n_factors = gp.F; c.st.symbolic_reused = reused; c.st.not_spd = 0; c.st.error_code = 0;
     const int N = gp.N, F = gp.F, T = std::max(F, 2 * N), M = gp.n_max();
     set_small_attr();
     gp.mirror_sync = false; gp.lp_last_valid = false;

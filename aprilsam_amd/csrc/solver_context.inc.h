@@ -223,6 +223,8 @@ struct Context {
     // marginal covariances (solver_marginals.inc.h): what the last successful solver call left in d_pool (FACT_*), at which value of
     // epoch_steps; the Sigma pool (front pool layout) and the step it was computed for; launch tables built per plan
     int fact_kind = 0; long long fact_epoch = -1; bool fact_asym = false;
+    bool resident_stepped = false;                 // the current resident loop has enqueued a step (its failure record means something)
+    bool resident_failed = false;                  // a step of the current resident loop met a non-positive pivot (resident_sync saw it): resident_end writes nothing
     DBuf<double> d_sigma, d_sel_scr; DBuf<SelFront> d_sel_fd; DBuf<int> d_sel_i32, d_sel_q; DBuf<int4> d_sel_ent; HBuf<double> h_cov;
     long long fact_serial = 0;                     // factorisations recorded so far (only grows)
     std::vector<SelLevel> sel_levels; int sel_tab_kind = 0, sel_N = 0;

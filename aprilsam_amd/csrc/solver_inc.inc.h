@@ -844,10 +844,21 @@ static void check_guard(Context &c, hipStream_t s) {
     if (cnt[0]) fail(ERR_GUARD, "pool_guard: %d words of the guard bands were overwritten (one of them: the band behind front %d of %d)", cnt[0], cnt[1], c.n_guard);
 }
 static bool check_bad(Context &c) {
-    if (!c.h_bad.p[0]) { c.st.not_spd = 0; return false; }
+    if (!c.h_bad.p[0]) { c.st.not_spd = 0; if (c.st.error_code == ERR_NOT_SPD) c.st.error_code = 0; return false; }
     if (c.h_bad.p[0] == 9 || c.h_bad.p[2] == 9) fail(ERR_DEP_TIMEOUT, "a multi-level launch gave up waiting for a dependency flag (the fronts it waits for never finished)");
     c.st.not_spd = 1;
     return true;
+}
+
+// A numeric phase that met a non-positive pivot stopped with fronts half written: the front pool holds no factorisation any more, whatever the
+// param held before.  Nothing may refactorise a tail from it, update it in place, solve with it or answer a covariance query from it, and
+// april_graph_cholesky_inc returns silently until a batch step succeeded (no prior factorisation, aprilsam.c:382-383).  The plan stays: it
+// describes the graph, not the numbers.  The code goes where the header says (stats.error_code, aprilsam_amd_last_error).
+static void forget_factor_after_bad_pivot(Context &c, const char *who) {
+    c.have_fact = false; c.fact_kind = FACT_NONE;
+    c.inc.tail_ok = -1; c.inc.upd_ok = false;
+    c.st.not_spd = 1; c.st.error_code = ERR_NOT_SPD;
+    set_last_error(ERR_NOT_SPD, std::string(who) + ": a pivot was not positive (information matrix not positive definite); node states left untouched");
 }
 
 static void set_lambda(Context &c, GraphPack &gp, double lambda) {

@@ -25,7 +25,8 @@ static int resident_begin_impl(april_graph_t *g, april_graph_cholesky_param_t *p
     if (!c.have_events) { for (auto &e : c.ev) HIPCHECK(hipEventCreate(&e)); c.have_events = true; }
     for (int k = 0; k < NKERN; k++) { c.k_ms[k] = 0; c.k_calls[k] = 0; }
     c.lev_up_ms.clear(); c.lev_dn_ms.clear();
-    c.st.n_nodes = gp.N; c.st.n_factors = gp.F; c.st.symbolic_reused = reused; c.st.not_spd = 0;
+    c.st.n_nodes = gp.N; c.st.n_factors = gp.F; c.st.symbolic_reused = reused; c.st.not_spd = 0; c.st.error_code = 0;
+    c.resident_failed = false; c.resident_stepped = false;
     HIPCHECK(hipStreamSynchronize(gp.stream));
     return 0;
 }
@@ -43,6 +44,7 @@ static int resident_steps_impl(april_graph_t *g, april_graph_cholesky_param_t *p
     const int N = gp.N;
     set_small_attr();
     gp.mirror_sync = false;                           // (states move on the device only)
+    if (n > 0) c.resident_stepped = true;
     // every node is re-linearised at the state it has when a batch step begins (aprilsam.c:131-135): once here, and from then on the state
     // update of step i leaves the new states in the l_points as well (UpdArgs::lp_next) -- no 84 KB copy between two steps of the loop
     // (round 5: 0.232 -> 0.225 ms per M3500 iteration)
@@ -86,7 +88,8 @@ static int resident_sync_impl(april_graph_t *g, april_graph_cholesky_param_t *pa
         if (t >= 0 && t < c.plan.nF) fprintf(stderr, " (nsb %d nub %d level %d off %lld)", c.plan.f_nsb[t], c.plan.f_nub[t], c.plan.f_level[t], (long long)c.plan.f_off[t]);
         fprintf(stderr, "\n");
     }
-    return c.h_bad.p[0] ? -2 : 0;
+    if (c.h_bad.p[0]) { c.resident_failed = true; forget_factor_after_bad_pivot(c, "aprilsam_amd_resident_sync"); }
+    return c.h_bad.p[0] ? ERR_NOT_SPD : 0;
 }
 static double resident_chi2_impl(april_graph_t *g);
 double resident_chi2(april_graph_t *g) {
@@ -108,6 +111,24 @@ static int resident_end_impl(april_graph_t *g, april_graph_cholesky_param_t *par
     GraphPack &gp = pack_for(g);
     hipStream_t s = gp.stream;
     const int N = gp.N, F = gp.F;
+    // A step of the loop that met a non-positive pivot (seen by resident_sync, or standing in the device's failure record now: every step's
+    // linearisation clears it, so it speaks for the last step -- and for nothing when the loop ran no step: then it is not looked at) moved the device states of every pose its back substitution reached with finite
+    // numbers -- the healthy components of a graph with several.  None of that reaches the caller: the node objects, which the loop never wrote,
+    // stay as resident_begin found them (states, l_points, delta_X, UID), the param keeps its ordering, and no factorisation is recorded.
+    c.h_bad.need(4);
+    HIPCHECK(hipMemcpyAsync(c.h_bad.p, c.d_bad.p, 16, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    if (c.resident_failed || (c.resident_stepped && check_bad(c))) {
+        c.resident_failed = false;
+        gp.lp_last_valid = false; gp.mirror_sync = false;
+        c.model.valid = false;
+        forget_factor_after_bad_pivot(c, "aprilsam_amd_resident_end");
+        return ERR_NOT_SPD;
+    }
+    // A loop that ran no step moved nothing and factorised nothing: the node objects and the param stay as resident_begin found them, and so
+    // does the param's factorisation -- none after a call that met a non-positive pivot, whose half-written front pool (and the dx of its
+    // back substitution) must not be recorded as a factor or handed to the caller here.
+    if (!c.resident_stepped) { gp.lp_last_valid = false; c.model.valid = false; return 0; }
     HIPCHECK(hipMemcpyAsync(gp.h_state.p, gp.d_state.p, (size_t)24 * N, hipMemcpyDeviceToHost, s));
     // l_point: where the last step was linearised (resident_steps parked it); d_lp follows, so that mirror and device agree again
     if (gp.lp_last_valid && gp.d_lp_last.cap >= (size_t)3 * N) HIPCHECK(hipMemcpyAsync(gp.d_lp.p, gp.d_lp_last.p, (size_t)24 * N, hipMemcpyDeviceToDevice, s));
@@ -145,8 +166,8 @@ int batch_resident(april_graph_t *g, april_graph_cholesky_param_t *param, int it
         if (ms_out) ms_out[it] = now_ms() - t0;
         if (rc == 0 && chi2_out) chi2_out[it + 1] = resident_chi2(g);
     }
-    if (rc == 0) rc = resident_end(g, param);
-    return rc;
+    const int rc_end = resident_end(g, param);         // (after a failed step too: it leaves the graph alone and drops the factor)
+    return rc ? rc : rc_end;
 }
 // per-kernel profile of the instrumented passes since resident_begin + algorithmic work per ITERATION
 // per level of the assembly tree: HIP-event time of the instrumented passes since resident_begin (factorisation incl. assembly /

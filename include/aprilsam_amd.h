@@ -261,9 +261,24 @@ int aprilsam_amd_get_stats(const april_graph_cholesky_param_t *param, aprilsam_a
  *         returns NaN) -- nothing is ever computed on the host
  *    -15  internal inconsistency of the planner
  *    -16  debug option "pool_guard": a kernel wrote into the guard band behind a frontal array
- * in stats.error_code and in aprilsam_amd_last_error (most recent failure of the process; msg may be NULL).  The param's
- * cached plan and factorisation are dropped: the next april_graph_cholesky starts from scratch, april_graph_cholesky_inc
- * returns silently until then (no prior factorisation, aprilsam.c:382-383). */
+ * in stats.error_code and in aprilsam_amd_last_error (most recent failure of the process; msg may be NULL).  For every code but -2
+ * the param's cached plan and factorisation are dropped: the next april_graph_cholesky starts from scratch, april_graph_cholesky_inc
+ * returns silently until then (no prior factorisation, aprilsam.c:382-383).  After -2 only the factorisation goes (next paragraph).
+ * stats.not_spd and stats.error_code speak for the most recent solver call on the param: a call that succeeds resets both.
+ *
+ * What -2 leaves behind, per entry point.  The numeric phase stopped with fronts half written, so the param's
+ * FACTORISATION is dropped whatever it held before -- april_graph_cholesky_inc and april_graph_cholesky_inc_solver return silently, the
+ * covariance / gating / solve entry points return -1 and write nothing, aprilsam_amd_factorised_nodes returns -1 -- until an
+ * april_graph_cholesky succeeded; the PLAN is kept (it describes the graph, not the numbers), and a repaired graph gives the bits of a
+ * fresh graph and param.  param->ordering, nreordering, factor_num and delta_x are not written.
+ *   april_graph_cholesky        every node's state and delta_X untouched; l_point = state and UID = index ARE written, as the reference
+ *                               writes them before it factorises (aprilsam.c:131-135, 628)
+ *   april_graph_cholesky_inc    states, delta_X, l_points and UIDs untouched
+ *   aprilsam_amd_resident_*     sync returns -2; end returns -2 and writes nothing at all: the node objects stay as resident_begin found them,
+ *                               also where the failed step moved the device states of a healthy component of the graph (with or without
+ *                               a resident_sync before it).  A loop that ran no step records no factorisation: begin / end after a
+ *                               failed call leaves the param without one
+ *   aprilsam_amd_optimize_lm    the step is rejected and counted in rejected_not_spd (see there); not a failure of the call */
 int  aprilsam_amd_last_error(char *msg, int cap);
 void aprilsam_amd_clear_error(void);
 

@@ -5,6 +5,16 @@ objective is F(x) = sum_f r_f' W_f r_f (no 0.5), a max factor contributing min_k
 Each iteration selects the max-factor components at x, solves (sum J'WJ + lambda I) h = sum J'W r with spsolve, forms
 x_t = x (+) h (theta wrapped), the model decrease pred = sum_f d_f' W_f (2 r_f - d_f), and applies Nielsen's rule and the stop tests
 with the device's latch.
+
+With spd_check (a function: dense matrix -> the pivots of its LDL' without pivoting; the tests pass pivot_placement.ldl_pivots) the model also
+takes the device's other rejection (k_lm_decide: `not_spd`): a system sum J'WJ + lambda I with a non-positive
+pivot is not solved, the step is rejected (lambda <- lambda nu, nu <- 2 nu) and counted in rejected_not_spd.  Positive definiteness is decided
+by the sign of the smallest pivot of a dense LDL' (tests/support/pivot_placement.py: by Sylvester's law the count of negative pivots does not
+depend on the elimination order); `margins` records min_j |d_j| / A_jj per iteration, so that a test can keep every decision away from
+rounding.  The model eliminates in NODE order, the device in its plan's order: the sign of the decision is the same, the margin is not --
+each pivot of the other order has its own size -- so a margin says how far THIS order's decision is from rounding, and the tests ask for one
+thousands of times the float64 pivot error (pivot_placement.LM_MARGIN) to leave room for the other.
+Dense, O(n^3) per iteration: for graphs of a few hundred unknowns.
 """
 import numpy as np
 import scipy.sparse as sp
@@ -118,18 +128,26 @@ def gn_steps(x, plain, steps, lam=0.0, mixes=()):
     return np.array(Fs), x
 
 
-def optimize(x0, plain, mixes=(), max_iters=50, lambda0=1e-4, lambda_max=1e16, eta=0.0, ftol=1e-10, xtol=1e-10):
-    """the device's run: dict(status, iterations, accepted, F_initial, F_final, lambda_final, x, dx, trace [it, 4], xs: x after every
-    iteration)"""
+def optimize(x0, plain, mixes=(), max_iters=50, lambda0=1e-4, lambda_max=1e16, eta=0.0, ftol=1e-10, xtol=1e-10, spd_check=False):
+    """the device's run: dict(status, iterations, accepted, rejected_not_spd, F_initial, F_final, lambda_final, x, dx, trace [it, 4], xs: x
+    after every iteration, margins: see the module docstring (spd_check only)); spd_check: None / False, or the pivots function"""
     x = np.array(x0, float, copy=True)
     F = cost(x, plain, mixes)
     F0, lam, nu = F, lambda0, 2.0
     status, it, accepted = 0, 0, 0
     trace, xs, dx = [], [], None
+    rejected_not_spd, margins = 0, []
     while status == 0:
         fa, fb, z, W = _concat(plain, selected(x, mixes) if mixes else None)
         A, B = system(x, fa, fb, z, W, lam)
-        h = spla.spsolve(A, B)
+        not_spd = False
+        if spd_check:
+            Ad = A.toarray()
+            d = spd_check(Ad)
+            not_spd = bool(np.isnan(d).any() or np.min(d) <= 0)
+            margins.append(float(np.nanmin(np.abs(d) / np.abs(np.diag(Ad)))))
+            rejected_not_spd += not_spd
+        h = np.full(len(B), np.nan) if not_spd else spla.spsolve(A, B)
         rejected = bool(np.isnan(h).any())
         xt = retract(x, h)
         Ft = cost(xt, plain, mixes) if not rejected else np.nan
@@ -164,7 +182,7 @@ def optimize(x0, plain, mixes=(), max_iters=50, lambda0=1e-4, lambda_max=1e16, e
             status = STALLED
         if status == 0 and it >= max_iters:
             status = MAX_ITERS
-    return dict(status=status, iterations=it, accepted=accepted, F_initial=F0, F_final=F, lambda_final=lam, x=x, dx=dx,
+    return dict(status=status, iterations=it, accepted=accepted, rejected_not_spd=rejected_not_spd, margins=np.array(margins), F_initial=F0, F_final=F, lambda_final=lam, x=x, dx=dx,
                 trace=np.array(trace, float).reshape(-1, 4), xs=xs)
 
 

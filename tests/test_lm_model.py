@@ -143,3 +143,39 @@ def test_optimize_lm_refuses_bad_options_without_touching_the_graph(lib):
         assert lib.last_error()[0] == -13
     assert (g.states() == before).all()
     p.destroy(); g.destroy()
+
+
+def test_rejection_of_a_step_whose_system_is_not_positive_definite(lib):
+    """the chain with one prior of negative information (tests/support/pivot_placement.py): the model rejects exactly the iterations whose
+    sum J'WJ + lambda I has a negative eigenvalue, counts them, multiplies lambda by nu and doubles nu, as k_lm_decide does; every decision
+    stays clear of rounding; and on a positive definite graph the check changes nothing"""
+    from tests.support import pivot_placement as pp
+    prm = lib.new_param(); lam0 = float(prm.c.tikhanov); prm.destroy()
+    pl = pp.placement(lib, "chain", 16, lam0)
+    seqs = []
+    for k, delta in pp.LM_CASES:
+        st, fa, fb, z, W = pl.case(*pl.classes()[k], delta=delta)["arr"]
+        r = M.optimize(st, (fa, fb, z, W), max_iters=pp.LM_ITERS, spd_check=pp.ldl_pivots)
+        t = r["trace"]
+        assert r["iterations"] == pp.LM_ITERS and r["margins"].min() > pp.LM_MARGIN
+        nspd = np.isnan(t[:, 0])
+        assert nspd[0] and r["rejected_not_spd"] == int(nspd.sum()) >= 4 and r["accepted"] == int(t[:, 3].sum()) >= 4
+        assert not np.any(nspd & (t[:, 3] == 1))
+        lam, nu = 1e-4, 2.0
+        x = np.array(st, float)
+        for i in range(len(t)):
+            assert t[i, 2] == lam
+            A, _ = M.system(x, fa, fb, z, W, lam)
+            assert (np.linalg.eigvalsh(A.toarray())[0] <= 0) == bool(nspd[i]), (k, i)
+            if t[i, 3] == 1:
+                u = 2.0 * t[i, 1] - 1.0
+                lam, nu = lam * max(1.0 / 3.0, 1.0 - u * u * u), 2.0
+            else:
+                lam, nu = lam * nu, 2.0 * nu
+            x = r["xs"][i]
+        assert r["lambda_final"] == lam
+        seqs.append("".join("N" if a else ("A" if b else "r") for a, b in zip(nspd, t[:, 3] == 1)))
+    assert seqs == ["NNNNAAAArAArrArr", "NNNNNNNAAAAANNAr", "NNNNNNANANNAANNA"], seqs
+    st, fa, fb, z, W = pp.graph("chain")
+    a = M.optimize(st, (fa, fb, z, W), max_iters=6, spd_check=pp.ldl_pivots); b = M.optimize(st, (fa, fb, z, W), max_iters=6)
+    assert a["rejected_not_spd"] == 0 and a["trace"].tobytes() == b["trace"].tobytes() and a["x"].tobytes() == b["x"].tobytes()
