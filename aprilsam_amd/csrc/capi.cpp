@@ -211,6 +211,22 @@ int aprilsam_amd_up_schedule(int nF, const int *parent, const int *nsb, const in
     return (int)v.size();
 }
 
+// The owner wave of every child block's destination column (plan.h: asm_owners), parent by parent, for a tree given as plain arrays
+int aprilsam_amd_asm_owners(int nF, const int *parent, const int *nsb, const int *nub, const long long *rows_ptr, const int *rel, int nw, int *owner) {
+    if (nF < 0 || !parent || !nsb || !nub || !rows_ptr || !rel || !owner || nw < 1 || rows_ptr[0] < 0) return -100;
+    std::vector<int64_t> rp((size_t)nF + 1);
+    for (int t = 0; t <= nF; t++) rp[t] = rows_ptr[t];
+    std::vector<std::vector<int>> kids((size_t)nF);
+    for (int t = 0; t < nF; t++) {
+        if (nsb[t] < 0 || nub[t] < 0 || rp[t + 1] - rp[t] != nub[t] || parent[t] < -1 || parent[t] >= nF || (parent[t] >= 0 && parent[t] <= t)) return -100;
+        if (parent[t] >= 0) kids[parent[t]].push_back(t);
+        for (int j = 0; j < nub[t]; j++) owner[rp[t] + j] = -1;
+    }
+    for (int p = 0; p < nF; p++)
+        if (!kids[p].empty()) asam::asm_owners(nsb[p] + nub[p], nw, kids[p].data(), (int)kids[p].size(), rp.data(), nub, rel, owner);
+    return 0;
+}
+
 long long aprilsam_amd_plan_query(const aprilsam_amd_plan_t *plan, const char *what, long long **out) {
     std::string k(what);
     if (k.compare(0, 3, "bd_") == 0 || k.compare(0, 3, "rd_") == 0) asam::build_gather_lists(const_cast<asam::Plan &>(plan->P));

@@ -47,6 +47,17 @@ constexpr int PROF_XCD_UP = 12, PROF_XCD_DN = 13;     // ... slots of the XCD a 
 // ... and of the hand-over of x in a multi-level back substitution (prof_mode 2, tools/backsolve_times.py): the front's last x store issued,
 // its stores drained and the workgroup through the barrier (flag protocols), its flag store issued
 constexpr int PROF_X_STORED = 14, PROF_X_DRAINED = 11, PROF_X_FLAG = 15;
+// ... and of the extend-add behind the wait of a multi-level factorisation (prof_mode 4: wave 0; 5: per stamp the LAST wave to get there, which is the
+// wave with the longest work list unless something else holds one up; tools/front_times.py --process).  They take the pivot chain's slots, which
+// stay empty in these modes; slot 11 is the wait itself.  "data back" and "adds done" drain the wave's counters first -- in these modes only.
+// A library built with -DAPRILSAM_AMD_EA_STAMPS only: even switched off at run time, the stamps' branches inside the trip loop cost the resident
+// step on M3500 1 % (0.1872 -> 0.1892 ms, profiles/extend_add.txt section 1), so the product is compiled without them.
+constexpr int PROF_EA_ISSUED = 8, PROF_EA_DATA = 9, PROF_EA_ADDS = 10, PROF_EA_REST = 14, PROF_EA_END = 15;
+#ifdef APRILSAM_AMD_EA_STAMPS
+constexpr bool EA_STAMPS = true;
+#else
+constexpr bool EA_STAMPS = false;
+#endif
 // the XCD this workgroup runs on (0-7): a hardware register read, for the profile stamps only -- placement is never relied upon
 __device__ __forceinline__ int xcc_id() { return __builtin_amdgcn_s_getreg(20 | (0 << 6) | ((4 - 1) << 11)) & 7; }     // hwreg(HW_REG_XCC_ID, 0, 4)
 constexpr int TPB = 256;          // threads per workgroup (4 waves)
@@ -67,7 +78,11 @@ struct FrontDesc {
     int parent;
     int dinv0;                     // first slot (NB x NB doubles each) of this front's persistent inverse diagonal blocks, -1: none (see k_block_chain)
     int prim1, prim2;              // 1 + index (in this front's child range) of the children with the largest / second largest update block, 0: none (see k_assemble_big)
-    int pad[2];
+    int own_nw;                    // waves per workgroup that DevPlan::f_own was built for over this front's children (option asm_balance), 0: no table -- column mod waves
+                                   // INVARIANT: nonzero only while the block maps of ALL of this front's children lie inside the table, [DevPlan::own_lo, own_hi).  The kernel
+                                   // picks table or modulo per map entry (slice_rel; the range test there only keeps the load inside the table), so children on both sides
+                                   // would give one column two owners: whoever re-stages any child's block map elsewhere sets 0 (solver_inc.inc.h: regenerated and tail fronts)
+    int pad;
 };
 static_assert(sizeof(FrontDesc) == 64, "FrontDesc must stay one cache line");
 // contributions of a destination: slots [src_begin, src_end) of Hc, or — for fronts regenerated by the
@@ -88,11 +103,12 @@ struct DevPlan {
     const DestRec *dest;
     const ChildRec *child;
     const int *f_rows, *f_rel;
+    const int *f_own; int own_lo, own_hi;   // parallel to f_rel, entries [own_lo, own_hi): the wave that owns the destination column of that child block in the parent's extend-add (FrontDesc::own_nw)
     const int *slot_blk, *slot_rhs;   // per factor: where k_linearize stores its 3 blocks / 2 rhs segments
     const int *src_idx;               // indirect source lists of regenerated fronts
     const double *lambda;         // per elimination position (block): Tikhonov term of its 3 diagonals
     long long *prof;              // debug: 8 wall-clock stamps (100 MHz) per front, or null
-    int prof_mode;                // 1: stamps of the factorisation kernels, 2: of the back substitution
+    int prof_mode;                // 1: stamps of the factorisation kernels, 2: of the back substitution, 3: of k_inc_one's chain, 4 / 5: of the extend-add behind the wait (PROF_EA_*)
     int schur_first_nub;          // panel-mode small fronts with at least this many update blocks assemble their update columns AFTER the Schur product (0: never; see front_small_body)
     // dependency flags of ALL multi-level launches carry the STEP NUMBER (see wait_flag): epoch = the counter the first kernel of every numeric
     // phase advances (k_linearize: a batch iteration; the prologue: an incremental step).  Nothing is ever reset.  Which children a front waits for:
@@ -543,13 +559,16 @@ constexpr int CAPQ = 64;                 // child records staged in LDS per fron
 // LDS for the staged child records + the work lists of nw waves
 __host__ __device__ constexpr int wl_bytes(int nw) { return CAPQ * 24 + nw * WCAP * 8 + nw * 64 * 8; }   // + one dummy double per lane
 
-// accumulate into the frontal array: plain read-modify-write in LDS; in HBM/L2 a no-return FP64 atomic add executed
-// by the L2 (fire and forget: no load latency on the critical path).  Every destination element is only ever
-// touched by ONE wave, in program order, so the sum order -- and the bits of the result -- are fixed by the plan.
+// accumulate into the frontal array: a no-return FP64 atomic add in both places, executed by the LDS (ds_add_f64) or by the L2
+// (fire and forget: no load latency, and no read / wait / add / write round trip per element, on the critical path).  Every
+// destination element is only ever touched by ONE wave, whose LDS operations execute in issue order and whose L2 atomics to one
+// address do, so the sum order -- and the bits of the result -- are fixed by the plan.  (Written as `*p += v` the compiler had to
+// assume that consecutive adds may alias -- masked lanes do share their dummy slot -- and serialised them: one LDS round trip each.)
+__device__ __forceinline__ void lds_add(double *p, double v) { (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 template <bool GLOBAL_DST>
 __device__ __forceinline__ void front_add(double *p, double v) {
     if (GLOBAL_DST) unsafeAtomicAdd(p, v);
-    else *p += v;
+    else lds_add(p, v);
 }
 
 // Dependency flags of the multi-level ("persistent") launches: a front that has finished publishes its flag after a device-scope
@@ -692,7 +711,7 @@ __device__ __forceinline__ void assemble_front(const DevPlan &P, const FrontDesc
     auto put = [&](int col, int row, double v) { if (col < csplit) dstL[(size_t)col * ldL + row] = v; else dstG[(size_t)col * ldG + row] = v; };
     auto add_plain = [&](int col, int row, double v) { if (col < csplit) dstL[(size_t)col * ldL + row] += v; else dstG[(size_t)col * ldG + row] += v; };
     auto add_child = [&](int col, int row, double v) {      // col is wave-uniform
-        if (col < csplit) front_add<false>(dstL + (size_t)col * ldL + row, v); else front_add<true>(dstG + (size_t)col * ldG + row, v);
+        if (MODE != ASM_GLOBAL && col < csplit) front_add<false>(dstL + (size_t)col * ldL + row, v); else front_add<true>(dstG + (size_t)col * ldG + row, v);
     };
     constexpr int NW = NT / 64;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
@@ -746,7 +765,8 @@ __device__ __forceinline__ void assemble_front(const DevPlan &P, const FrontDesc
     if (pf && tid == 0) pf[5] = wall_clock64();
     // 3. children's update matrices (extend-add).  Destination block column b belongs to wave b mod NW, which alone
     //    adds every child's contribution to it, child after child -- no two waves ever touch the same element, so
-    //    there is no barrier and no atomic in LDS, and the order of the sum is fixed.
+    //    there is no barrier, and the order of the sum is fixed.  (Or to the wave the plan names, DevPlan::f_own: the same
+    //    one wave per column, chosen so that the waves' lists are even -- for the workgroup width the table was built for.)
     //    (a) fill: per child, lanes test its blocks (rel = child block -> block of this front) and compact the
     //        owned ones into the wave's work list in LDS: entry = (child, child block, destination block);
     //    (b) process: two entries per trip -- 6 coalesced column loads and 2 row-map loads in flight -- lanes run
@@ -807,11 +827,11 @@ __device__ __forceinline__ void assemble_front(const DevPlan &P, const FrontDesc
             const int r = T.r0[u] + lane;
             const bool inr = r < T.nrow[u];
             const int du = (T.rc[u] < T.nrow[u] - 1) ? 3 * T.d[u] + T.rc[u] % 3 : rhs_row;      // destination row
-            if (T.col[u] < csplit) {                 // wave-uniform
+            if (MODE != ASM_GLOBAL && T.col[u] < csplit) {                 // wave-uniform
 #pragma unroll
                 for (int c3 = 0; c3 < 3; c3++) {
                     const int o = (inr && r >= T.cc[u] + c3) ? (T.col[u] + c3) * ldL + du : dummy_off;
-                    dstL[o] += T.v[3 * u + c3];
+                    lds_add(dstL + o, T.v[3 * u + c3]);
                 }
             } else {
 #pragma unroll
@@ -849,39 +869,57 @@ __device__ __forceinline__ void assemble_front(const DevPlan &P, const FrontDesc
     };
     // (two trips in flight -- the loads of trip k + 1 issued before the adds of trip k -- was measured slower: the second
     // register set costs occupancy on the wide levels and a spill in the 1024-thread variant)
-    auto process = [&](int n) {
+    const int ea_prof = (EA_STAMPS && pf && P.prof_mode >= 4 && lane == 0 && (P.prof_mode == 5 || wv == 0)) ? P.prof_mode : 0;      // debug stamps PROF_EA_*
+    auto ea_stamp = [&](int slot) {
+        if (ea_prof == 4) pf[slot] = wall_clock64();
+        else atomicMax((unsigned long long *)(pf + slot), (unsigned long long)wall_clock64());
+    };
+    // (tail: the list holds a block with rows beyond 128 -- only then is there anything for rest() to do: its walk over the items costs two dependent
+    // LDS reads each between one trip's adds and the next trip's loads, and M3500's plan has no such block at all)
+    auto process = [&](int n, bool tail, bool stamps) {
         for (int i = 0; i < n; i += TE) {
             Trip T;
             load_trip(i, n, T);
+            if (stamps && i == 0) { if (ea_prof) ea_stamp(PROF_EA_ISSUED); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); if (ea_prof) ea_stamp(PROF_EA_DATA); }
             apply_trip(T);
-            rest(i, n);
+            if (stamps && i == 0) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); if (ea_prof) ea_stamp(PROF_EA_ADDS); }
+            if (tail) rest(i, n);
+            if (stamps && i == 0 && ea_prof) ea_stamp(PROF_EA_REST);
         }
+        if (stamps && ea_prof) ea_stamp(PROF_EA_END);
     };
     // (a) + (b) as ONE loop with one copy of each (code size: the instruction cache is shared by the whole CU):
     // fill until the list cannot take another 32-block slice (at most 64 items), process, resume where fill stopped.
     // The block map of the next slice is requested before the current one is compacted.
     int qn = 0, c0n = 0;                              // next slice: child qn, blocks [c0n, c0n + 32)
-    auto slice_rel = [&](int q, int c0, int *cnu_out) -> int {
+    const bool balanced = D.own_nw == NW;            // the plan's owners hold for this workgroup width; else column mod waves
+    auto slice_rel = [&](int q, int c0, int *cnu_out, int *own_out) -> int {
+        *own_out = -1;
         if (q >= min(nch, g0 + CAPQ)) { *cnu_out = 0; return -1; }
         const ChildRec c = rec_of(q);
         if (q == skip_child || q == skip_child2) { *cnu_out = 0; return -1; }      // (a child without blocks: the fill loop moves on)
         *cnu_out = c.cnu;
-        const int jb = c0 + lane;
-        return (lane < 32 && jb < c.cnu) ? P.f_rel[c.rel_begin + jb] : -1;
+        const int jb = c0 + lane, e = c.rel_begin + jb;
+        const bool in = lane < 32 && jb < c.cnu;
+        // (same address arithmetic as the map entry: the two loads travel together.  A balanced front has ALL its children's maps inside the table --
+        // FrontDesc::own_nw's invariant -- so the range test never splits a front between the two rules; it only bounds the load)
+        if (balanced && in && e >= P.own_lo && e < P.own_hi) *own_out = P.f_own[e];
+        return in ? P.f_rel[e] : -1;
     };
-    int cnu_cur = 0;
-    int rv_cur = slice_rel(0, 0, &cnu_cur);
-    bool waited = false;
+    int cnu_cur = 0, ow_cur = -1;
+    int rv_cur = slice_rel(0, 0, &cnu_cur, &ow_cur);
+    bool waited = false, ea_now = false;            // ea_now: this round's process() is the one right behind the wait and stamps are wanted
     for (;;) {
         const int qend = min(nch, g0 + CAPQ);
         int n = 0;
+        bool tail = false;                             // wave-uniform: one of this list's blocks has a third 64-row pass (rest())
         while (qn < qend && n + 64 <= WCAP) {
             int qx = qn, cx = c0n + 32;                // the slice after this one
             if (cx >= cnu_cur) { qx++; cx = 0; }
-            int cnu_nxt = 0;
-            const int rv_nxt = slice_rel(qx, cx, &cnu_nxt);
+            int cnu_nxt = 0, ow_nxt = -1;
+            const int rv_nxt = slice_rel(qx, cx, &cnu_nxt, &ow_nxt);
             const int jb = c0n + lane, rv = rv_cur;
-            const bool own = rv >= bc0 && rv < bc1 && ((rv & (NW - 1)) == wv);
+            const bool own = rv >= bc0 && rv < bc1 && ((ow_cur >= 0 ? ow_cur : (rv & (NW - 1))) == wv);
             const unsigned long long mask = __ballot(own);
             if (own) mywl[n + __popcll(mask & ((1ull << lane) - 1ull))] = make_int2(qn, jb | (rv << 16));
             n += __popcll(mask);
@@ -889,7 +927,8 @@ __device__ __forceinline__ void assemble_front(const DevPlan &P, const FrontDesc
             const unsigned long long mask2 = __ballot(tall);
             if (tall) mywl[n + __popcll(mask2 & ((1ull << lane) - 1ull))] = make_int2(qn | (1 << 30), jb | (rv << 16));
             n += __popcll(mask2);
-            qn = qx; c0n = cx; rv_cur = rv_nxt; cnu_cur = cnu_nxt;
+            tail = tail || __ballot(own && (3 * cnu_cur + 1 - 3 * jb > 128)) != 0;
+            qn = qx; c0n = cx; rv_cur = rv_nxt; cnu_cur = cnu_nxt; ow_cur = ow_nxt;
         }
         if (pf && tid == 0 && pf[6] == 0) { pf[6] = wall_clock64(); pf[7] = n; }
         // multi-level launch: everything up to here -- zero fill, factor blocks, the first work lists (static block maps) --
@@ -906,15 +945,17 @@ __device__ __forceinline__ void assemble_front(const DevPlan &P, const FrontDesc
             asm volatile("" ::: "memory");
             waited = true;
             if (pf && tid == 0) pf[11] = wall_clock64();
+            ea_now = EA_STAMPS && pf && P.prof_mode >= 4;
         }
-        process(n);
+        process(n, tail, EA_STAMPS && ea_now);
+        ea_now = false;
         if (qn >= nch) break;
         if (qn >= qend) {                           // next group of child records (every wave gets here once per group)
             __syncthreads();
             g0 += CAPQ;
             if (tid < min(nch - g0, CAPQ)) crs[tid] = P.child[D.ch_begin + g0 + tid];
             __syncthreads();
-            rv_cur = slice_rel(qn, 0, &cnu_cur);
+            rv_cur = slice_rel(qn, 0, &cnu_cur, &ow_cur);
         }
     }
     __syncthreads();
@@ -1272,7 +1313,7 @@ __device__ __forceinline__ void front_small_body(const DevPlan &P, const int t, 
         assemble_front<NT, ASM_LDS>(P, D, pool, Hc, 0, nbc, true, S, ld, nullptr, 0, wl, P.prof ? P.prof + (size_t)t * PROF_SLOTS : nullptr, wflags, bad, ev);
         if (P.prof && threadIdx.x == 0) P.prof[(size_t)t * PROF_SLOTS + 1] = wall_clock64();
         // rank-3 steps measured ~1.6x faster than the NB=32 blocked variant on LDS-resident fronts (chain-bound)
-        factor_front_blk<NT>(S, ld, nsb, nbc, bad, (double *)wl, -1, P.prof ? P.prof + (size_t)t * PROF_SLOTS : nullptr);
+        factor_front_blk<NT>(S, ld, nsb, nbc, bad, (double *)wl, -1, (P.prof && (!EA_STAMPS || P.prof_mode < 4)) ? P.prof + (size_t)t * PROF_SLOTS : nullptr);
         if (P.prof && threadIdx.x == 0) P.prof[(size_t)t * PROF_SLOTS + 2] = wall_clock64();
         // store the block-lower trapezoid back to HBM: the update block first -- it is all the parent waits for -- then
         // the L panel, which nobody reads before the back substitution
@@ -1297,7 +1338,7 @@ __device__ __forceinline__ void front_small_body(const DevPlan &P, const int t, 
         if (schur_first) assemble_front<NT, ASM_SPLIT>(P, D, pool, Hc, 0, nsb, false, S, ld, Fg, R, wl, P.prof ? P.prof + (size_t)t * PROF_SLOTS : nullptr, wflags, bad, ev);
         else assemble_front<NT, ASM_SPLIT>(P, D, pool, Hc, 0, nbc, true, S, ld, Fg, R, wl, P.prof ? P.prof + (size_t)t * PROF_SLOTS : nullptr, wflags, bad, ev);   // own columns -> LDS, update columns -> HBM/L2
         if (P.prof && threadIdx.x == 0) P.prof[(size_t)t * PROF_SLOTS + 1] = wall_clock64();
-        factor_front_blk<NT>(S, ld, nsb, nbc, bad, (double *)wl, nsb, P.prof ? P.prof + (size_t)t * PROF_SLOTS : nullptr);
+        factor_front_blk<NT>(S, ld, nsb, nbc, bad, (double *)wl, nsb, (P.prof && (!EA_STAMPS || P.prof_mode < 4)) ? P.prof + (size_t)t * PROF_SLOTS : nullptr);
         if (P.prof && threadIdx.x == 0) P.prof[(size_t)t * PROF_SLOTS + 2] = wall_clock64();
         if (schur_first) {
             lds_panel_syrk<NT, 2>(S, ld, 0, ns, ns, C, R - 2, Fg, R);

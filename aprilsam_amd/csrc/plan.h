@@ -119,6 +119,17 @@ int up_schedule_check(const std::vector<int> &list, const std::vector<int> &base
 // the model's makespan (us) of any such list, -1 where a child does not precede its parent
 double up_makespan(const std::vector<int> &list, const int *parent, const int *nsb, int nF, int cap);
 
+// ---- owners of the extend-add's destination columns (option asm_balance) -----------------------------------------------------------------
+// A front's extend-add gives every destination block column to ONE wave of the workgroup, which adds every child's contribution to it, child
+// after child: the order of each sum is fixed whoever the owner is, and the time behind the wait for the children is set by the wave with the
+// longest work list.  Column b mod nw leaves the lists uneven; here the columns of ONE parent (nbc of them, `kids` its children) are taken by
+// decreasing item count and each goes to the least loaded of the nw waves -- ties to the lower column, then to the lower wave.  An item is what
+// the kernel's fill loop queues (asm_items: one per child block, one more where the block has a second 64-row pass).  owner[e] for every entry e
+// of the children's block maps (the index of `rel`, rows_ptr[child] + block), -1 for an entry that maps outside the parent.  A parent whose
+// longest list would come out longer than under b mod nw keeps b mod nw.
+inline int asm_items(int cnu, int jb) { return 1 + (3 * cnu + 1 - 3 * jb > 64 ? 1 : 0); }
+void asm_owners(int nbc, int nw, const int *kids, int n_kids, const int64_t *rows_ptr, const int *nub, const int *rel, int *owner);
+
 // ---- pieces, exposed for tests --------------------------------------------------------------------------
 struct NDTree {
     struct Node { std::vector<int> verts; std::vector<int> children; };

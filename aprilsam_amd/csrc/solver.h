@@ -43,6 +43,7 @@ struct Options {
     int persist_leaves = 1;       // ... and level 0 inside the back substitution's launch where only persist_max_fronts kept it out (upload_plan has the rule): the leaves wait for their parents' x with their L panel in LDS, one k_backsolve_w per step instead of two; 0 = level 0 keeps its own launch.  Measured on M3500: hop into level 0 10-16 -> 0.7 us, resident step 0.2026 -> 0.1978 ms median (profiles/persist_leaves.txt); the up-sweep's half: persist_up
     int persist_up = 2;           // ... and level 0 inside the factorisation's launch under the same rule, where no front changes between its full-LDS and its panel form (upload_plan): 0 = its own launch; 1 = joined, level order; 2 = joined, descending remaining path to the root's end (a cost model's critical path is dispatched first); 3 = joined, the slot-aware list schedule (plan.h: up_schedule); 2 and 3 also order the one launch of graphs that never had two.  Measured on M3500, eight alternating runs against the parent commit: resident step 0.19808 -> 0.19570 (1) / 0.18774 (2) / 0.18812 ms (3) median, -5.2 % for 2, every run of 2 below every parent run; 2 and 3 cannot be told apart, the simpler one is the default (profiles/persist_up.txt)
     int xcd_place = 1;            // ... and their lists (and those of the level-0 launches below them) in an order where a front shares its costliest child's XCD (plan.h: xcd_place); 0 = level by level.  Measured on M3500: 0.2131 -> 0.2102 ms (the back substitution's two launches alone: 0.2113)
+    int asm_balance = 1;          // extend-add of the small fronts: a parent's block columns are given to its workgroup's waves by item count, longest first to the least loaded wave (plan.h: asm_owners), instead of column mod waves; 0 = modulo everywhere.  The sums keep their order either way: the results are bitwise equal
     int tail_poses = 28;          // incremental path: own poses per tail front (>= 8; measured on the M3500 demo: 24 / 28 / 32 -> 546 / 530 / 528 ms total, median 0.038 / 0.0385 / 0.040 ms)
     int blk_backsolve = 1;        // wide multi-workgroup fronts: back substitution 128 columns at a time by a chain workgroup + helpers (0: k_backsolve_gemv + k_backsolve_t)
     int wave_backsolve = 1;       // multi-level back substitution: column-per-lane kernel (0: the per-32-column-block kernel)

@@ -85,7 +85,7 @@ static const OptionDef OPTION_TABLE[] = {
     { "wave_backsolve", &Options::wave_backsolve, 0, false }, { "tagged_x", &Options::tagged_x, 0, false, 2 }, { "blk_backsolve", &Options::blk_backsolve, 0, false }, { "tail_poses", &Options::tail_poses, 8, false },
     { "batch_extend", &Options::batch_extend, 0, true }, { "extend_tail_fronts", &Options::extend_tail_fronts, 0, true }, { "mem_cap_mb", &Options::mem_cap_mb, 0, true }, { "solve_chunk_cols", &Options::solve_chunk_cols, 0, true },
     { "pool_guard", &Options::pool_guard, 0, false }, { "amalg", &Options::amalg, 0, false }, { "amalg_max", &Options::amalg_max, 1, false }, { "pool_poison", &Options::pool_poison, 0, false }, { "skip_flag_waits", &Options::skip_flag_waits, 0, false },
-    { "polar_on_host", &Options::polar_on_host, 0, false, 1 },
+    { "polar_on_host", &Options::polar_on_host, 0, false, 1 }, { "asm_balance", &Options::asm_balance, 0, false, 1 },
 };
 static const OptionDef *find_option(const char *name) {
     for (const OptionDef &d : OPTION_TABLE) if (!strcmp(d.name, name)) return &d;

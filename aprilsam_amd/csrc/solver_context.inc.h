@@ -563,6 +563,10 @@ static void upload_plan(Context &c, hipStream_t s, const ShardLayout *lay = null
     std::vector<int> i32;
     auto put32 = [&](const std::vector<int> &v) { size_t o = i32.size(); i32.insert(i32.end(), v.begin(), v.end()); if (v.empty()) i32.push_back(0); return o; };
     size_t o_rows = put32(P.f_rows), o_rel = put32(P.f_rel);
+    // the extend-add's owner table, parallel to f_rel: filled below, once the levels know their workgroup widths.  Nobody reads it with asm_balance
+    // off or in a sharded layout (no front gets an own_nw there): then it takes no room in the arena
+    const bool own_tab = g_opt.asm_balance && !lay && !P.f_rel.empty();
+    const size_t o_own = own_tab ? put32(std::vector<int>(P.f_rel.size(), -1)) : 0;
     size_t o_sb = put32(P.slot_blk); i32.resize(i32.size() + (size_t)3 * INC_FACT_, -1);      // room for factors added incrementally
     size_t o_sr = put32(P.slot_rhs); i32.resize(i32.size() + (size_t)2 * INC_FACT_, -1);
     c.inc.i32_used = (long long)i32.size(); c.inc.dest_used = (long long)P.dest.size(); c.inc.child_used = (long long)P.ch_idx.size();
@@ -579,6 +583,8 @@ static void upload_plan(Context &c, hipStream_t s, const ShardLayout *lay = null
     DevPlan &d = c.dp;
     d.nF = P.nF;
     d.fd = c.d_fd.p; d.dest = c.d_dest.p; d.child = c.d_child.p;
+    d.f_own = nullptr; d.own_lo = 0; d.own_hi = 0;
+    if (own_tab) { d.f_own = c.d_i32.p + o_own - o_rel; d.own_lo = (int)o_rel; d.own_hi = (int)(o_rel + P.f_rel.size()); }      // (indexed like f_rel: ChildRec::rel_begin + block)
     d.f_rows = c.d_i32.p; d.f_rel = c.d_i32.p; d.slot_blk = c.d_i32.p + o_sb; d.slot_rhs = c.d_i32.p + o_sr; d.src_idx = c.d_i32.p;
     c.inc.o_rows = (long long)o_rows; c.inc.o_rel = (long long)o_rel;
     d.lambda = c.d_lambda.p;
@@ -601,6 +607,23 @@ static void upload_plan(Context &c, hipStream_t s, const ShardLayout *lay = null
     for (int l = 0; l < P.nLevels; l++) {
         std::vector<int> fr(P.lev_fronts.begin() + P.lev_ptr[l], P.lev_fronts.begin() + P.lev_ptr[l + 1]);
         build_level(c.levels[l], fr, tab, [&](int t, int *nsb, int *nub) { *nsb = P.f_nsb[t]; *nub = P.f_nub[t]; }, [](int) { return true; });
+    }
+    // Owners of the extend-add's destination columns (option asm_balance, plan.h: asm_owners): per single-workgroup front, for the workgroup width
+    // of its level's launch -- which is the multi-level launches' width wherever they take the level in.  A launch of another width (k_inc_one,
+    // k_assemble_big's 256 threads) and a front without a table (multi-workgroup fronts, sharded layouts, fronts the incremental path regenerates
+    // or adds) give column b to wave b mod waves, as before.  One wave per column either way: the sums keep their order and their bits.
+    if (own_tab) {
+        std::vector<int> own(P.f_rel.size(), -1);
+        for (int l = 0; l < P.nLevels; l++) {
+            const LevelPlan &L = c.levels[l];
+            for (int k = 0; k < L.n_small; k++) {
+                const int t = tab[L.small_off + k];
+                if (P.ch_ptr[t + 1] == P.ch_ptr[t]) continue;
+                fd[t].own_nw = waves_of(L.small_nt);
+                asm_owners(P.f_nsb[t] + P.f_nub[t], fd[t].own_nw, P.ch_idx.data() + P.ch_ptr[t], P.ch_ptr[t + 1] - P.ch_ptr[t], P.f_rows_ptr.data(), P.f_nub.data(), P.f_rel.data(), own.data());
+            }
+        }
+        HIPCHECK(hipMemcpyAsync(c.d_i32.p + o_own, own.data(), own.size() * 4, hipMemcpyHostToDevice, s));      // (pageable source, like i32 above: staged before the call returns)
     }
     {   // persistent inverse diagonal blocks of the multi-workgroup fronts (k_block_chain leaves them, k_block_solve and
         // k_backsolve_blk use them): whole outer blocks per front

@@ -682,4 +682,35 @@ int up_schedule_check(const std::vector<int> &list, const std::vector<int> &base
     return 0;
 }
 
+// ---- owners of the extend-add's destination columns (plan.h: asm_owners) ----------------------------------------------------------------------
+void asm_owners(int nbc, int nw, const int *kids, int n_kids, const int64_t *rows_ptr, const int *nub, const int *rel, int *owner) {
+    std::vector<int> items((size_t)std::max(nbc, 0), 0), order, wave_of((size_t)std::max(nbc, 0), 0), load((size_t)std::max(nw, 1), 0);
+    for (int k = 0; k < n_kids; k++) {
+        const int c = kids[k];
+        for (int jb = 0; jb < nub[c]; jb++) {
+            const int b = rel[rows_ptr[c] + jb];
+            if (b >= 0 && b < nbc) items[b] += asm_items(nub[c], jb);
+        }
+    }
+    for (int b = 0; b < nbc; b++) if (items[b] > 0) order.push_back(b);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return items[a] > items[b]; });       // (stable: ties keep the lower column first)
+    for (int b : order) {
+        int w = 0;
+        for (int v = 1; v < nw; v++) if (load[v] < load[w]) w = v;                                           // (ties: the lower wave)
+        wave_of[b] = w; load[w] += items[b];
+    }
+    // never behind the modulo rule (longest-first is a heuristic and carries no such promise of its own): where it is, the front keeps b mod nw
+    std::vector<int> mload((size_t)std::max(nw, 1), 0);
+    for (int b = 0; b < nbc; b++) mload[b % std::max(nw, 1)] += items[b];
+    if (*std::max_element(load.begin(), load.end()) > *std::max_element(mload.begin(), mload.end()))
+        for (int b = 0; b < nbc; b++) wave_of[b] = b % nw;
+    for (int k = 0; k < n_kids; k++) {
+        const int c = kids[k];
+        for (int jb = 0; jb < nub[c]; jb++) {
+            const int b = rel[rows_ptr[c] + jb];
+            owner[rows_ptr[c] + jb] = (b >= 0 && b < nbc) ? wave_of[b] : -1;
+        }
+    }
+}
+
 }  // namespace asam

@@ -371,6 +371,10 @@ void aprilsam_amd_clear_error(void);
  *                       (M3500: resident step 0.1981 -> 0.1877 ms); 3 = ... in
  *                       the order of a list schedule that knows how many workgroups an XCD holds at once (plan.h: up_schedule).  2 and 3 also
  *                       order the launch of graphs that run one launch per sweep anyway.  Speed only, results bitwise the same
+ *   "asm_balance"       1 (default): in the extend-add of a single-workgroup front, the block columns are given to the workgroup's waves by
+ *                       their number of work items, longest first to the least loaded wave (aprilsam_amd_asm_owners), so that no wave's
+ *                       list is longer than it has to be; 0 = column modulo waves everywhere (APRILSAM_AMD_ASM_BALANCE).  One wave per column
+ *                       either way, so every sum keeps its order: speed only, results bitwise the same
  *   "blk_backsolve"     1 (default): multi-workgroup fronts are back-substituted 128 columns at a time by a chain
  *                       workgroup + helper workgroups, with the inverse diagonal blocks the factorisation left behind; 0 = one
  *                       workgroup per front, 32 columns at a time
@@ -904,6 +908,16 @@ int aprilsam_amd_persist_leaves_list(int nF, const int *parent, const int *level
  * which: 0 the list (returns the length; fills out up to out_cap), 1 the self-check of the list against base (0 or a negative code).
  * makespan (may be NULL) receives the cost model's makespan of the returned list in us, so mode 0 gives that of any list; host logic only. */
 int aprilsam_amd_up_schedule(int nF, const int *parent, const int *nsb, const int *base, int n_base, int cap, int mode, int which, int *out, int out_cap, double *makespan);
+/* Which wave of a front's workgroup adds its children's update blocks into which block column (option "asm_balance").  A tree of nF fronts
+ * (children have lower indices than their parents; parent -1: a root); front t has nsb[t] own and nub[t] update blocks, and entry
+ * rows_ptr[t] + j of rel (aprilsam_amd_plan_query: "front_rows_ptr", "front_rel") is the block column of t's parent that t's update block j
+ * goes to.  owner (rows_ptr[nF] ints) receives for every such entry the wave, 0 .. nw - 1, that owns its column in the parent: per parent the
+ * columns are taken by decreasing number of work items (one per child block, one more where 3 nub + 1 - 3 j > 64) and each goes to the least
+ * loaded wave, ties to the lower column and then the lower wave; -1 for the entries of a root.  A parent whose longest list would come out
+ * longer that way than with column b on wave b mod nw keeps b mod nw for all its columns (longest-first is a heuristic), so no parent's
+ * longest list is ever longer than under the modulo rule.  Returns 0, or -100 for arguments that are no such tree (rows_ptr must start at
+ * 0 or above and advance by nub[t]); host logic only. */
+int aprilsam_amd_asm_owners(int nF, const int *parent, const int *nsb, const int *nub, const long long *rows_ptr, const int *rel, int nw, int *owner);
 void aprilsam_amd_free(void *p);
 
 /* Host logic behind the incremental path: the reference's elimination order (aprilsam.c:999-1249, restated
