@@ -217,6 +217,16 @@ __global__ void __launch_bounds__(256) k_selinv_sss(const SelFront *__restrict__
 // row-major, a's unknowns first), read from the front that owns the earlier-eliminated of the two; all 36 values NaN when the
 // later one is not among that front's rows (the pair is not on the pattern of L).  One thread per output value.  pos: node ->
 // elimination position, pos_front: position -> owning front.
+// scalar row of elimination position q in front F's row list (own rows, then the struct rows by binary search), -1 if absent.  Shared with
+// k_factor_audit (audit.hip.h).
+__device__ __forceinline__ int sel_local_row(const SelFront &F, const int *__restrict__ rows, int q) {
+    if (q >= F.first && q < F.first + F.nsb) return 3 * (q - F.first);
+    int lo = 0, hi = F.u / 3;
+    const int *rw = rows + F.rows_begin;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (rw[mid] < q) lo = mid + 1; else hi = mid; }
+    return lo < F.u / 3 && rw[lo] == q ? F.s + 3 * lo : -1;
+}
+
 __global__ void __launch_bounds__(256) k_marginal_extract(int n, const int *__restrict__ qa, const int *__restrict__ qb, const int *__restrict__ pos,
                                                           const int *__restrict__ pos_front, const SelFront *__restrict__ fr, const int *__restrict__ rows,
                                                           const double *__restrict__ sig, double *__restrict__ out) {
@@ -234,14 +244,7 @@ __global__ void __launch_bounds__(256) k_marginal_extract(int n, const int *__re
     const int pa = pos[qa[p]], pb = pos[qb[p]];
     const int t = pos_front[min(pa, pb)];
     const SelFront F = fr[t];
-    auto local = [&](int q) -> int {              // scalar row of position q in front t's row list, -1 if absent
-        if (q >= F.first && q < F.first + F.nsb) return 3 * (q - F.first);
-        int lo = 0, hi = F.u / 3;
-        const int *rw = rows + F.rows_begin;
-        while (lo < hi) { const int mid = (lo + hi) >> 1; if (rw[mid] < q) lo = mid + 1; else hi = mid; }
-        return lo < F.u / 3 && rw[lo] == q ? F.s + 3 * lo : -1;
-    };
-    const int la = local(pa), lb = local(pb);              // (the pair is on the pattern or it is not: one decision for all 36 values)
+    const int la = sel_local_row(F, rows, pa), lb = sel_local_row(F, rows, pb);      // (the pair is on the pattern or it is not: one decision for all 36 values)
     const int r = e / 6, c = e % 6;
     const int lr = r < 3 ? la : lb, lc = c < 3 ? la : lb;
     out[g] = (la < 0 || lb < 0) ? __builtin_nan("") : sig[F.off + (long long)(lc + c % 3) * F.R + lr + r % 3];

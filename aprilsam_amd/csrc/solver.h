@@ -139,5 +139,6 @@ bool polar_of(const april_graph_factor_t *f, int *kind);
 bool node_fixed(const april_graph_node_t *n);
 bool fixed_ever();                                               // false until the process fixes its first node: graphs are not walked for flags before
 int robust_weights(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *factors, double *w);   // solver_calls.inc.h
+int factor_audit(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *factors, double *out);   // solver_audit.inc.h
 
 }  // namespace asam

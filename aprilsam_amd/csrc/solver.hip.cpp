@@ -36,6 +36,7 @@
 #include "lm.hip.h"
 #include "chordal.hip.h"
 #include "selinv.hip.h"
+#include "audit.hip.h"
 #include "pathsolve.hip.h"
 #include "polargate.hip.h"
 #include "treesolve.hip.h"
@@ -254,6 +255,7 @@ struct PatchList {
 #include "solver_shard.inc.h"
 #include "solver_marginals.inc.h"
 #include "solver_gating.inc.h"
+#include "solver_audit.inc.h"
 #include "solver_treesolve.inc.h"
 #include "solver_lm.inc.h"
 #include "solver_gnc.inc.h"
@@ -517,6 +519,9 @@ extern "C" int aprilsam_amd_max_selected(april_graph_t *graph, april_graph_chole
 }
 extern "C" int aprilsam_amd_robust_weights(april_graph_t *graph, april_graph_cholesky_param_t *param, int n, const int *factors, double *w) {
     return asam::robust_weights(graph, param, n, factors, w);
+}
+extern "C" int aprilsam_amd_factor_audit(april_graph_t *graph, april_graph_cholesky_param_t *param, int n, const int *factors, double *out) {
+    return asam::factor_audit(graph, param, n, factors, out);
 }
 extern "C" long long aprilsam_amd_debug_selinv_runs(const april_graph_cholesky_param_t *param) { return asam::selinv_runs(param); }
 extern "C" int aprilsam_amd_marginals_joint_any(april_graph_t *graph, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, double *cov) {

@@ -398,6 +398,7 @@ static void inc_impl(april_graph_t *g, april_graph_cholesky_param_t *param) {
         return;
     }
     record_factor(c, reused ? FACT_EXTENDED : FACT_PLAN, gp);
+    c.fact_upt = !reused;                             // (the re-planned step linearised the priors at d_upt: RunArgs::unary_at_lp)
     // bookkeeping exactly as the reference: which poses solve_node visits / updates, start_over (refmodel.cpp)
     april_graph_node_t **ns = (april_graph_node_t **)g->nodes->data;
     for (int i = (partial && reused) ? std::min(N_before, N) : 0; i < N; i++) ns[i]->UID = i;      // aprilsam.c:474 (the new nodes; every node where the walk is full anyway)
@@ -562,7 +563,7 @@ double graph_chi2(april_graph_t *g) {
 static double chi2_impl(april_graph_t *g) {
     ensure_device();
     SlotLock lk(nullptr, g);
-    GraphPack &gp = pack_for(g);
+    GraphPack &gp = pack_for(g, true);                // (writes d_state and edited z / W, which content_version records: no linearisation)
     pack_factors(gp, g);
     pack_states(gp, g, false);
     upload_factors(gp);

@@ -223,6 +223,7 @@ struct Context {
     // marginal covariances (solver_marginals.inc.h): what the last successful solver call left in d_pool (FACT_*), at which value of
     // epoch_steps; the Sigma pool (front pool layout) and the step it was computed for; launch tables built per plan
     int fact_kind = 0; long long fact_epoch = -1; bool fact_asym = false;
+    long long fact_pack = -1; bool fact_upt = false;      // the pack (GraphPack::serial) the factorised system was linearised from; its priors were linearised at d_upt (factor audit)
     bool resident_stepped = false;                 // the current resident loop has enqueued a step (its failure record means something)
     bool resident_failed = false;                  // a step of the current resident loop met a non-positive pivot (resident_sync saw it): resident_end writes nothing
     DBuf<double> d_sigma, d_sel_scr; DBuf<SelFront> d_sel_fd; DBuf<int> d_sel_i32, d_sel_q; DBuf<int4> d_sel_ent; HBuf<double> h_cov;
@@ -338,7 +339,7 @@ static void rewind_epoch(Context &c, hipStream_t s, long long phases);
 static void set_const_granules(Context &c, hipStream_t s);
 // marginal covariances (solver_marginals.inc.h): what a successful solver call left in the front pool
 enum { FACT_NONE = 0, FACT_PLAN = 1, FACT_EXTENDED = 2 };      // no factor / the factor of c.plan / tail fronts appended by the incremental path
-static void record_factor(Context &c, int kind, const GraphPack &gp);
+static void record_factor(Context &c, int kind, GraphPack &gp);
 // slack reserved at plan upload so that the incremental path can append without reallocating device buffers
 constexpr int INC_NODES = 4096, INC_FACT = 16384, INC_I32 = 4 << 20, INC_DEST = 1 << 20, INC_CHILD = 1 << 18, INC_TAB = 1 << 20;
 #define TAIL_POSES (g_opt.tail_poses)         // own poses per tail front of the incremental path (inc_fast_step), option tail_poses (>= 8)

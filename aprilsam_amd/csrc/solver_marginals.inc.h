@@ -123,9 +123,11 @@ static void enqueue_selinv(Context &c, hipStream_t s) {
 // later phase (a resident step, an incremental step, a failed call) moves the counter on and the stamp no longer matches
 // (rewind_epoch forgets the factor when it starts the counter over).  fact_serial numbers the factorisations: Sigma and its tables are
 // kept against it.
-static void record_factor(Context &c, int kind, const GraphPack &gp) {
+static void record_factor(Context &c, int kind, GraphPack &gp) {
     c.fact_kind = kind; c.fact_epoch = c.epoch_steps; c.fact_asym = gp.n_asym > 0 || c.wt_any; c.fact_serial++;
     c.fact_fixed = gp.fx_nodes;
+    c.fact_pack = gp.serial; c.fact_upt = false;
+    gp.lin_ctx = &c; gp.lin_serial = c.fact_serial; gp.lin_content = gp.content_version;      // (the pack holds THIS factorisation's linearisation)
 }
 // Fixed nodes: the consumers of the retained factor describe the system it was made from, identity blocks
 // included.  A node fixed or freed since then makes that system another one: the factor is dropped, and the consumer answers as without.

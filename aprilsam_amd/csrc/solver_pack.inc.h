@@ -45,6 +45,10 @@ struct GraphPack {
     DBuf<double> d_z, d_W, d_state, d_lp, d_dx, d_chi2f, d_scalar;
     DBuf<double> d_lp_last; bool lp_last_valid = false;        // resident loops: the linearisation point of the LAST step enqueued (d_lp itself already holds the next one, UpdArgs::lp_next)
     int F_on_device = 0;               // factors already uploaded
+    // whose linearisation the slots, d_lp and d_dx hold: the Context and fact_serial of the solver call that last linearised into the pack
+    // and kept its factor (record_factor), at lin_content = content_version.  Every call that takes the pack to write into it clears the
+    // stamp first (pack_for), so a step, LM or GNC run, or failed call of ANOTHER param on the graph leaves it not this param's (factor audit)
+    const void *lin_ctx = nullptr; long long lin_serial = -1, lin_content = -1;
     int dirty_lo = 0, dirty_hi = 0;    // packed factors whose z / W changed since the last upload
     long long content_version = 0;     // bumped whenever z / W of a packed factor changed
     long long topo_version = 0;        // bumped whenever the packed endpoints (h_fa / h_fb, F) changed in any way: a pattern compared equal at (serial, topo_version) still is
@@ -139,7 +143,7 @@ static int slot_of_graph(const void *g) {
 }
 // the pack of a graph, on the slot of the call in progress (a pack left behind on another slot by an earlier call moves: dropped there,
 // rebuilt here -- one graph is driven from one slot at a time)
-static GraphPack &pack_for(const april_graph_t *g) {
+static GraphPack &pack_for(const april_graph_t *g, bool keep_lin = false) {
     auto it = g_packs.find(g);
     if (it != g_packs.end() && it->second->slot != t_slot) {
         // The pack is released under the OLD slot's lock as well, so that no call on that slot is inside it (april_graph_chi2 or a destroy
@@ -163,6 +167,7 @@ static GraphPack &pack_for(const april_graph_t *g) {
         p->stream = take_stream(t_slot);
         it = g_packs.emplace(g, std::move(p)).first;
     }
+    if (!keep_lin) it->second->lin_ctx = nullptr;      // (keep_lin: a call that linearises nothing -- april_graph_chi2)
     return *it->second;
 }
 void drop_graph_pack(const april_graph_t *g) {
@@ -605,7 +610,7 @@ static void upload_factors(GraphPack &gp) {
         gp.F_cap = std::max(F, gp.F_cap + gp.F_cap / 2 + 64);
         gp.d_fa.need(gp.F_cap); gp.d_fb.need(gp.F_cap); gp.d_z.need((size_t)3 * gp.F_cap); gp.d_W.need((size_t)9 * gp.F_cap);
         gp.d_chi2f.need((size_t)gp.F_cap + REDUCE_PARTS);       // per-factor terms + the partial sums of device_chi2
-        gp.F_on_device = 0;
+        gp.F_on_device = 0; gp.lin_ctx = nullptr;        // (the weighted and selected slots of the last linearisation are gone with it)
     }
     const int f0 = gp.F_on_device;
     if (F > f0) {

@@ -192,6 +192,8 @@ class SolverLib:
                 d.aprilsam_amd_node_get_fixed.argtypes = [C.POINTER(abi.Node)]
             if hasattr(d, "aprilsam_amd_robust_weights"):    # (defined in the HIP translation unit)
                 d.aprilsam_amd_robust_weights.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.c_int, _ip, _dp]
+            if hasattr(d, "aprilsam_amd_factor_audit"):      # (defined in the HIP translation unit)
+                d.aprilsam_amd_factor_audit.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.c_int, _ip, _dp]
             if hasattr(d, "aprilsam_amd_factor_polar_create"):
                 d.aprilsam_amd_factor_polar_create.restype = C.POINTER(abi.Factor)
                 d.aprilsam_amd_factor_polar_create.argtypes = [C.c_int, C.c_int, C.c_int, _dp, _dp]
@@ -433,6 +435,21 @@ class Graph:
         if rc != 0:
             raise RuntimeError(f"aprilsam_amd_robust_weights failed rc={rc}: {self.lib.last_error()}")
         return out
+
+    def factor_audit(self, param, factors=None):
+        """(array [n, 4], count): per listed factor chi2, leverage, d2_loo and checkability in the system the last solver call factorised
+        (include/aprilsam_amd.h: aprilsam_amd_factor_audit), and how many of the listed factors could not be audited (host-evaluated: a
+        row of NaN each).  All factors of the factorised system when `factors` is None: one row per factor of the graph, rows of factors
+        added since that call stay NaN.  Raises RuntimeError on a negative code."""
+        if factors is None:
+            idx = None; out = np.full((self.n_factors, 4), np.nan)
+        else:
+            idx = np.ascontiguousarray(factors, dtype=np.int32).ravel(); out = np.full((len(idx), 4), np.nan)
+        rc = self.lib.dll.aprilsam_amd_factor_audit(self.ptr, param.ptr if param is not None else None, 0 if idx is None else len(idx),
+                                                    None if idx is None else _np_i(idx), _np_d(out))
+        if rc < 0:
+            raise RuntimeError(f"aprilsam_amd_factor_audit failed rc={rc}: {self.lib.last_error()}")
+        return out, int(rc)
 
     def make_factor_polar(self, kind, a, b, z, W):
         """a range / bearing / range-bearing factor, a observing b (include/aprilsam_amd.h: aprilsam_amd_factor_polar_create; DESIGN.md

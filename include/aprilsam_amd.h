@@ -744,6 +744,43 @@ int aprilsam_amd_associate_polar(april_graph_t *graph, april_graph_cholesky_para
 int aprilsam_amd_debug_polar_gate(int kind, const double *pa, const double *pb, const double *z, const double *W, const double *cov36,
                                   double *d2, double *S4);
 
+/* ---- per-factor audit: leverage and leave-one-out distance ------------------------------------------------------
+ * Which factors ALREADY in the graph does the rest of the graph contradict, and which can nothing check at all?  Answered on the GPU for
+ * the linear system A the last successful solver call factorised, Sigma = A^-1 at that call's linearisation points lp, Delta the step it
+ * solved (the nodes' delta_X).  Like the covariance calls, it describes the system that was factorised: every factor is taken in the
+ * xyt form (a, b, z, W) its linearisation slot held -- a robust factor with W_eff = w W, a max-mixture with the component that was
+ * selected, a range / bearing factor as its xyt slot (exact: r_eff' W_eff r_eff = r_p' W_p r_p at lp, W_eff of rank 1 or 2); b < 0 is an
+ * xytpos prior.  Per listed factor f:
+ *     J = [J_a J_b], r     the factor's Jacobians and residual (theta wrapped) at lp; J = I for a prior
+ *     v = r - (J_a Delta_a + J_b Delta_b)      the linear model's post-fit residual
+ *     P = J Sigma_ff J'    Sigma_ff: the 3 x 3 / 6 x 6 block of f's nodes (always on the pattern of L); rows and columns of a node that
+ *                          was fixed are exact zeros
+ *     M = I - P W
+ * out[4 i ..] =
+ *     chi2          v' W v         the factor's share of the linear system's cost
+ *     leverage      tr(P W)        in [0, rank W]: degrees of freedom the factor spends; rank W - leverage is its redundancy number
+ *     d2_loo        v' W M^-1 v    the Mahalanobis distance of f against the same linear system WITHOUT f (where W is regular:
+ *                                  v' (W^-1 - P)^-1 v): compare with the chi^2 quantiles quoted at aprilsam_amd_gate_xyt.  NaN when det M <= 0
+ *                                  or is not finite
+ *     checkability  det M          in [0, 1]; 0: f is the only information on some direction (a bridge, a lone prior) and d2_loo means
+ *                                  nothing, however small chi2 is
+ * No threshold is applied: the caller reads checkability and decides.  A factor between two fixed nodes gives 0, 1 and d2_loo == chi2.
+ * factors == NULL: all graph factors of the factorised system, in graph order (n ignored).
+ * Returns >= 0: the number of listed factors that cannot be audited, four NaN each -- the factors evaluated on the host through eval()
+ * (foreign types, more than two nodes): they have no slot and user code is not called back.  Or the codes of aprilsam_amd_marginals:
+ * -1 no retained factor (also after aprilsam_amd_optimize_lm / _gnc / _initialize_chordal, during a resident run, or when the param's
+ * last call was made with another graph, or the graph's device copy no longer holds THIS param's linearisation: lp, Delta and the slots
+ * live with the graph, shared by every param that solves it, so another param's solver call on the graph -- a step, an LM or GNC run, a
+ * failed call -- an april_graph_cholesky_inc_solver call, or a factor's z / W edited and then evaluated by april_graph_chi2 ends the
+ * audit's availability until this param's next batch call; april_graph_chi2 alone does not); -12 sharded param, asymmetric W in the factorised graph, or the retained factor is the extended
+ * structure of a fast april_graph_cholesky_inc step (its slots are no consistent picture of that system: a batch call makes the audit
+ * available); -13 null argument, n < 0, a factor index outside the factors that call packed (factors added since), a node count that
+ * differs from the factorised one, or a graph that holds fewer factors than the factorised system; -14 no HIP device; -11 the Sigma pool does not fit under mem_cap_mb.  A refused or failed call writes
+ * nothing, sets aprilsam_amd_last_error and leaves plan, factor and Sigma in place; two calls give the same bits; a second call with no
+ * solver call in between runs no selected inversion.  Available after april_graph_cholesky, aprilsam_amd_batch_resident,
+ * aprilsam_amd_resident_end and an april_graph_cholesky_inc call that fell back to a batch step. */
+int aprilsam_amd_factor_audit(april_graph_t *graph, april_graph_cholesky_param_t *param, int n, const int *factors, double *out);
+
 /* ---- fixed nodes: poses held constant ------------------------------------------------------------------------------
  * A library-made xyt node (april_graph_node_xyt_create) is free or FIXED.  With Phi the fixed set, a step solves the normal equations with
  * the rows and columns of Phi removed: in the assembled system every block (i, j) with i or j in Phi is zero, every right-hand-side segment
