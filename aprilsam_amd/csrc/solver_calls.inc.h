@@ -65,9 +65,7 @@ static void batch_impl(april_graph_t *g, april_graph_cholesky_param_t *param) {
             // z / W of already-packed factors edited in place by the caller (pack_factors recorded the range) only reach the
             // device through upload_factors: the patch list of inc_fast_step carries the NEW factors alone
             if (F > gp.F_cap || gp.dirty_hi > gp.dirty_lo) upload_factors(gp);
-            upload_mixture(gp);                         // (max factors appended: their components, for the step's k_select_mixture)
-            upload_robust(gp);                          // (robust factors appended or edited: their table, for the step's k_robust_weight)
-            upload_polar(gp);                           // (polar factors appended or edited: their table, for the step's k_polar_slot)
+            upload_tables(gp);                          // (max, robust, polar factors appended or edited: their tables, for the step's k_select_mixture, k_robust_weight, k_polar_slot)
             c.h_bad.need(4);
             hybrid = inc_fast_step(c, gp, N, F, c.inc_F, c.inc_N, nullptr, lam);
             reused = hybrid;
@@ -329,9 +327,7 @@ static void inc_impl(april_graph_t *g, april_graph_cholesky_param_t *param) {
     const double tp1 = now_ms() - (tp0b - tp0a);      // (profile: "pack" = factors + states, "model" = the bookkeeping in between)
     const double tp2 = tp1 + (tp0b - tp0a);
     if (F > gp.F_cap || !g_opt.inc_fast || !gp.host_idx.empty()) upload_factors(gp);     // (growing the device arrays re-uploads everything)
-    upload_mixture(gp);
-    upload_robust(gp);
-    upload_polar(gp);
+    upload_tables(gp);
     if (!gp.host_idx.empty()) {       // new foreign factors are linearised now, at the host objects' current l_points
         eval_host_factors(gp, g, gp.host_evaluated);     // (aprilsam.c:508-542); older ones keep their evaluation
         upload_host_index(gp);
@@ -605,13 +601,7 @@ int max_selected(april_graph_t *g, april_graph_cholesky_param_t *param, int n, c
         if (it == g_packs.end() || it->second->slot != t_slot) { for (int i = 0; i < n; i++) out[i] = -1; return 0; }
         GraphPack &gp = *it->second;
         std::vector<int> sel(gp.mx_sel);
-        if (gp.mx_on_device > 0) {             // (through the pinned staging buffer; the stream is idle before it is written)
-            HIPCHECK(hipStreamSynchronize(gp.stream));
-            gp.mx_stage.need((size_t)gp.mx_on_device);
-            HIPCHECK(hipMemcpyAsync(gp.mx_stage.p, gp.d_sel.p, (size_t)4 * gp.mx_on_device, hipMemcpyDeviceToHost, gp.stream));
-            HIPCHECK(hipStreamSynchronize(gp.stream));
-            memcpy(sel.data(), gp.mx_stage.p, (size_t)4 * gp.mx_on_device);
-        }
+        if (gp.mx.on_device > 0) { HIPCHECK(hipStreamSynchronize(gp.stream)); gp.mx.read_back(gp.stream, sel.data()); }
         for (int i = 0; i < n; i++) {
             const int gi = factors[i], m = gi < (int)gp.mx_of.size() && gi < gp.Fg ? gp.mx_of[gi] : -1;
             out[i] = m >= 0 ? sel[m] : -1;
@@ -636,13 +626,7 @@ int robust_weights(april_graph_t *g, april_graph_cholesky_param_t *param, int n,
         if (it == g_packs.end() || it->second->slot != t_slot) { for (int i = 0; i < n; i++) out[i] = -1; return 0; }
         GraphPack &gp = *it->second;
         std::vector<double> w(gp.rb_w);
-        if (gp.rb_on_device > 0) {             // (through the pinned staging buffer; the stream is idle before it is written)
-            HIPCHECK(hipStreamSynchronize(gp.stream));
-            gp.rb_stage.need((size_t)gp.rb_on_device);
-            HIPCHECK(hipMemcpyAsync(gp.rb_stage.p, gp.d_rb_w.p, (size_t)8 * gp.rb_on_device, hipMemcpyDeviceToHost, gp.stream));
-            HIPCHECK(hipStreamSynchronize(gp.stream));
-            memcpy(w.data(), gp.rb_stage.p, (size_t)8 * gp.rb_on_device);
-        }
+        if (gp.rb.on_device > 0) { HIPCHECK(hipStreamSynchronize(gp.stream)); gp.rb.read_back(gp.stream, w.data()); }
         for (int i = 0; i < n; i++) {
             const int gi = factors[i], q = gi < (int)gp.rb_of.size() && gi < gp.Fg ? gp.rb_of[gi] : -1;
             out[i] = q >= 0 ? w[q] : -1.0;

@@ -168,32 +168,17 @@ struct Context {
     DBuf<double> d_dinv, d_bsb_far; DBuf<int> d_bsb_flags;   // inverse diagonal blocks of the big fronts; scratch of k_backsolve_blk
     DBuf<int> d_solve_tab; std::vector<int> solve_tab;      // april_graph_cholesky_inc_solver: front lists of its back substitution
     DBuf<UpdRec> d_upd; DBuf<double> d_wbuf;               // incremental steps: update records per launch-list entry, the step's travelling vectors
-    hipGraphExec_t gexec = nullptr;
-    const void *gexec_key = nullptr;      // GraphPack the graph was captured against
-    long long gexec_serial = 0;
-    long long gexec_mx = -1;              // GraphPack::mx_gen it was captured with (max-mixture table)
-    long long gexec_rb = -1;              // GraphPack::rb_gen it was captured with (robust table)
-    long long gexec_pl = -1;              // GraphPack::pl_gen it was captured with (polar table)
-    long long gexec_fx = -1;              // GraphPack::fx_gen it was captured with (fixed nodes)
-    // the same phase as the API call runs it: first kernel reads the caller's states from the pinned mirror, last kernel
-    // writes new states / dx / pivot flag back to pinned mirrors -- one graph launch + one stream sync per call
-    hipGraphExec_t gexec_api = nullptr;
-    const void *api_key[11] = {};
-    // Levenberg-Marquardt (solver_lm.inc.h): one iteration captured as its own graph, keyed like gexec plus the LM buffers it reads
-    hipGraphExec_t gexec_lm = nullptr;
-    const void *lm_key[12] = {};
     DBuf<double> d_lm_trial, d_lm_hacc, d_lm_terms, d_lm_trace; DBuf<LmScalars> d_lm; HBuf<LmScalars> h_lm;
     // chordal initialisation (solver_chordal.inc.h): [scratch of the state update 3N][theta N][4 scalars]; the components chosen for the max factors
     DBuf<double> d_ch; HBuf<double> h_ch; DBuf<int> d_ch_sel;
     long long n_captures = 0;                      // hipGraphs captured and instantiated for this context so far (aprilsam_amd_debug_graph_captures)
-    int api_key_runs = 0;                          // calls seen with this key: the first one runs without a graph (run_numeric)
     // captured graphs that are no longer current: hipGraphExecDestroy takes 0.24 ms on this stack, so they are destroyed while the
     // GPU works on a step (reap_retired), not on the way to the next plan
     // A retired graph may still have launches in flight (resident / sharded loops enqueue steps without a sync in between): it carries an
     // event recorded on the stream it was last launched on and is destroyed only once that event has completed.
     struct Retired { hipGraphExec_t g; hipEvent_t done; };
     std::vector<Retired> retired;
-    hipStream_t graph_stream = nullptr;            // the stream gexec / gexec_api were last launched on (run_numeric)
+    hipStream_t graph_stream = nullptr;            // the stream a captured graph was last launched on (replay_captured)
     void reap_retired(bool wait = false) {
         size_t keep = 0;
         for (Retired &r : retired) {
@@ -216,6 +201,31 @@ struct Context {
         } else r.done = nullptr;
         retired.push_back(r); g = nullptr;
     }
+    // One captured hipGraph: the exec handle, the key it was captured with (GraphPack::capture_key plus this graph's extras) and how many
+    // runs that key has seen.  fit() is the whole staleness rule: another key retires the graph; it returns whether this run replays
+    // (or captures) one.  skip_first: a graph is worth its capture, instantiation and destruction (0.3 ms together) only if the
+    // configuration comes back, so the first run with a new key enqueues its kernels directly
+    struct Captured {
+        const bool skip_first; hipGraphExec_t exec = nullptr; CaptureKey key; long long runs = 0;
+        Captured(bool skip_first = false) : skip_first(skip_first) {}
+        bool fit(Context &c, const CaptureKey &k) {
+            if (!(k == key)) { c.retire(exec); key = k; runs = 0; }
+            return runs++ > 0 || !skip_first;
+        }
+    };
+    // The numeric phase of a resident step.  Extras: none.  N is not in the key: this graph runs only behind resident_begin_impl, whose
+    // prepare_plan makes a new plan when N differs from the pattern's (upload_plan retires every capture); the re-planned incremental
+    // step (unary_at_lp) is never captured.  gc_gen is not in it: gc_n > 0 only inside aprilsam_amd_optimize_gnc, which enqueues LM
+    // iterations (cap_lm) and never this phase
+    Captured cap_step;
+    // The same phase as the API call runs it: first kernel reads the caller's states from the pinned mirror, last kernel writes new
+    // states / dx / pivot flag back to pinned mirrors -- one graph launch + one stream sync per call.  Extras: those four mirrors
+    // (h_state, h_lp, h_dx, h_bad) and N, the length k_load_states copies.  No gc_gen, as above
+    Captured cap_api{ true };
+    // Levenberg-Marquardt (solver_lm.inc.h): one iteration.  Extras: the four LM buffers it reads, N (the lengths of k_lm_commit and
+    // k_lm_norms) and gc_gen -- a GNC run's candidates table serves that run alone
+    Captured cap_lm;
+    void retire_captures() { for (Captured *g : { &cap_step, &cap_api, &cap_lm }) { retire(g->exec); g->runs = 0; } }
     double lambda_val = -1; int lambda_N = -1;     // what d_lambda currently holds (uniform batch value), -1: unknown
     long long lambda_fx_gen = 0, lambda_fx_serial = 0;      // ... apart from the 1.0 of the fixed nodes of this pack at this fx_gen (k_fix_mask; set_lambda)
     DBuf<int> d_fx_mask;                           // ... and which nodes of a covariance query are among them (k_fix_cov)
@@ -244,7 +254,7 @@ struct Context {
         h_done.release(); h_kstamp.release(); d_prof.release(); d_upd.release(); d_wbuf.release(); d_flags.release(); d_flevel.release(); d_epoch.release(); d_marks.release(); d_perm.release(); d_solve_tab.release(); d_dinv.release(); d_bsb_far.release(); d_bsb_flags.release(); d_guard.release(); d_guard_cnt.release(); n_guard = 0;
         d_lm_trial.release(); d_lm_hacc.release(); d_lm_terms.release(); d_lm_trace.release(); d_lm.release(); h_lm.release();
         d_ch.release(); h_ch.release(); d_ch_sel.release();
-        retire(gexec); retire(gexec_api); retire(gexec_lm); reap_retired(true);
+        retire_captures(); reap_retired(true);
         if (have_events) for (auto &e : ev) (void)hipEventDestroy(e);
         have_events = false;
         for (auto &e : k_ev) (void)hipEventDestroy(e);
@@ -523,7 +533,7 @@ static void upload_plan(Context &c, hipStream_t s, const ShardLayout *lay = null
     const Plan &P = c.plan;
     const bool uprof = getenv("APRILSAM_AMD_PLAN_PROFILE") != nullptr;
     const double u0 = uprof ? now_ms() : 0;
-    c.retire(c.gexec); c.retire(c.gexec_api); c.retire(c.gexec_lm); c.api_key_runs = 0;
+    c.retire_captures();
     c.lambda_N = -1;
     c.release_sel();                          // (Sigma and its tables describe the plan being replaced)
     // ---- descriptors + index arrays ----------------------------------------------------------------------------

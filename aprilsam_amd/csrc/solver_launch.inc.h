@@ -315,20 +315,21 @@ static void collect_kernel_times(Context &c) {
     c.k_ids.clear();
 }
 
-// Replay what `enqueue` puts on stream s as a captured hipGraph: captured and instantiated into `exec` when that is null, then launched.  Whether
-// an existing graph still fits (its key) is the caller's question: it retires a stale one (Context::retire) before it comes here.
-template <class Enqueue> static void replay_captured(Context &c, hipGraphExec_t &exec, hipStream_t s, Enqueue enqueue) {
-    if (!exec) {
+// Run what `enqueue` puts on stream s as the captured hipGraph g, which depends on `key`: a graph captured with another key is retired
+// (Captured::fit, which also says when a run is not worth a graph: enqueued directly then); captured and instantiated when g holds none; launched.
+template <class Enqueue> static void replay_captured(Context &c, Context::Captured &g, const CaptureKey &key, hipStream_t s, Enqueue enqueue) {
+    if (!g.fit(c, key)) { enqueue(); return; }
+    if (!g.exec) {
         hipGraph_t graph = nullptr;
         HIPCHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
         enqueue();
         HIPCHECK(hipStreamEndCapture(s, &graph));
-        HIPCHECK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+        HIPCHECK(hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0));
         HIPCHECK(hipGraphDestroy(graph));
         c.n_captures++;
     }
     c.graph_stream = s;
-    HIPCHECK(hipGraphLaunch(exec, s));
+    HIPCHECK(hipGraphLaunch(g.exec, s));
 }
 
 long long graph_captures(const april_graph_cholesky_param_t *param) {
@@ -337,8 +338,9 @@ long long graph_captures(const april_graph_cholesky_param_t *param) {
     return it == g_ctx.end() ? -1 : it->second->n_captures;
 }
 
-// run the numeric phase, replaying a captured hipGraph when enabled.  timing: record the stage events c.ev (never captured); the rest as NumericArgs (io_host: the other two do not apply)
-struct RunArgs { bool timing = false, unary_at_lp = false, io_host = false, relin = false; };
+// run the numeric phase, replaying a captured hipGraph when enabled.  timing: record the stage events c.ev; ktime: an event pair around every
+// kernel (neither is ever captured); the rest as NumericArgs (io_host: the other two do not apply)
+struct RunArgs { bool timing = false, ktime = false, unary_at_lp = false, io_host = false, relin = false; };
 static void run_numeric(Context &c, GraphPack &gp, const RunArgs &r = RunArgs{}) {
     hipStream_t s = gp.stream;
     set_small_attr();
@@ -347,23 +349,13 @@ static void run_numeric(Context &c, GraphPack &gp, const RunArgs &r = RunArgs{})
     NumericArgs a;
     a.io_host = r.io_host;
     if (!r.io_host) a.relin = r.relin;
-    const bool graph = g_opt.use_graph && !r.timing && gp.host_idx.empty();      // (host-evaluated factors: staging buffers may move)
-    if (r.io_host && graph) {
-        const void *key[11] = { gp.d_state.p, gp.h_state.p, gp.h_lp.p, gp.h_dx.p, c.h_bad.p, (const void *)(size_t)gp.N, (const void *)(size_t)gp.serial, (const void *)(size_t)gp.mx_gen,
-                                (const void *)(size_t)gp.rb_gen, (const void *)(size_t)gp.pl_gen, (const void *)(size_t)gp.fx_gen };
-        // A graph is worth its capture, instantiation and destruction (0.3 ms together) only if the configuration comes back:
-        // the first call with a new key -- every fall-back of an incremental run, every cold call -- enqueues its kernels directly.
-        if (memcmp(key, c.api_key, sizeof(key)) != 0) { c.retire(c.gexec_api); memcpy(c.api_key, key, sizeof(key)); c.api_key_runs = 0; }
-        if (c.api_key_runs++ == 0) enqueue_numeric(c, gp, s, a);
-        else replay_captured(c, c.gexec_api, s, [&] { enqueue_numeric(c, gp, s, a); });
-    } else if (!r.io_host && graph && !r.unary_at_lp) {
-        if (c.gexec_key != (const void *)gp.d_state.p || c.gexec_serial != gp.serial || c.gexec_mx != gp.mx_gen || c.gexec_rb != gp.rb_gen || c.gexec_pl != gp.pl_gen || c.gexec_fx != gp.fx_gen) {
-            c.retire(c.gexec);
-            c.gexec_key = (const void *)gp.d_state.p; c.gexec_serial = gp.serial; c.gexec_mx = gp.mx_gen; c.gexec_rb = gp.rb_gen; c.gexec_pl = gp.pl_gen; c.gexec_fx = gp.fx_gen;
-        }
-        replay_captured(c, c.gexec, s, [&] { enqueue_numeric(c, gp, s, a); });
+    const bool graph = g_opt.use_graph && !r.timing && !r.ktime && gp.host_idx.empty();      // (host-evaluated factors: staging buffers may move)
+    Context::Captured *cap = !graph ? nullptr : r.io_host ? &c.cap_api : !r.unary_at_lp ? &c.cap_step : nullptr;
+    if (cap) {
+        const CaptureKey key = r.io_host ? gp.capture_key({ (size_t)gp.h_state.p, (size_t)gp.h_lp.p, (size_t)gp.h_dx.p, (size_t)c.h_bad.p, (size_t)gp.N }) : gp.capture_key();
+        replay_captured(c, *cap, key, s, [&] { enqueue_numeric(c, gp, s, a); });      // (API calls: not the first one with a new key -- every fall-back of an incremental run, every cold call)
     } else {
-        a.ev = r.timing ? c.ev : nullptr;
+        a.ev = r.timing ? c.ev : nullptr; a.ktime = r.ktime;
         if (!r.io_host) a.unary_at_lp = r.unary_at_lp;
         enqueue_numeric(c, gp, s, a);
     }

@@ -2,7 +2,7 @@
 // aprilsam_amd_optimize_lm, Levenberg-Marquardt on the device (kernels in lm.hip.h).
 //
 // Set-up is resident_begin_impl's (pack, plan, upload).  One iteration = the numeric phase with its state update pointed at the trial
-// buffer, then cost / model / norms / decide / commit, captured once as c.gexec_lm and replayed; the host synchronises every check_every
+// buffer, then cost / model / norms / decide / commit, captured once as c.cap_lm and replayed; the host synchronises every check_every
 // iterations and reads the status block k_lm_decide mirrors into pinned memory.  The end copies the states back as resident_end does and
 // drops the retained factor (it was made at another point with another lambda).
 
@@ -72,11 +72,8 @@ static void lm_enqueue_iteration(Context &c, GraphPack &gp, hipStream_t s) {
 static void lm_run_iteration(Context &c, GraphPack &gp, hipStream_t s) {
     rewind_epoch(c, s, 1);
     if (!g_opt.use_graph) { lm_enqueue_iteration(c, gp, s); return; }
-    const void *key[12] = { gp.d_state.p, (const void *)(size_t)gp.serial, (const void *)(size_t)gp.mx_gen, (const void *)(size_t)gp.N,
-                           c.d_lm_trial.p, c.d_lm_terms.p, c.d_lm_trace.p, c.d_lm.p, (const void *)(size_t)gp.rb_gen, (const void *)(size_t)gp.gc_gen, (const void *)(size_t)gp.pl_gen,
-                           (const void *)(size_t)gp.fx_gen };
-    if (memcmp(key, c.lm_key, sizeof(key)) != 0) { c.retire(c.gexec_lm); memcpy(c.lm_key, key, sizeof(key)); }
-    replay_captured(c, c.gexec_lm, s, [&] { lm_enqueue_iteration(c, gp, s); });
+    const CaptureKey key = gp.capture_key({ (size_t)c.d_lm_trial.p, (size_t)c.d_lm_terms.p, (size_t)c.d_lm_trace.p, (size_t)c.d_lm.p, (size_t)gp.N, (size_t)gp.gc_gen });
+    replay_captured(c, c.cap_lm, key, s, [&] { lm_enqueue_iteration(c, gp, s); });
 }
 
 // ---- the pieces of a run, shared with the stage driver of aprilsam_amd_optimize_gnc (solver_gnc.inc.h) --------------------------------

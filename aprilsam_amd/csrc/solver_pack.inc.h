@@ -30,6 +30,90 @@ static void park_stream(int slot, hipStream_t s) {
     } else (void)hipGetLastError();
     (void)hipStreamDestroy(s);
 }
+// The device table of one factor family (max-mixture, robust, polar): columns of ints or doubles, one row per factor of the family, kept on
+// the device append-only.  The host vectors and device buffers belong to the GraphPack, by name (kernels and the select_new_* rules read
+// them); the table knows how they go up.  `gen` changes whenever the table's size or device addresses do: captured graphs are keyed by
+// it (GraphPack::capture_key).
+struct SideTable {
+    // One column: `width` elements per row and `extra` behind the last row -- or, BY_COMP, per COMPONENT: the rows of such a column are the
+    // table's prefix array (the max factors' z, W, c through mx_k).  Double columns are listed before int columns (staging alignment).
+    // WRITTEN: the column a kernel writes (d_sel, d_rb_w: at most one) -- the host holds its values only for rows not yet uploaded.
+    enum { WRITTEN = 1, BY_COMP = 2 };
+    struct Col {
+        std::vector<int> *hi = nullptr; DBuf<int> *di = nullptr; std::vector<double> *hd = nullptr; DBuf<double> *dd = nullptr; int width, extra; bool written, by_comp;
+        template <class T> Col(std::vector<T> &h, DBuf<T> &d, int width = 1, int flags = 0, int extra = 0) : width(width), extra(extra), written(flags & WRITTEN), by_comp(flags & BY_COMP) {
+            if constexpr (std::is_same<T, int>::value) { hi = &h; di = &d; } else { hd = &h; dd = &d; }
+        }
+        size_t esz() const { return hi ? 4 : 8; }
+        const char *host() const { return hi ? (const char *)hi->data() : (const char *)hd->data(); }
+        char *dev() const { return hi ? (char *)di->p : (char *)dd->p; }
+        size_t cap() const { return hi ? di->cap : dd->cap; }
+        void need(size_t n) const { if (hi) di->need(n); else dd->need(n); }
+        void release() const { if (hi) di->release(); else dd->release(); }
+        void clear() const { if (hi) hi->assign((size_t)extra, 0); else hd->clear(); }
+    };
+    const std::vector<int> &f;                      // the packed entry of each row: its size is the table's row count
+    const std::vector<int> *prefix;                 // row -> first component (rows + 1 entries), or null: no column is by_comp
+    std::vector<Col> cols;
+    HBuf<double> stage;                             // pinned staging of every copy, packed as 8-byte words
+    int on_device = 0; bool dirty = false; long long gen = 0;
+    SideTable(const std::vector<int> &f, const std::vector<int> *prefix, std::vector<Col> cols) : f(f), prefix(prefix), cols(std::move(cols)) {}
+    int rows() const { return (int)f.size(); }
+    // elements of column c that rows [0, r) occupy (without `extra`)
+    size_t upto(const Col &c, int r) const { return (size_t)c.width * (size_t)(c.by_comp ? (*prefix)[r] : r); }
+    void clear() {
+        if (rows() || on_device) gen++;             // (a pack that never held such factors keeps its captured graphs)
+        for (const Col &c : cols) c.clear();
+        on_device = 0; dirty = false;
+    }
+    const Col *written() const { for (const Col &c : cols) if (c.written) return &c; return nullptr; }
+    // the device's values of the written column, rows [0, on_device), into out.  Through the pinned staging buffer: the stream is idle
+    // before it is written (the caller has synchronised it)
+    void read_back(hipStream_t s, void *out) {
+        const Col *c = written();
+        if (!c || on_device <= 0) return;
+        const size_t bytes = c->esz() * (size_t)on_device;
+        stage.need((bytes + 7) / 8);
+        HIPCHECK(hipMemcpyAsync(stage.p, c->dev(), bytes, hipMemcpyDeviceToHost, s));
+        HIPCHECK(hipStreamSynchronize(s));
+        memcpy(out, stage.p, bytes);
+    }
+    // host -> device: what was appended since the last upload, everything after an edit (dirty) or a move.  The written column receives
+    // the host's values of the appended rows only: the device's own of the older rows stay, and are carried across a move (read_back).
+    // A buffer that is too small is allocated with head-room of half as much again and 64 rows: all of them move then
+    void upload(hipStream_t s) {
+        const int R = rows();
+        if (R == 0 || (on_device == R && !dirty)) return;
+        HIPCHECK(hipStreamSynchronize(s));          // (the pinned staging buffer is written below; this runs only when factors of the family were added or edited)
+        bool fits = true;
+        for (const Col &c : cols) fits = fits && upto(c, R) + c.extra <= c.cap();
+        if (!fits) {
+            if (const Col *c = written()) read_back(s, (void *)c->host());      // (the host's copy of these rows is stale or was never made)
+            for (const Col &c : cols) { const size_t n = upto(c, R) / c.width; c.need((n + n / 2 + 64) * c.width + c.extra); }
+            on_device = 0; dirty = true; gen++;
+        }
+        const int r0 = dirty ? 0 : on_device, w0 = std::min(on_device, R);
+        auto first = [&](const Col &c) { return upto(c, c.written ? w0 : r0); };
+        size_t bytes = 0;
+        for (const Col &c : cols) bytes += c.esz() * (upto(c, R) + c.extra - first(c));
+        stage.need((bytes + 7) / 8);
+        char *st = (char *)stage.p;
+        for (const Col &c : cols) {
+            const size_t e0 = first(c), nb = c.esz() * (upto(c, R) + c.extra - e0);
+            if (!nb) continue;
+            memcpy(st, c.host() + c.esz() * e0, nb);
+            HIPCHECK(hipMemcpyAsync(c.dev() + c.esz() * e0, st, nb, hipMemcpyHostToDevice, s));
+            st += nb;
+        }
+        on_device = R; dirty = false;
+    }
+    void release() { for (const Col &c : cols) c.release(); stage.release(); }
+};
+// what a captured hipGraph of any kind depends on in the pack (GraphPack::capture_key), plus what that kind adds (`extra`, zero-filled)
+struct CaptureKey {
+    const void *state = nullptr; long long serial = 0, tables_gen = -1; std::array<size_t, 6> extra{};
+    bool operator==(const CaptureKey &o) const { return state == o.state && serial == o.serial && tables_gen == o.tables_gen && extra == o.extra; }
+};
 struct GraphPack {
     int slot = 0;                      // device slot the pack's buffers and stream live on (solver.hip.cpp: SlotLock)
     const long long serial = ++g_pack_serial;      // captured hipGraphs are keyed by it: a pack freed and another allocated at the same addresses must not match
@@ -71,35 +155,29 @@ struct GraphPack {
     // max-mixture factors: per max factor m its packed entry mx_f[m] and components [mx_k[m], mx_k[m + 1]); per
     // component z (3), W (9), c = -2 logw - ln det W and logw as given (content check); mx_sel: the selection made on the host (incremental
     // steps; -1: none yet) -- d_sel, written by k_select_mixture, holds the selection of each factor's most recent linearisation.  mx_of: per
-    // graph factor its m or -1.  mx_gen changes whenever the table's size or device addresses do: captured graphs are keyed by it
+    // graph factor its m or -1
     std::vector<int> mx_f, mx_k{ 0 }, mx_sel, mx_of; std::vector<double> mx_z, mx_W, mx_c, mx_logw;
-    DBuf<int> d_mx_f, d_mx_k, d_sel; DBuf<double> d_mx_z, d_mx_W, d_mx_c; HBuf<double> mx_stage;
-    int mx_on_device = 0; bool mx_dirty = false; long long mx_gen = 0;
+    DBuf<int> d_mx_f, d_mx_k, d_sel; DBuf<double> d_mx_z, d_mx_W, d_mx_c;
+    SideTable mx{ mx_f, &mx_k, { { mx_z, d_mx_z, 3, SideTable::BY_COMP }, { mx_W, d_mx_W, 9, SideTable::BY_COMP }, { mx_c, d_mx_c, 1, SideTable::BY_COMP }, { mx_f, d_mx_f }, { mx_k, d_mx_k, 1, 0, 1 }, { mx_sel, d_sel, 1, SideTable::WRITTEN } } };
     int n_max() const { return (int)mx_f.size(); }
-    void mx_clear() {
-        if (!mx_f.empty() || mx_on_device) mx_gen++;      // (a pack that never held max factors keeps its captured graphs)
-        mx_f.clear(); mx_k.assign(1, 0); mx_sel.clear(); mx_of.clear(); mx_z.clear(); mx_W.clear(); mx_c.clear(); mx_logw.clear(); mx_on_device = 0; mx_dirty = false; }
+    void mx_clear() { mx.clear(); mx_of.clear(); mx_logw.clear(); }
     // robust factors: per robust factor q its packed entry rb_f[q], kind rb_kind[q], scale rb_c[q] and unweighted
     // information matrix rb_W0[9q] (the slot of h_W / d_W holds W_eff = w W0 once a linearisation weighted it); rb_w: the host's weight
     // (incremental steps; -1: none yet) -- d_rb_w, written by k_robust_weight, holds the weight of each factor's most recent linearisation.
-    // rb_of: per graph factor its q or -1.  rb_gen changes whenever the table's size or device addresses do: captured graphs are keyed by it
+    // rb_of: per graph factor its q or -1
     std::vector<int> rb_f, rb_kind, rb_of; std::vector<double> rb_c, rb_W0, rb_w;
-    DBuf<int> d_rb_f, d_rb_kind; DBuf<double> d_rb_c, d_rb_W0, d_rb_w; HBuf<double> rb_stage;
-    int rb_on_device = 0; bool rb_dirty = false; long long rb_gen = 0;
+    DBuf<int> d_rb_f, d_rb_kind; DBuf<double> d_rb_c, d_rb_W0, d_rb_w;
+    SideTable rb{ rb_f, nullptr, { { rb_W0, d_rb_W0, 9 }, { rb_c, d_rb_c }, { rb_w, d_rb_w, 1, SideTable::WRITTEN }, { rb_f, d_rb_f }, { rb_kind, d_rb_kind } } };
     int n_robust() const { return (int)rb_f.size(); }
-    void rb_clear() {
-        if (!rb_f.empty() || rb_on_device) rb_gen++;      // (a pack that never held robust factors keeps its captured graphs)
-        rb_f.clear(); rb_kind.clear(); rb_of.clear(); rb_c.clear(); rb_W0.clear(); rb_w.clear(); rb_on_device = 0; rb_dirty = false; }
+    void rb_clear() { rb.clear(); rb_of.clear(); }
     // polar factors (polar.hip.h): per polar factor p its packed entry pl_f[p], kind pl_kind[p], measurement pl_z[2p] and
     // information matrix pl_W[4p] (the slot of h_z / h_W holds a null placeholder until k_polar_slot or select_new_polar writes z_eff / W_eff).
-    // pl_of: per graph factor its p or -1.  pl_gen changes whenever the table's size or device addresses do: captured graphs are keyed by it
+    // pl_of: per graph factor its p or -1
     std::vector<int> pl_f, pl_kind, pl_of; std::vector<double> pl_z, pl_W;
-    DBuf<int> d_pl_f, d_pl_kind; DBuf<double> d_pl_z, d_pl_W; HBuf<double> pl_stage;
-    int pl_on_device = 0; bool pl_dirty = false; long long pl_gen = 0;
+    DBuf<int> d_pl_f, d_pl_kind; DBuf<double> d_pl_z, d_pl_W;
+    SideTable pl{ pl_f, nullptr, { { pl_z, d_pl_z, 2 }, { pl_W, d_pl_W, 4 }, { pl_f, d_pl_f }, { pl_kind, d_pl_kind } } };
     int n_polar() const { return (int)pl_f.size(); }
-    void pl_clear() {
-        if (!pl_f.empty() || pl_on_device) pl_gen++;      // (a pack that never held polar factors keeps its captured graphs)
-        pl_f.clear(); pl_kind.clear(); pl_of.clear(); pl_z.clear(); pl_W.clear(); pl_on_device = 0; pl_dirty = false; }
+    void pl_clear() { pl.clear(); pl_of.clear(); }
     // fixed nodes (fixed.hip.h): fx_nodes: the ids of the nodes held constant, ascending, as the last call's walk over
     // the node objects found them (sync_fixed); fx_rec: one record per packed entry with a fixed endpoint (.x the entry, .y the FX_* bits of
     // the slots k_fix_mask zeroes), built from the PACKED entries -- the pairs of a host-evaluated clique included -- at fx_topo =
@@ -108,6 +186,10 @@ struct GraphPack {
     DBuf<int> d_fx_nodes; DBuf<int2> d_fx_rec;
     bool fx_dirty = false; long long fx_gen = 0;
     int n_fixed() const { return (int)fx_nodes.size(); }
+    // What every captured graph reads of the pack: the device arrays (d_state stands for all that grow with the nodes), this pack and no
+    // other at the same addresses, and every side table where it lay at the capture.  Each generation only grows, so their sum changes
+    // exactly when one of them does: a new table-keeping family adds its generation to this sum and is keyed everywhere
+    CaptureKey capture_key(std::array<size_t, 6> extra = {}) const { return CaptureKey{ d_state.p, serial, mx.gen + rb.gen + pl.gen + fx_gen, extra }; }
     // GNC candidates (gnc.hip.h): a table that exists on the device for the length of ONE aprilsam_amd_optimize_gnc
     // call -- gc_n > 0 only inside it.  d_gc_f / d_gc_W0 / d_gc_w: packed entry, plain W and last weight per candidate, d_gc_par: loss, c
     // and mu; d_gc_out / gc_stage: results and their pinned staging.  gc_gen changes with every run: captured LM iterations are keyed by it
@@ -124,9 +206,9 @@ struct GraphPack {
         h_fa.release(); h_fb.release(); h_z.release(); h_W.release(); h_state.release(); h_lp.release(); h_dx.release();
         d_fa.release(); d_fb.release(); d_z.release(); d_W.release(); d_state.release(); d_lp.release(); d_lp_last.release(); d_dx.release();
         d_chi2f.release(); d_scalar.release(); h_scalar.release(); h_hostH.release(); d_hostH.release(); d_host_idx.release(); d_upt.release();
-        d_mx_f.release(); d_mx_k.release(); d_sel.release(); d_mx_z.release(); d_mx_W.release(); d_mx_c.release(); mx_stage.release(); mx_clear();
-        d_rb_f.release(); d_rb_kind.release(); d_rb_c.release(); d_rb_W0.release(); d_rb_w.release(); rb_stage.release(); rb_clear();
-        d_pl_f.release(); d_pl_kind.release(); d_pl_z.release(); d_pl_W.release(); pl_stage.release(); pl_clear();
+        mx.release(); mx_clear();
+        rb.release(); rb_clear();
+        pl.release(); pl_clear();
         d_fx_nodes.release(); d_fx_rec.release(); fx_nodes.clear(); fx_rec.clear(); fx_topo = -1; fx_dirty = false;
         d_gc_f.release(); d_gc_W0.release(); d_gc_w.release(); d_gc_out.release(); d_gc_par.release(); gc_stage.release(); gc_n = 0;
         if (stream) { forget_stream(stream); park_stream(slot, stream); }
@@ -274,7 +356,7 @@ static void pack_factors(GraphPack &gp, const april_graph_t *g, bool validate_ol
                         edit = true;
                     }
                 }
-                if (edit) { gp.mx_dirty = true; lo = std::min(lo, p0); hi = std::max(hi, p0 + 1); }
+                if (edit) { gp.mx.dirty = true; lo = std::min(lo, p0); hi = std::max(hi, p0 + 1); }
                 continue;
             }
             if (is_pl) {               // the slot holds z_eff / W_eff: the object against the table
@@ -282,7 +364,7 @@ static void pack_factors(GraphPack &gp, const april_graph_t *g, bool validate_ol
                 double *tz = gp.pl_z.data() + (size_t)2 * q, *tW = gp.pl_W.data() + (size_t)4 * q;
                 if (memcmp(tz, f->u.common.z, (size_t)8 * m) != 0 || memcmp(tW, f->u.common.W->data, (size_t)8 * m * m) != 0) {
                     memcpy(tz, f->u.common.z, (size_t)8 * m); memcpy(tW, f->u.common.W->data, (size_t)8 * m * m);
-                    gp.pl_dirty = true; lo = std::min(lo, p0); hi = std::max(hi, p0 + 1);
+                    gp.pl.dirty = true; lo = std::min(lo, p0); hi = std::max(hi, p0 + 1);
                 }
                 continue;
             }
@@ -293,7 +375,7 @@ static void pack_factors(GraphPack &gp, const april_graph_t *g, bool validate_ol
                 if (memcmp(zp, f->u.common.z, 24) != 0 || memcmp(W0, f->u.common.W->data, 72) != 0 || gp.rb_kind[q] != rb_kind || memcmp(&gp.rb_c[q], &rb_c, 8) != 0) {
                     memcpy(zp, f->u.common.z, 24); memcpy(W0, f->u.common.W->data, 72); memcpy(Wp, W0, 72);
                     gp.rb_kind[q] = rb_kind; gp.rb_c[q] = rb_c;
-                    gp.rb_dirty = true; lo = std::min(lo, p0); hi = std::max(hi, p0 + 1);
+                    gp.rb.dirty = true; lo = std::min(lo, p0); hi = std::max(hi, p0 + 1);
                 }
                 continue;
             }
@@ -348,7 +430,7 @@ static void pack_factors(GraphPack &gp, const april_graph_t *g, bool validate_ol
                     gp.mx_c.push_back(max_const(f, j)); gp.mx_logw.push_back(f->u.max.logw[j]);
                 }
                 gp.mx_k.push_back((int)gp.mx_c.size());
-                gp.mx_gen++;
+                gp.mx.gen++;
             } else if (is_pl) {        // the slot holds a null factor (symmetric) until k_polar_slot / select_new_polar writes z_eff / W_eff
                 memset(gp.h_z.p + (size_t)3 * F, 0, 24); memset(gp.h_W.p + (size_t)9 * F, 0, 72);
                 gp.note_asym(F, gp.h_W.p + (size_t)9 * F, true);
@@ -357,7 +439,7 @@ static void pack_factors(GraphPack &gp, const april_graph_t *g, bool validate_ol
                 memcpy(tz, f->u.common.z, (size_t)8 * m); memcpy(tW, f->u.common.W->data, (size_t)8 * m * m);
                 gp.pl_of[i] = gp.n_polar(); gp.pl_f.push_back(F); gp.pl_kind.push_back(pl_kind);
                 gp.pl_z.insert(gp.pl_z.end(), tz, tz + 2); gp.pl_W.insert(gp.pl_W.end(), tW, tW + 4);
-                gp.pl_gen++;
+                gp.pl.gen++;
             } else {
                 memcpy(gp.h_z.p + (size_t)3 * F, f->u.common.z, 24);
                 memcpy(gp.h_W.p + (size_t)9 * F, f->u.common.W->data, 72);
@@ -365,58 +447,13 @@ static void pack_factors(GraphPack &gp, const april_graph_t *g, bool validate_ol
                 if (is_rb) {           // the slot holds W0 until a weighting writes W_eff (k_robust_weight, select_new_robust)
                     gp.rb_of[i] = gp.n_robust(); gp.rb_f.push_back(F); gp.rb_kind.push_back(rb_kind); gp.rb_c.push_back(rb_c); gp.rb_w.push_back(-1.0);
                     gp.rb_W0.insert(gp.rb_W0.end(), f->u.common.W->data, f->u.common.W->data + 9);
-                    gp.rb_gen++;
+                    gp.rb.gen++;
                 }
             }
         }
         gp.g2p[i + 1] = F;
     }
     gp.F = F; gp.Fg = Fg;
-}
-// the component table of the max factors -> device: what was appended since the last upload, everything after an edit or a move.  d_sel
-// receives the host's selections of the appended factors only: the device's own of the older ones stay (kept across a move)
-static void upload_mixture(GraphPack &gp) {
-    const int M = gp.n_max(), C = gp.mx_k.back();
-    if (M == 0 || (gp.mx_on_device == M && !gp.mx_dirty)) return;
-    hipStream_t s = gp.stream;
-    // (through the pinned staging buffer mx_stage, as every other upload of the pack goes from pinned memory: the stream is idle before
-    // it is written -- this runs only when max factors were added or edited)
-    HIPCHECK(hipStreamSynchronize(s));
-    // (each buffer against its own capacity: they grow by half at different moments)
-    if ((size_t)M > gp.d_sel.cap || (size_t)M > gp.d_mx_f.cap || (size_t)M + 1 > gp.d_mx_k.cap || (size_t)C > gp.d_mx_c.cap || (size_t)3 * C > gp.d_mx_z.cap ||
-        (size_t)9 * C > gp.d_mx_W.cap) {
-        if (gp.mx_on_device > 0) {
-            gp.mx_stage.need((size_t)gp.mx_on_device);
-            HIPCHECK(hipMemcpyAsync(gp.mx_stage.p, gp.d_sel.p, (size_t)4 * gp.mx_on_device, hipMemcpyDeviceToHost, s));
-            HIPCHECK(hipStreamSynchronize(s));
-            memcpy(gp.mx_sel.data(), gp.mx_stage.p, (size_t)4 * gp.mx_on_device);
-        }
-        gp.d_mx_f.need(M); gp.d_sel.need(M); gp.d_mx_k.need((size_t)M + 1);
-        gp.d_mx_z.need((size_t)3 * C); gp.d_mx_W.need((size_t)9 * C); gp.d_mx_c.need(C);
-        gp.mx_on_device = 0; gp.mx_dirty = true; gp.mx_gen++;
-    }
-    const int m0 = gp.mx_dirty ? 0 : gp.mx_on_device, k0 = gp.mx_k[m0], s0 = std::min(gp.mx_on_device, M);
-    // staging layout (8-byte words): z | W | c | f, k, sel (ints, packed by two)
-    const size_t nz = (size_t)3 * (C - k0), nW = (size_t)9 * (C - k0), nc = (size_t)(C - k0);
-    const size_t ni = (size_t)(M - m0) + (size_t)(M + 1 - m0) + (size_t)(M - s0);
-    gp.mx_stage.need(nz + nW + nc + (ni + 1) / 2);
-    double *st = gp.mx_stage.p;
-    memcpy(st, gp.mx_z.data() + (size_t)3 * k0, 8 * nz);
-    memcpy(st + nz, gp.mx_W.data() + (size_t)9 * k0, 8 * nW);
-    memcpy(st + nz + nW, gp.mx_c.data() + k0, 8 * nc);
-    int *si = (int *)(st + nz + nW + nc);
-    memcpy(si, gp.mx_f.data() + m0, (size_t)4 * (M - m0));
-    memcpy(si + (M - m0), gp.mx_k.data() + m0, (size_t)4 * (M + 1 - m0));
-    memcpy(si + (M - m0) + (M + 1 - m0), gp.mx_sel.data() + s0, (size_t)4 * (M - s0));
-    if (nc) {
-        HIPCHECK(hipMemcpyAsync(gp.d_mx_z.p + (size_t)3 * k0, st, 8 * nz, hipMemcpyHostToDevice, s));
-        HIPCHECK(hipMemcpyAsync(gp.d_mx_W.p + (size_t)9 * k0, st + nz, 8 * nW, hipMemcpyHostToDevice, s));
-        HIPCHECK(hipMemcpyAsync(gp.d_mx_c.p + k0, st + nz + nW, 8 * nc, hipMemcpyHostToDevice, s));
-    }
-    HIPCHECK(hipMemcpyAsync(gp.d_mx_f.p + m0, si, (size_t)4 * (M - m0), hipMemcpyHostToDevice, s));
-    HIPCHECK(hipMemcpyAsync(gp.d_mx_k.p + m0, si + (M - m0), (size_t)4 * (M + 1 - m0), hipMemcpyHostToDevice, s));
-    if (M > s0) HIPCHECK(hipMemcpyAsync(gp.d_sel.p + s0, si + (M - m0) + (M + 1 - m0), (size_t)4 * (M - s0), hipMemcpyHostToDevice, s));
-    gp.mx_on_device = M; gp.mx_dirty = false;
 }
 // incremental steps: the max factors packed at or after entry f_from are selected on the host at the l_point mirror (max_select, the rule
 // k_select_mixture applies) and their slots of h_z / h_W take the winner -- the fast path uploads and linearises them as plain xyt factors
@@ -443,44 +480,6 @@ static void enqueue_chi2_mixture(GraphPack &gp, hipStream_t s) {
     if (M == 0) return;
     hipLaunchKernelGGL(k_chi2_mixture, dim3((M + TPB - 1) / TPB), dim3(TPB), 0, s, M, gp.d_mx_f.p, gp.d_mx_k.p, gp.d_mx_z.p, gp.d_mx_W.p, gp.d_mx_c.p,
                        gp.d_fa.p, gp.d_fb.p, gp.d_state.p, gp.d_chi2f.p);
-}
-// the robust table -> device, the rule of upload_mixture: what was appended since the last upload, everything after
-// an edit or a move.  d_rb_w receives the host's weights of the appended factors only: the device's own of the older ones stay
-static void upload_robust(GraphPack &gp) {
-    const int R = gp.n_robust();
-    if (R == 0 || (gp.rb_on_device == R && !gp.rb_dirty)) return;
-    hipStream_t s = gp.stream;
-    HIPCHECK(hipStreamSynchronize(s));       // (the pinned staging buffer is written below)
-    if ((size_t)R > gp.d_rb_f.cap || (size_t)R > gp.d_rb_kind.cap || (size_t)R > gp.d_rb_c.cap || (size_t)R > gp.d_rb_w.cap || (size_t)9 * R > gp.d_rb_W0.cap) {
-        if (gp.rb_on_device > 0) {
-            gp.rb_stage.need((size_t)gp.rb_on_device);
-            HIPCHECK(hipMemcpyAsync(gp.rb_stage.p, gp.d_rb_w.p, (size_t)8 * gp.rb_on_device, hipMemcpyDeviceToHost, s));
-            HIPCHECK(hipStreamSynchronize(s));
-            memcpy(gp.rb_w.data(), gp.rb_stage.p, (size_t)8 * gp.rb_on_device);
-        }
-        const size_t cap = (size_t)R + R / 2 + 64;
-        gp.d_rb_f.need(cap); gp.d_rb_kind.need(cap); gp.d_rb_c.need(cap); gp.d_rb_w.need(cap); gp.d_rb_W0.need(9 * cap);
-        gp.rb_on_device = 0; gp.rb_dirty = true; gp.rb_gen++;
-    }
-    const int q0 = gp.rb_dirty ? 0 : gp.rb_on_device, s0 = std::min(gp.rb_on_device, R);
-    // staging layout (8-byte words): W0 | c | w | f, kind (ints, packed by two)
-    const size_t n = (size_t)(R - q0), nw = (size_t)(R - s0);
-    gp.rb_stage.need(9 * n + n + nw + n);
-    double *st = gp.rb_stage.p;
-    memcpy(st, gp.rb_W0.data() + (size_t)9 * q0, 72 * n);
-    memcpy(st + 9 * n, gp.rb_c.data() + q0, 8 * n);
-    memcpy(st + 10 * n, gp.rb_w.data() + s0, 8 * nw);
-    int *si = (int *)(st + 10 * n + nw);
-    memcpy(si, gp.rb_f.data() + q0, 4 * n);
-    memcpy(si + n, gp.rb_kind.data() + q0, 4 * n);
-    if (n) {
-        HIPCHECK(hipMemcpyAsync(gp.d_rb_W0.p + (size_t)9 * q0, st, 72 * n, hipMemcpyHostToDevice, s));
-        HIPCHECK(hipMemcpyAsync(gp.d_rb_c.p + q0, st + 9 * n, 8 * n, hipMemcpyHostToDevice, s));
-        HIPCHECK(hipMemcpyAsync(gp.d_rb_f.p + q0, si, 4 * n, hipMemcpyHostToDevice, s));
-        HIPCHECK(hipMemcpyAsync(gp.d_rb_kind.p + q0, si + n, 4 * n, hipMemcpyHostToDevice, s));
-    }
-    if (nw) HIPCHECK(hipMemcpyAsync(gp.d_rb_w.p + s0, st + 10 * n, 8 * nw, hipMemcpyHostToDevice, s));
-    gp.rb_on_device = R; gp.rb_dirty = false;
 }
 // incremental steps: the robust factors packed at or after entry f_from are weighted on the host (robust_host_s + robust_weight, the rule
 // k_robust_weight applies) at the point the fast path linearises them -- the l_point mirror (xyt) or the state mirror (xytpos, as
@@ -509,36 +508,6 @@ static void enqueue_chi2_robust(GraphPack &gp, hipStream_t s) {
     if (R == 0) return;
     hipLaunchKernelGGL(k_chi2_robust, dim3((R + TPB - 1) / TPB), dim3(TPB), 0, s, R, gp.d_rb_f.p, gp.d_rb_kind.p, gp.d_rb_c.p, gp.d_rb_W0.p,
                        gp.d_fa.p, gp.d_fb.p, gp.d_z.p, gp.d_state.p, gp.d_chi2f.p);
-}
-// the polar table -> device, the rule of upload_robust: what was appended since the last upload, everything after an
-// edit or a move
-static void upload_polar(GraphPack &gp) {
-    const int P = gp.n_polar();
-    if (P == 0 || (gp.pl_on_device == P && !gp.pl_dirty)) return;
-    hipStream_t s = gp.stream;
-    HIPCHECK(hipStreamSynchronize(s));       // (the pinned staging buffer is written below)
-    if ((size_t)P > gp.d_pl_f.cap || (size_t)P > gp.d_pl_kind.cap || (size_t)2 * P > gp.d_pl_z.cap || (size_t)4 * P > gp.d_pl_W.cap) {
-        const size_t cap = (size_t)P + P / 2 + 64;
-        gp.d_pl_f.need(cap); gp.d_pl_kind.need(cap); gp.d_pl_z.need(2 * cap); gp.d_pl_W.need(4 * cap);
-        gp.pl_on_device = 0; gp.pl_dirty = true; gp.pl_gen++;
-    }
-    const int q0 = gp.pl_dirty ? 0 : gp.pl_on_device;
-    // staging layout (8-byte words): z | W | f, kind (ints, packed by two)
-    const size_t n = (size_t)(P - q0);
-    gp.pl_stage.need(2 * n + 4 * n + n);
-    double *st = gp.pl_stage.p;
-    memcpy(st, gp.pl_z.data() + (size_t)2 * q0, 16 * n);
-    memcpy(st + 2 * n, gp.pl_W.data() + (size_t)4 * q0, 32 * n);
-    int *si = (int *)(st + 6 * n);
-    memcpy(si, gp.pl_f.data() + q0, 4 * n);
-    memcpy(si + n, gp.pl_kind.data() + q0, 4 * n);
-    if (n) {
-        HIPCHECK(hipMemcpyAsync(gp.d_pl_z.p + (size_t)2 * q0, st, 16 * n, hipMemcpyHostToDevice, s));
-        HIPCHECK(hipMemcpyAsync(gp.d_pl_W.p + (size_t)4 * q0, st + 2 * n, 32 * n, hipMemcpyHostToDevice, s));
-        HIPCHECK(hipMemcpyAsync(gp.d_pl_f.p + q0, si, 4 * n, hipMemcpyHostToDevice, s));
-        HIPCHECK(hipMemcpyAsync(gp.d_pl_kind.p + q0, si + n, 4 * n, hipMemcpyHostToDevice, s));
-    }
-    gp.pl_on_device = P; gp.pl_dirty = false;
 }
 // incremental steps: the slots of the polar factors packed at or after entry f_from are written on the host (polar.h, the formulas
 // k_polar_slot applies) at the l_point mirror -- the fast path uploads and linearises them as plain xyt factors
@@ -604,6 +573,8 @@ static void upload_fixed(GraphPack &gp) {
     HIPCHECK(hipStreamSynchronize(gp.stream));      // (the sources are pageable)
     gp.fx_dirty = false; gp.fx_topo = gp.topo_version;
 }
+// the families' tables -> device (SideTable::upload): rows appended or edited since the last call, for the kernels of the step that follows
+static void upload_tables(GraphPack &gp) { gp.mx.upload(gp.stream); gp.rb.upload(gp.stream); gp.pl.upload(gp.stream); }
 static void upload_factors(GraphPack &gp) {
     const int F = gp.F;
     if (F > gp.F_cap) {           // reallocation loses the old content: re-upload everything
@@ -628,9 +599,7 @@ static void upload_factors(GraphPack &gp) {
     gp.dirty_lo = gp.dirty_hi = 0;
     gp.F_on_device = F;
     gp.d_scalar.need(8); gp.h_scalar.need(8);
-    upload_mixture(gp);
-    upload_robust(gp);
-    upload_polar(gp);
+    upload_tables(gp);
 }
 // evaluate the host factors [from, end) through their vtable (aprilsam.c:156 calls factor->eval the same way) and form
 // (J_a^T W) J_a, (J_a^T W) J_b, (J_b^T W) J_b, (J^T W) r in the reference's association (aprilsam.c:162-187)

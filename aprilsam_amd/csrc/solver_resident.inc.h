@@ -58,15 +58,9 @@ static int resident_steps_impl(april_graph_t *g, april_graph_cholesky_param_t *p
             HIPCHECK(hipMemcpyAsync(gp.d_lp_last.p, gp.d_lp.p, (size_t)24 * N, hipMemcpyDeviceToDevice, s));
             gp.lp_last_valid = true;
         }
-        if (mode == 1) {
-            NumericArgs a; a.ktime = true; a.relin = true;
-            enqueue_numeric(c, gp, s, a);
-            HIPCHECK(hipStreamSynchronize(s));
-            collect_kernel_times(c);
-        } else {
-            RunArgs r; r.relin = true;
-            run_numeric(c, gp, r);
-        }
+        RunArgs r; r.relin = true; r.ktime = mode == 1;
+        run_numeric(c, gp, r);
+        if (mode == 1) { HIPCHECK(hipStreamSynchronize(s)); collect_kernel_times(c); }
     }
     return 0;
 }

@@ -332,3 +332,21 @@ def test_refusals(lib, tmp_path):
     with pytest.raises(RuntimeError):
         g.max_selected(p, [g.n_factors])
     p.destroy(); g.destroy()
+
+
+# ---- a table move with device-written selections in flight --------------------------------------------------------------------
+def test_selections_survive_a_move_of_the_table(lib):
+    """tests/support/table_move.py: 140 max factors (K = 2) appended one or two per incremental step, 6 of them before the first batch
+    step and a second batch step at the 56th.  The component table moves whenever one of its buffers runs out of room (the capacities
+    are worked out in that file: under the rule of commit 362a7eb at 9, 13, 19, 28, 42, 63 and 94 factors, under the robust table's rule
+    at 41 and 73), and every selection k_select_mixture wrote must come through: aprilsam_amd_max_selected before and after every
+    fast-path step agrees for every older factor.  The steps that take the count past each of those capacities are fast-path steps, and
+    so are at least 90 % of all steps (a re-planned step selects everything again and proves nothing).  Checked on a scratch copy: with
+    the read-back before the move deleted, this test fails (the first batch step's selections come back as -1)."""
+    from tests.support import table_move as tm
+    r = tm.grow(lib, tm.scene(3), lambda g, a, b, z, W: g.add_factor_max(a, b, *mm.two_component(z, W)), lambda g, p, idx: g.max_selected(p, idx))
+    print(f"max factors {r['family']}, incremental steps {r['steps']}, fast path {r['fast']}, (step, factor) pairs compared {r['checked']}")
+    assert r["family"] >= tm.FAMILY_FACTORS_MIN and r["fast"] >= 0.9 * r["steps"]
+    for cap in tm.ROW_CAPS["max"]:
+        assert any(lo <= cap < hi for lo, hi in r["spans"]), (cap, r["spans"])
+    assert set(r["values"].tolist()) == {0, 1}                              # both components won somewhere

@@ -463,3 +463,24 @@ def test_refusals(lib, tmp_path):
         g.robust_weights(p, [g.n_factors])
     for gg, pp in ((g, p), (gf, pf)):
         pp.destroy(); gg.destroy()
+
+
+# ---- a table move with device-written weights in flight -----------------------------------------------------------------------
+def test_weights_survive_a_move_of_the_table(lib):
+    """tests/support/table_move.py: 140 robust factors (Cauchy) appended one or two per incremental step, 6 of them before the first
+    batch step and a second batch step at the 56th.  The table is allocated for n + n / 2 + 64 rows -- 73 at the first upload -- so it
+    moves when the 74th factor arrives, and every weight k_robust_weight wrote must come through: aprilsam_amd_robust_weights before and
+    after every fast-path step agrees bit for bit for every older factor.  The step that takes the count past 73 is a fast-path step,
+    and so are at least 90 % of all steps (a re-planned step weights everything again and proves nothing).  Checked on a scratch copy:
+    with the read-back before the move deleted, this test fails (the weights of the batch steps come back as the host's stale ones)."""
+    from tests.support import table_move as tm
+
+    def add(g, a, b, z, W):
+        g.add_factor_xyt(a, b, z, W)
+        assert g.set_robust(g.n_factors - 1, rm.CAUCHY, 1.0) == 0
+    r = tm.grow(lib, tm.scene(4), add, lambda g, p, idx: g.robust_weights(p, idx))
+    print(f"robust factors {r['family']}, incremental steps {r['steps']}, fast path {r['fast']}, (step, factor) pairs compared {r['checked']}")
+    assert r["family"] >= tm.FAMILY_FACTORS_MIN and r["fast"] >= 0.9 * r["steps"]
+    for cap in tm.ROW_CAPS["robust"]:
+        assert any(lo <= cap < hi for lo, hi in r["spans"]), (cap, r["spans"])
+    assert np.all((r["values"] > 0) & (r["values"] <= 1)) and np.min(r["values"]) < 0.5 and np.max(r["values"]) > 0.9      # (Cauchy: below 1 wherever s > 0)
