@@ -148,6 +148,11 @@ ROBUST_NONE, ROBUST_HUBER, ROBUST_CAUCHY, ROBUST_DCS = 0, 1, 2, 3
 POLAR_RANGE, POLAR_BEARING, POLAR_RANGE_BEARING = 1, 2, 3
 FACTOR_POLAR_TYPE = 4
 
+# dense Gaussian factor on k nodes, information form (include/aprilsam_amd.h: aprilsam_amd_factor_gaussian_create)
+FACTOR_GAUSSIAN_TYPE = 5
+GAUSSIAN_MAX_NODES = 11
+MARGINAL_MAX_NODES = 40        # aprilsam_amd_marginal_prior: removed nodes + blanket nodes
+
 # measured LP64 layout of the reference; checked by tests/test_abi.py
 EXPECTED_SIZES = {"ZArray": 24, "Graph": 32, "Factor": 104, "Node": 112, "CholeskyParam": 128}
 EXPECTED_OFFSETS = {

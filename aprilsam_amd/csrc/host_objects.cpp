@@ -10,6 +10,8 @@
 // (max_select) is the one the incremental path applies on the host and k_select_mixture restates on the device.  Robust losses on xyt /
 // xytpos factors are kept here as well: a tagged block hung off u.common.impl, applied by eval_finish.  Range, bearing
 // and range-bearing factors (type 4) are built here: true m-row factors on the host, xyt slots on the device (polar.h).
+// Dense Gaussian factors on k nodes (type 5) and the graph edit that removes nodes are here as well: the factor's
+// square-root form (a pivoted Cholesky) is what its host evaluation returns; the device takes Lambda and eta as they are (gaussian.hip.h).
 #include <atomic>
 #include <cmath>
 #include <cstdio>
@@ -344,9 +346,176 @@ april_graph_factor_t *polar_copy(april_graph_factor_t *f) {
     return c;
 }
 
+// ---- dense Gaussian factor on k nodes, information form --------------------------------------
+// u.common as the reference lays it out: z holds xbar (3 k) then eta (3 k), W is Lambda (3 k x 3 k), ztruth stays NULL; the square-root
+// form the host evaluation returns lives in a tagged block hung off u.common.impl, with a copy of the eta and Lambda it was made from
+// (z and W may be edited in place: gaussian_refresh factorises again).
+constexpr unsigned long long GAUSSIAN_TAG = 0x67617573735f616dULL;     // "gauss_am"
+struct GaussianBlock {
+    unsigned long long tag = GAUSSIAN_TAG; int k = 0, rank = 0; bool ok = false; double c0 = 0;
+    std::vector<double> R, d, snap;      // R: rank x 3k row-major (R'R = Lambda), d: rank (R'd = eta), snap: eta (3k) + Lambda (9 k^2) as factorised
+};
+std::atomic<bool> g_gaussian_ever{ false };
+april_graph_factor_eval_t *gaussian_eval(april_graph_factor_t *f, april_graph_t *g, april_graph_factor_eval_t *e);
+GaussianBlock *own_gaussian(const april_graph_factor_t *f) {
+    if (f->type != APRILSAM_AMD_FACTOR_GAUSSIAN_TYPE || f->eval != gaussian_eval) return nullptr;
+    void *p = f->u.common.impl;
+    GaussianBlock *b = (p && *(const unsigned long long *)p == GAUSSIAN_TAG) ? (GaussianBlock *)p : nullptr;
+    return (b && f->nnodes == b->k && f->nodes && f->u.common.z && f->u.common.W) ? b : nullptr;
+}
+// Diagonally pivoted Cholesky of the n x n matrix L (row-major, bitwise symmetric), LAPACK dpstrf's default stop: the largest remaining
+// diagonal <= n eps max diag.  R (rank x n, columns in the ORIGINAL order) with R'R = L; d with R'd = eta from the triangular solve in pivot
+// order.  false: L is not finite, not symmetric or not positive semi-definite (a remaining diagonal below -10 times the stop bound)
+bool gaussian_factorise(int n, const double *eta, const double *L, int *rank_out, std::vector<double> &R, std::vector<double> &d, double *c0) {
+    for (int i = 0; i < n; i++) {
+        if (!std::isfinite(eta[i])) return false;
+        for (int j = 0; j < n; j++) {
+            if (!std::isfinite(L[(size_t)i * n + j])) return false;
+            if (memcmp(&L[(size_t)i * n + j], &L[(size_t)j * n + i], 8) != 0) return false;
+        }
+    }
+    std::vector<double> A(L, L + (size_t)n * n), Rp((size_t)n * n, 0.0);
+    std::vector<int> piv((size_t)n);
+    for (int i = 0; i < n; i++) piv[i] = i;
+    double amax = 0;
+    for (int i = 0; i < n; i++) { if (A[(size_t)i * n + i] < 0) return false; amax = std::max(amax, A[(size_t)i * n + i]); }
+    const double tol = (double)n * 2.220446049250313e-16 * amax;
+    int rank = 0;
+    for (int j = 0; j < n; j++) {
+        int p = j;
+        for (int i = j + 1; i < n; i++) if (A[(size_t)i * n + i] > A[(size_t)p * n + p]) p = i;      // (the first of equal candidates)
+        if (!(A[(size_t)p * n + p] > tol)) break;
+        if (p != j) {                  // symmetric interchange of the remainder, and of the columns of the rows of R made so far
+            for (int i = 0; i < n; i++) std::swap(A[(size_t)i * n + j], A[(size_t)i * n + p]);
+            for (int i = 0; i < n; i++) std::swap(A[(size_t)j * n + i], A[(size_t)p * n + i]);
+            for (int l = 0; l < j; l++) std::swap(Rp[(size_t)l * n + j], Rp[(size_t)l * n + p]);
+            std::swap(piv[j], piv[p]);
+        }
+        const double rjj = sqrt(A[(size_t)j * n + j]);
+        Rp[(size_t)j * n + j] = rjj;
+        for (int i = j + 1; i < n; i++) Rp[(size_t)j * n + i] = A[(size_t)j * n + i] / rjj;
+        for (int i = j + 1; i < n; i++)
+            for (int l = j + 1; l < n; l++) A[(size_t)i * n + l] -= Rp[(size_t)j * n + i] * Rp[(size_t)j * n + l];
+        rank = j + 1;
+    }
+    for (int i = rank; i < n; i++) if (A[(size_t)i * n + i] < -10.0 * tol) return false;
+    if (amax == 0)                     // (a zero diagonal: positive semi-definite only as the zero matrix)
+        for (size_t i = 0; i < (size_t)n * n; i++) if (L[i] != 0) return false;
+    R.assign((size_t)rank * n, 0.0); d.assign((size_t)rank, 0.0);
+    for (int l = 0; l < rank; l++)
+        for (int c = 0; c < n; c++) R[(size_t)l * n + piv[c]] = Rp[(size_t)l * n + c];
+    double cc = 0;
+    for (int l = 0; l < rank; l++) {   // R11' d = (P' eta)[0:rank], forward
+        double acc = eta[piv[l]];
+        for (int m = 0; m < l; m++) acc -= Rp[(size_t)m * n + l] * d[m];
+        d[l] = acc / Rp[(size_t)l * n + l];
+        cc += d[l] * d[l];
+    }
+    *rank_out = rank; *c0 = cc;
+    return true;
+}
+// the block against the object: factorised again when eta or Lambda were edited in place.  false: they are not admissible (any more)
+bool gaussian_refresh(const april_graph_factor_t *f, GaussianBlock *b) {
+    const int n = 3 * b->k;
+    if ((int)f->u.common.W->nrows != n || (int)f->u.common.W->ncols != n) { b->ok = false; b->snap.clear(); return false; }
+    const double *eta = f->u.common.z + n, *L = f->u.common.W->data;
+    const size_t nl = (size_t)n * n;
+    if (b->snap.size() == n + nl && memcmp(b->snap.data(), eta, (size_t)8 * n) == 0 && memcmp(b->snap.data() + n, L, 8 * nl) == 0) return b->ok;
+    b->snap.assign(eta, eta + n); b->snap.insert(b->snap.end(), L, L + nl);
+    b->ok = gaussian_factorise(n, eta, L, &b->rank, b->R, b->d, &b->c0);
+    if (!b->ok) { b->rank = 0; b->R.clear(); b->d.clear(); b->c0 = 0; }
+    return b->ok;
+}
+// april_graph_factor_eval_destroy frees the Jacobians [0, min(length, k)) and r (april_graph.c:38-46): those Jacobians are blocks of their
+// own, the others live behind r in r's block
+april_graph_factor_eval_t *gaussian_eval_alloc(int k, int L) {
+    april_graph_factor_eval_t *e = (april_graph_factor_eval_t *)calloc(1, sizeof(*e));
+    e->jacobians = (matd_t **)calloc((size_t)k + 1, sizeof(matd_t *));            // NULL-terminated
+    const size_t one = sizeof(matd_t) + (size_t)L * 3 * sizeof(double), rlen = (size_t)std::max(L, 1) * sizeof(double);
+    const int nsep = std::min(L, k);
+    for (int i = 0; i < nsep; i++) e->jacobians[i] = (matd_t *)calloc(1, one);
+    char *blk = (char *)calloc(1, rlen + (size_t)(k - nsep) * one);
+    e->r = (double *)blk;
+    for (int i = nsep; i < k; i++) e->jacobians[i] = (matd_t *)(blk + rlen + (size_t)(i - nsep) * one);
+    for (int i = 0; i < k; i++) { e->jacobians[i]->nrows = (unsigned)L; e->jacobians[i]->ncols = 3; }
+    e->W = matd_new(L, L, nullptr);
+    e->length = L;
+    return e;
+}
+april_graph_factor_eval_t *gaussian_eval_at(april_graph_factor_t *f, april_graph_t *g, april_graph_factor_eval_t *e, bool at_state) {
+    GaussianBlock *b = own_gaussian(f);
+    if (!b || !gaussian_refresh(f, b)) return nullptr;
+    const int k = b->k, n = 3 * k, L = b->rank;
+    if (e && e->length != L) { april_graph_factor_eval_destroy(e); e = nullptr; }      // (the rank changed with an edit)
+    if (!e) e = gaussian_eval_alloc(k, L);
+    april_graph_node_t **ns = (april_graph_node_t **)g->nodes->data;
+    std::vector<double> delta((size_t)n);
+    for (int i = 0; i < k; i++) {
+        const double *p = at_state ? ns[f->nodes[i]]->state : ns[f->nodes[i]]->l_point, *xb = f->u.common.z + 3 * i;
+        delta[3 * i] = p[0] - xb[0]; delta[3 * i + 1] = p[1] - xb[1]; delta[3 * i + 2] = mod2pi_h(p[2] - xb[2]);
+    }
+    double chi2 = 0;
+    for (int l = 0; l < L; l++) {
+        double acc = 0;
+        for (int c = 0; c < n; c++) acc += b->R[(size_t)l * n + c] * delta[c];
+        e->r[l] = b->d[l] - acc;
+        chi2 += e->r[l] * e->r[l];
+        for (int i = 0; i < k; i++)
+            for (int c = 0; c < 3; c++) e->jacobians[i]->data[l * 3 + c] = b->R[(size_t)l * n + 3 * i + c];
+        for (int m = 0; m < L; m++) e->W->data[(size_t)l * L + m] = l == m ? 1.0 : 0.0;
+    }
+    e->length = L; e->chi2 = chi2;
+    return e;
+}
+april_graph_factor_eval_t *gaussian_eval(april_graph_factor_t *f, april_graph_t *g, april_graph_factor_eval_t *e) { return gaussian_eval_at(f, g, e, false); }
+april_graph_factor_eval_t *gaussian_state_eval(april_graph_factor_t *f, april_graph_t *g, april_graph_factor_eval_t *e) { return gaussian_eval_at(f, g, e, true); }
+void gaussian_destroy(april_graph_factor_t *f) {
+    delete own_gaussian(f);
+    free(f->nodes); free(f->u.common.z); free(f->u.common.ztruth); free(f->u.common.W);
+    attr_free(f->attr);
+    free(f);
+}
+april_graph_factor_t *gaussian_copy(april_graph_factor_t *f);
+// nullptr when eta / Lambda are refused (nothing is owned then)
+april_graph_factor_t *gaussian_make(int k, const int *nodes, const double *xbar_eta, const double *Lambda) {
+    const int n = 3 * k;
+    GaussianBlock *blk = new GaussianBlock(); blk->k = k;
+    april_graph_factor_t *f = (april_graph_factor_t *)calloc(1, sizeof(april_graph_factor_t));
+    f->type = APRILSAM_AMD_FACTOR_GAUSSIAN_TYPE;
+    f->nnodes = k;
+    f->nodes = (int *)calloc((size_t)k, sizeof(int));
+    memcpy(f->nodes, nodes, sizeof(int) * (size_t)k);
+    f->u.common.z = (double *)malloc(sizeof(double) * (size_t)2 * n);
+    memcpy(f->u.common.z, xbar_eta, sizeof(double) * (size_t)2 * n);
+    f->u.common.W = matd_new(n, n, Lambda);
+    f->u.common.impl = blk;
+    f->copy = gaussian_copy; f->eval = gaussian_eval; f->state_eval = gaussian_state_eval; f->destroy = gaussian_destroy;
+    if (!gaussian_refresh(f, blk)) { gaussian_destroy(f); return nullptr; }
+    f->length = blk->rank;
+    g_gaussian_ever.store(true, std::memory_order_relaxed);
+    return f;
+}
+april_graph_factor_t *gaussian_copy(april_graph_factor_t *f) {
+    if (!own_gaussian(f)) return nullptr;
+    april_graph_factor_t *c = gaussian_make(f->nnodes, f->nodes, f->u.common.z, f->u.common.W->data);
+    if (c) c->attr = attr_clone(f->attr);
+    return c;
+}
+
 }  // namespace
 
 namespace asam {
+
+bool gaussian_of(const april_graph_factor_t *f, int *k, double *c0, bool *ok) {
+    GaussianBlock *b = own_gaussian(f);
+    if (!b) return false;
+    const bool good = gaussian_refresh(f, b);
+    if (k) *k = b->k;
+    if (c0) *c0 = b->c0;
+    if (ok) *ok = good;
+    return true;
+}
+bool gaussian_ever() { return g_gaussian_ever.load(std::memory_order_relaxed); }
 
 bool is_native_max(const april_graph_factor_t *f) { return f->type == APRILSAM_AMD_FACTOR_MAX_TYPE && f->eval == max_eval; }
 
@@ -546,6 +715,40 @@ int aprilsam_amd_factor_get_polar(const april_graph_factor_t *f, int *kind) {
     return 0;
 }
 
+april_graph_factor_t *aprilsam_amd_factor_gaussian_create(int k, const int *nodes, const double *xbar, const double *eta, const double *Lambda) {
+    const char *who = "aprilsam_amd_factor_gaussian_create: ";
+    if (!nodes || !xbar || !eta || !Lambda || k < 1) {
+        asam::set_last_error(asam::ERR_BAD_GRAPH, std::string(who) + "k = " + std::to_string(k) + " (at least 1) or a null argument");
+        return nullptr;
+    }
+    if (k > APRILSAM_AMD_GAUSSIAN_MAX_NODES) {
+        asam::set_last_error(asam::ERR_UNSUPPORTED, std::string(who) + "k = " + std::to_string(k) + " nodes (1 to " + std::to_string(APRILSAM_AMD_GAUSSIAN_MAX_NODES) +
+                             " are supported: the clique limit of factors with more than two nodes)");
+        return nullptr;
+    }
+    for (int i = 0; i < k; i++)
+        for (int j = 0; j < i; j++)
+            if (nodes[i] == nodes[j]) {
+                asam::set_last_error(asam::ERR_BAD_GRAPH, std::string(who) + "node " + std::to_string(nodes[i]) + " is named twice: the node ids must be distinct");
+                return nullptr;
+            }
+    std::vector<double> ze((size_t)6 * k);
+    for (int i = 0; i < 3 * k; i++) {
+        if (!std::isfinite(xbar[i]) || !std::isfinite(eta[i])) { asam::set_last_error(asam::ERR_BAD_GRAPH, std::string(who) + "xbar and eta must be finite"); return nullptr; }
+        ze[i] = xbar[i]; ze[(size_t)3 * k + i] = eta[i];
+    }
+    april_graph_factor_t *f = gaussian_make(k, nodes, ze.data(), Lambda);
+    if (!f) asam::set_last_error(asam::ERR_UNSUPPORTED, std::string(who) + "Lambda must be finite, symmetric (mirror entries bitwise equal) and positive semi-definite");
+    return f;
+}
+
+int aprilsam_amd_factor_get_gaussian(const april_graph_factor_t *f, int *k) {
+    int kk = 0;
+    if (f) (void)asam::gaussian_of(f, &kk, nullptr, nullptr);
+    if (k) *k = kk;
+    return 0;
+}
+
 int aprilsam_amd_debug_polar_slot(int kind, const double *pa, const double *pb, const double *z, const double *W, double *z_eff3, double *W_eff9) {
     if (kind < APRILSAM_AMD_POLAR_RANGE || kind > APRILSAM_AMD_POLAR_RANGE_BEARING || !pa || !pb || !z || !W || !z_eff3 || !W_eff9) {
         asam::set_last_error(asam::ERR_BAD_GRAPH, "aprilsam_amd_debug_polar_slot: kind out of range (1 to 3) or a null argument");
@@ -584,6 +787,58 @@ void april_graph_destroy(april_graph_t *g) {
     free(g->factors->data); free(g->factors);
     attr_free(g->attr);
     free(g);
+}
+
+// the graph edit.  Everything is validated before anything is touched
+int aprilsam_amd_graph_remove_nodes(april_graph_t *g, int m, const int *remove, int *new_index) {
+    const char *who = "aprilsam_amd_graph_remove_nodes: ";
+    if (!g || !g->nodes || !g->factors || m < 0 || (m > 0 && !remove)) { asam::set_last_error(asam::ERR_BAD_GRAPH, std::string(who) + "null argument or negative count"); return asam::ERR_BAD_GRAPH; }
+    const int N = g->nodes->size, F = g->factors->size;
+    april_graph_node_t **ns = (april_graph_node_t **)g->nodes->data;
+    april_graph_factor_t **fs = (april_graph_factor_t **)g->factors->data;
+    std::vector<int> idx((size_t)N, 0);               // 0: kept, -1: removed; the new index afterwards
+    for (int i = 0; i < m; i++) {
+        if (remove[i] < 0 || remove[i] >= N) { asam::set_last_error(asam::ERR_BAD_GRAPH, std::string(who) + "node " + std::to_string(remove[i]) + " out of range (" + std::to_string(N) + " nodes)"); return asam::ERR_BAD_GRAPH; }
+        if (idx[remove[i]] < 0) { asam::set_last_error(asam::ERR_BAD_GRAPH, std::string(who) + "node " + std::to_string(remove[i]) + " is listed twice"); return asam::ERR_BAD_GRAPH; }
+        idx[remove[i]] = -1;
+    }
+    auto nodes_ok = [&](const april_graph_factor_t *f) {
+        if (!f || f->nnodes < 0 || (f->nnodes > 0 && !f->nodes)) return false;
+        for (int k = 0; k < f->nnodes; k++) if (f->nodes[k] < 0 || f->nodes[k] >= N) return false;
+        return true;
+    };
+    for (int i = 0; i < F; i++) {
+        bool ok = nodes_ok(fs[i]);
+        if (ok && asam::is_native_max(fs[i]))
+            for (int j = 0; j < fs[i]->u.max.nfactors && ok; j++) ok = nodes_ok(fs[i]->u.max.factors[j]);
+        if (!ok) { asam::set_last_error(asam::ERR_BAD_GRAPH, std::string(who) + "factor " + std::to_string(i) + " names a node outside the graph"); return asam::ERR_BAD_GRAPH; }
+    }
+    for (int i = 0, k = 0; i < N; i++) if (idx[i] == 0) idx[i] = k++;
+    if (new_index) memcpy(new_index, idx.data(), sizeof(int) * (size_t)N);
+    if (m == 0) return 0;
+    asam::drop_graph_pack(g);                         // (the device copy describes the graph before the edit)
+    int nf = 0;
+    for (int i = 0; i < F; i++) {
+        april_graph_factor_t *f = fs[i];
+        bool gone = false;                            // (a max factor is judged by its own nodes)
+        for (int k = 0; k < f->nnodes; k++) gone = gone || idx[f->nodes[k]] < 0;
+        if (gone) { f->destroy(f); continue; }
+        for (int k = 0; k < f->nnodes; k++) f->nodes[k] = idx[f->nodes[k]];
+        if (asam::is_native_max(f))
+            for (int j = 0; j < f->u.max.nfactors; j++) {
+                april_graph_factor_t *cf = f->u.max.factors[j];
+                for (int k = 0; k < cf->nnodes; k++) cf->nodes[k] = idx[cf->nodes[k]] < 0 ? cf->nodes[k] : idx[cf->nodes[k]];
+            }
+        fs[nf++] = f;
+    }
+    g->factors->size = nf;
+    int nn = 0;
+    for (int i = 0; i < N; i++) {
+        if (idx[i] < 0) { ns[i]->destroy(ns[i]); continue; }
+        ns[nn++] = ns[i];
+    }
+    g->nodes->size = nn;
+    return 0;
 }
 
 april_graph_node_t *april_graph_node_xyt_create(const double *state, const double *init, const double *truth) {

@@ -55,6 +55,7 @@ struct Options {
     int pool_poison = 0;          // debug: 1 = before every step, the update block of every front the step (re)factorises and x at its own positions are filled with NaN: a dependency wait of a multi-level launch that passes early yields NaN instead of the previous step's numbers
     int skip_flag_waits = 0;      // debug, negative control of pool_poison: 1 = the fronts of the batch path's multi-level factorisation launch do NOT wait for their children
     int polar_on_host = 0;        // debug: 1 = polar factors are packed as host-evaluated foreign factors through their own eval() (the A/B oracle of the native path)
+    int gaussian_on_host = 0;     // debug: 1 = dense Gaussian factors are packed as host-evaluated cliques through their own eval() (the A/B oracle of the native path)
     int panel_mode = 1;           // fronts too large for LDS whose own columns fit run in k_front_small's panel mode
 };
 extern Options g_opt;
@@ -135,10 +136,17 @@ bool plain_common_factor(const april_graph_factor_t *f);           // an xyt / x
 double robust_host_s(const double *z, const double *w, const double *pa, const double *pb);      // r^T W r at pa (/ pb: xyt), eval_finish's association
 // range / bearing / range-bearing factors (host_objects.cpp): true for this library's polar factor, with its kind
 bool polar_of(const april_graph_factor_t *f, int *kind);
+// dense Gaussian factors (host_objects.cpp): true for this library's Gaussian factor, with its node count, its chi^2
+// constant c0 and whether eta / Lambda (as they stand now: edited in place, they are factorised again here) are admissible
+bool gaussian_of(const april_graph_factor_t *f, int *k, double *c0, bool *ok);
+bool gaussian_ever();                                            // false until the process makes its first Gaussian factor: graphs are not walked for them before
 // fixed nodes (host_objects.cpp): true for an xyt node of this library that is held constant
 bool node_fixed(const april_graph_node_t *n);
 bool fixed_ever();                                               // false until the process fixes its first node: graphs are not walked for flags before
 int robust_weights(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *factors, double *w);   // solver_calls.inc.h
 int factor_audit(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *factors, double *out);   // solver_audit.inc.h
+int marginal_prior(april_graph_t *g, april_graph_cholesky_param_t *param, int m, const int *remove, int cap, int *n_keep, int *keep, double *xbar, double *eta,
+                   double *Lambda);                                                                                 // solver_marginal_prior.inc.h
+int graph_marginalize(april_graph_t *g, april_graph_cholesky_param_t *param, int m, const int *remove, int *new_index);
 
 }  // namespace asam

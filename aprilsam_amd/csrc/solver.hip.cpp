@@ -31,6 +31,7 @@
 #include "maxmix.hip.h"
 #include "robust.hip.h"
 #include "polar.hip.h"
+#include "gaussian.hip.h"
 #include "fixed.hip.h"
 #include "gnc.hip.h"
 #include "lm.hip.h"
@@ -86,7 +87,7 @@ static const OptionDef OPTION_TABLE[] = {
     { "wave_backsolve", &Options::wave_backsolve, 0, false }, { "tagged_x", &Options::tagged_x, 0, false, 2 }, { "blk_backsolve", &Options::blk_backsolve, 0, false }, { "tail_poses", &Options::tail_poses, 8, false },
     { "batch_extend", &Options::batch_extend, 0, true }, { "extend_tail_fronts", &Options::extend_tail_fronts, 0, true }, { "mem_cap_mb", &Options::mem_cap_mb, 0, true }, { "solve_chunk_cols", &Options::solve_chunk_cols, 0, true },
     { "pool_guard", &Options::pool_guard, 0, false }, { "amalg", &Options::amalg, 0, false }, { "amalg_max", &Options::amalg_max, 1, false }, { "pool_poison", &Options::pool_poison, 0, false }, { "skip_flag_waits", &Options::skip_flag_waits, 0, false },
-    { "polar_on_host", &Options::polar_on_host, 0, false, 1 }, { "asm_balance", &Options::asm_balance, 0, false, 1 },
+    { "polar_on_host", &Options::polar_on_host, 0, false, 1 }, { "gaussian_on_host", &Options::gaussian_on_host, 0, false, 1 }, { "asm_balance", &Options::asm_balance, 0, false, 1 },
 };
 static const OptionDef *find_option(const char *name) {
     for (const OptionDef &d : OPTION_TABLE) if (!strcmp(d.name, name)) return &d;
@@ -256,6 +257,7 @@ struct PatchList {
 #include "solver_marginals.inc.h"
 #include "solver_gating.inc.h"
 #include "solver_audit.inc.h"
+#include "solver_marginal_prior.inc.h"
 #include "solver_treesolve.inc.h"
 #include "solver_lm.inc.h"
 #include "solver_gnc.inc.h"
@@ -522,6 +524,13 @@ extern "C" int aprilsam_amd_robust_weights(april_graph_t *graph, april_graph_cho
 }
 extern "C" int aprilsam_amd_factor_audit(april_graph_t *graph, april_graph_cholesky_param_t *param, int n, const int *factors, double *out) {
     return asam::factor_audit(graph, param, n, factors, out);
+}
+extern "C" int aprilsam_amd_marginal_prior(april_graph_t *graph, april_graph_cholesky_param_t *param, int m, const int *remove, int cap, int *n_keep, int *keep,
+                                           double *xbar, double *eta, double *Lambda) {
+    return asam::marginal_prior(graph, param, m, remove, cap, n_keep, keep, xbar, eta, Lambda);
+}
+extern "C" int aprilsam_amd_graph_marginalize(april_graph_t *graph, april_graph_cholesky_param_t *param, int m, const int *remove, int *new_index) {
+    return asam::graph_marginalize(graph, param, m, remove, new_index);
 }
 extern "C" long long aprilsam_amd_debug_selinv_runs(const april_graph_cholesky_param_t *param) { return asam::selinv_runs(param); }
 extern "C" int aprilsam_amd_marginals_joint_any(april_graph_t *graph, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, double *cov) {

@@ -3,44 +3,67 @@
 // leverage, its leave-one-out distance and its checkability (audit.hip.h), from the selected inversion's Sigma pool
 // (solver_marginals.inc.h) and the linearisation slots of the graph's pack.  DESIGN.md section 23.
 // ------------------------------------------------------------------------------------------------------
+// The retained linearisation of a param's last factorisation, for the calls that read the contribution slots, d_lp and d_dx of the graph's
+// pack as that factorisation saw them (the factor audit; the marginal prior, solver_marginal_prior.inc.h): 0 with the context, the pack and
+// Fg, the number of graph factors wholly inside the factorised entries -- or the refusal's code (-1 / -12 / -13 / -14), recorded.  `what`
+// names the caller's product in the messages ("the audit").  The caller holds the SlotLock.
+static int retained_linearisation(april_graph_t *g, april_graph_cholesky_param_t *param, const char *who, const char *what, Context *&cp, GraphPack *&gpp, int &Fg) {
+    char msg[640];
+    if (int rc = ps_context(param, who, cp, g)) return rc;
+    Context &c = *cp;
+    if (c.fact_kind == FACT_EXTENDED) {
+        snprintf(msg, sizeof msg, "%s: the retained factor is an incremental step's extended structure: the device slots of a fast "
+                                  "incremental step are not a consistent picture of the factorised system (new robust and polar factors are weighted on the host, old "
+                                  "factors keep stale linearisations); a batch call that plans anew (april_graph_cholesky: the second in a row, or under option batch_extend = 0) "
+                                  "makes %s available", who, what);
+        return gate_refuse(ERR_UNSUPPORTED, msg);
+    }
+    // the pack the factorised system was linearised from: this graph's, unchanged in its first inc_F entries
+    auto pit = g_packs.find(g);
+    if (pit == g_packs.end() || pit->second->slot != t_slot || pit->second->serial != c.fact_pack) {
+        snprintf(msg, sizeof msg, "%s: no retained factor of this graph (the param's last solver call was made with another graph, or the graph's "
+                                  "device copy has been dropped since)", who);
+        return gate_refuse(-1, msg);
+    }
+    GraphPack &gp = *pit->second;
+    // the pack is the graph's, shared by every param that solves it: lp, Delta and the weighted slots must be the ones THIS param's
+    // factorisation linearised, not what a later step, LM or GNC run or failed call of another param left there
+    if (gp.lin_ctx != (const void *)&c || gp.lin_serial != c.fact_serial || gp.lin_content != gp.content_version) {
+        snprintf(msg, sizeof msg, "%s: the graph's device copy no longer holds the linearisation of this param's retained factor (another "
+                                  "param's solver call on the graph, an april_graph_cholesky_inc_solver call, or a factor's z / W edited and evaluated since); "
+                                  "a batch call with this param makes %s available", who, what);
+        return gate_refuse(-1, msg);
+    }
+    const int N = c.plan.N, Fp = c.inc_F;
+    if (zsize(g->nodes) != N || gp.N != N) {
+        snprintf(msg, sizeof msg, "%s: the graph's node count differs from the factorised system's (nodes added since the last solver call?)", who);
+        return gate_refuse(ERR_BAD_GRAPH, msg);
+    }
+    bool same = Fp > 0 && Fp <= gp.F && Fp <= gp.F_on_device && (int)c.pat.size() == 2 * Fp && (int)gp.is_host.size() >= Fp;
+    if (same && !(c.pat_serial == gp.serial && c.pat_topo == gp.topo_version))
+        for (int f = 0; f < Fp && same; f++) same = c.pat[2 * f] == gp.h_fa.p[f] && c.pat[2 * f + 1] == gp.h_fb.p[f];
+    if (!same) {
+        snprintf(msg, sizeof msg, "%s: the graph's factors are no longer the ones the last solver call factorised (a factor's nodes or kind changed)", who);
+        return gate_refuse(-1, msg);
+    }
+    // graph factors wholly inside the factorised entries
+    Fg = (int)(std::upper_bound(gp.g2p.begin(), gp.g2p.begin() + std::min<size_t>(gp.g2p.size(), (size_t)gp.Fg + 1), Fp) - gp.g2p.begin()) - 1;
+    // (a caller that passes NULL sizes out by the graph it holds: never write more rows than that graph has factors)
+    if (zsize(g->factors) < Fg) {
+        snprintf(msg, sizeof msg, "%s: the graph holds fewer factors than the factorised system (factors removed since the last solver call?)", who);
+        return gate_refuse(ERR_BAD_GRAPH, msg);
+    }
+    gpp = &gp;
+    return 0;
+}
 static int audit_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *factors, double *out) {
     const char *who = "aprilsam_amd_factor_audit";
     if (!g || !param || !out || (factors && n < 0)) return gate_refuse(ERR_BAD_GRAPH, "aprilsam_amd_factor_audit: null argument or negative count");
     ensure_device();
     SlotLock lk(param, g);
-    Context *cp = nullptr;
-    if (int rc = ps_context(param, who, cp, g)) return rc;
-    Context &c = *cp;
-    if (c.fact_kind == FACT_EXTENDED)
-        return gate_refuse(ERR_UNSUPPORTED, "aprilsam_amd_factor_audit: the retained factor is an incremental step's extended structure: the device slots of a fast "
-                                            "incremental step are not a consistent picture of the factorised system (new robust and polar factors are weighted on the host, old "
-                                            "factors keep stale linearisations); a batch call that plans anew (april_graph_cholesky: the second in a row, or under option batch_extend = 0) "
-                                            "makes the audit available");
-    // the pack the factorised system was linearised from: this graph's, unchanged in its first inc_F entries
-    auto pit = g_packs.find(g);
-    if (pit == g_packs.end() || pit->second->slot != t_slot || pit->second->serial != c.fact_pack)
-        return gate_refuse(-1, "aprilsam_amd_factor_audit: no retained factor of this graph (the param's last solver call was made with another graph, or the graph's "
-                               "device copy has been dropped since)");
-    GraphPack &gp = *pit->second;
-    // the pack is the graph's, shared by every param that solves it: lp, Delta and the weighted slots must be the ones THIS param's
-    // factorisation linearised, not what a later step, LM or GNC run or failed call of another param left there
-    if (gp.lin_ctx != (const void *)&c || gp.lin_serial != c.fact_serial || gp.lin_content != gp.content_version)
-        return gate_refuse(-1, "aprilsam_amd_factor_audit: the graph's device copy no longer holds the linearisation of this param's retained factor (another "
-                               "param's solver call on the graph, an april_graph_cholesky_inc_solver call, or a factor's z / W edited and evaluated since); "
-                               "a batch call with this param makes the audit available");
-    const int N = c.plan.N, Fp = c.inc_F;
-    if (zsize(g->nodes) != N || gp.N != N)
-        return gate_refuse(ERR_BAD_GRAPH, "aprilsam_amd_factor_audit: the graph's node count differs from the factorised system's (nodes added since the last solver call?)");
-    bool same = Fp > 0 && Fp <= gp.F && Fp <= gp.F_on_device && (int)c.pat.size() == 2 * Fp && (int)gp.is_host.size() >= Fp;
-    if (same && !(c.pat_serial == gp.serial && c.pat_topo == gp.topo_version))
-        for (int f = 0; f < Fp && same; f++) same = c.pat[2 * f] == gp.h_fa.p[f] && c.pat[2 * f + 1] == gp.h_fb.p[f];
-    if (!same)
-        return gate_refuse(-1, "aprilsam_amd_factor_audit: the graph's factors are no longer the ones the last solver call factorised (a factor's nodes or kind changed)");
-    // graph factors wholly inside the factorised entries
-    const int Fg = (int)(std::upper_bound(gp.g2p.begin(), gp.g2p.begin() + std::min<size_t>(gp.g2p.size(), (size_t)gp.Fg + 1), Fp) - gp.g2p.begin()) - 1;
-    // (a caller that passes NULL sizes out by the graph it holds: never write more rows than that graph has factors)
-    if (zsize(g->factors) < Fg)
-        return gate_refuse(ERR_BAD_GRAPH, "aprilsam_amd_factor_audit: the graph holds fewer factors than the factorised system (factors removed since the last solver call?)");
+    Context *cp = nullptr; GraphPack *gpp = nullptr; int Fg = 0;
+    if (int rc = retained_linearisation(g, param, who, "the audit", cp, gpp, Fg)) return rc;
+    Context &c = *cp; GraphPack &gp = *gpp;
     if (!factors) n = Fg;
     for (int i = 0; factors && i < n; i++)
         if (factors[i] < 0 || factors[i] >= Fg)
@@ -51,7 +74,8 @@ static int audit_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int
     for (int i = 0; i < n; i++) {
         const int gi = factors ? factors[i] : i, p = gp.g2p[gi];
         // (host-evaluated: foreign types and cliques of more than two nodes have no slot, and user code is not called back)
-        const bool ok = gp.g2p[gi + 1] - p == 1 && !gp.is_host[p] && gp.h_fa.p[p] >= 0;
+        // (a dense Gaussian factor's slot holds no z / W either: DESIGN.md section 24)
+        const bool ok = gp.g2p[gi + 1] - p == 1 && !gp.is_host[p] && gp.h_fa.p[p] >= 0 && !(gi < (int)gp.gs_of.size() && gp.gs_of[gi] >= 0);
         list[i] = ok ? p : -1; qa[i] = ok ? gp.h_fa.p[p] : -1; qb[i] = ok ? gp.h_fb.p[p] : -1;
         off += ok ? 0 : 1;
     }

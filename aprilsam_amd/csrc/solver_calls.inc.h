@@ -51,8 +51,9 @@ static void batch_impl(april_graph_t *g, april_graph_cholesky_param_t *param) {
     bool hybrid = false, reused = false;
     {
         const int patF = (int)c.pat.size() / 2;
-        // (fixed nodes: the extended plan's step linearises on its own, without the mask -- such a graph is planned again)
-        bool ext = g_opt.batch_extend && !timing && c.have_plan && c.inc.ready && gp.host_idx.empty() && gp.n_asym == 0 && !c.wt_any && gp.n_fixed() == 0 && N >= c.patN && F >= patF &&
+        // (fixed nodes: the extended plan's step linearises on its own, without the mask -- such a graph is planned again; so is one with dense
+        // Gaussian factors, whose slots that step does not write)
+        bool ext = g_opt.batch_extend && !timing && c.have_plan && c.inc.ready && gp.host_idx.empty() && gp.n_asym == 0 && !c.wt_any && gp.n_fixed() == 0 && gp.n_gaussian() == 0 && N >= c.patN && F >= patF &&
                    c.inc_N == c.patN && c.inc_F == patF && c.plan.leaf_nodes == g_opt.leaf_nodes && c.plan_pin == g_opt.pin_last &&
                    c.plan_persist == launch_table_key();
         for (int i = 0; i < patF && ext; i++) ext = c.pat[2 * i] == gp.h_fa.p[i] && c.pat[2 * i + 1] == gp.h_fb.p[i];
@@ -284,6 +285,7 @@ static void inc_impl(april_graph_t *g, april_graph_cholesky_param_t *param) {
     }
     if (param->factor_num == zsize(g->factors)) return;                  // aprilsam.c:384-385
     if (inc_refuse_fixed("april_graph_cholesky_inc", g, param)) return;  // (-12 through aprilsam_amd_last_error, nothing written)
+    if (refuse_gaussian("april_graph_cholesky_inc", g)) return;          // (the same)
     ensure_device();
     Context &c = ctx_for(param);
     GraphPack &gp = pack_for(g);
@@ -521,6 +523,7 @@ void inc_solve_only(april_graph_t *g, april_graph_cholesky_param_t *param) {
         auto it = g_ctx.find(param);
         if (it == g_ctx.end() || !it->second->have_fact || !param->nreordering) return;        // aprilsam.c:580
         if (inc_refuse_fixed("april_graph_cholesky_inc_solver", g, param)) return;
+        if (refuse_gaussian("april_graph_cholesky_inc_solver", g)) return;
         ensure_device();
         Context &c = *it->second;
         GraphPack &gp = pack_for(g);
@@ -573,7 +576,7 @@ static double chi2_impl(april_graph_t *g) {
             last = gi;
             // (debug option polar_on_host: a polar factor's term is taken at the states, where the native path's k_chi2_polar takes it)
             int pk = 0;
-            const bool at_state = polar_of(fs[gi], &pk) && fs[gi]->state_eval;
+            const bool at_state = (polar_of(fs[gi], &pk) || gaussian_of(fs[gi], nullptr, nullptr, nullptr)) && fs[gi]->state_eval;      // (gaussian_on_host: the same)
             april_graph_factor_eval_t *e = at_state ? fs[gi]->state_eval(fs[gi], g, nullptr) : fs[gi]->eval ? fs[gi]->eval(fs[gi], g, nullptr) : nullptr;
             if (!e) fail(ERR_BAD_GRAPH, "factor %d: eval() returned no evaluation (aprilsam.h:75-89)", gi);      // (never takes the process down: errors.h)
             chi2 += e->chi2;

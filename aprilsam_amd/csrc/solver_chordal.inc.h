@@ -84,6 +84,7 @@ static int initialize_chordal_impl(april_graph_t *g, april_graph_cholesky_param_
         if (!gp.host_idx.empty()) { snprintf(msg, sizeof msg, "%s: the graph holds host-evaluated factors (foreign types): use april_graph_cholesky", who); return gate_refuse(-4, msg); }
         if (gp.n_asym > 0) { snprintf(msg, sizeof msg, "%s: a factor has an asymmetric information matrix", who); return gate_refuse(ERR_UNSUPPORTED, msg); }
         if (gp.n_polar() > 0) { snprintf(msg, sizeof msg, "%s: the graph holds polar factors, which carry no relative heading (DESIGN.md section 19)", who); return gate_refuse(ERR_UNSUPPORTED, msg); }
+        if (gp.n_gaussian() > 0) { snprintf(msg, sizeof msg, "%s: the graph holds dense Gaussian factors, which the two linear stages do not know (DESIGN.md section 24)", who); return gate_refuse(ERR_UNSUPPORTED, msg); }
     }
     SlotLock lk(param, g);
     Context &c = ctx_for(param);

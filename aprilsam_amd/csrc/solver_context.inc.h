@@ -853,6 +853,7 @@ static void rewind_epoch(Context &c, hipStream_t s, long long phases) {
 }
 
 static void enqueue_chi2_polar(GraphPack &gp, hipStream_t s);      // solver_launch.inc.h (launch_polar)
+static void enqueue_chi2_gaussian(GraphPack &gp, hipStream_t s);   // solver_launch.inc.h (launch_gaussian)
 static double device_chi2(GraphPack &gp) {     // chi^2 at d_state; synchronises the stream
     hipStream_t s = gp.stream;
     if (gp.F == 0) return 0;
@@ -860,6 +861,7 @@ static double device_chi2(GraphPack &gp) {     // chi^2 at d_state; synchronises
     enqueue_chi2_mixture(gp, s);       // (max factors: their terms selected at the states, in place -- the sums below keep their order)
     enqueue_chi2_robust(gp, s);        // (robust factors: rho(s) in place of s)
     enqueue_chi2_polar(gp, s);         // (polar factors: r_p' Wp r_p in place of the slot's term)
+    enqueue_chi2_gaussian(gp, s);      // (dense Gaussian factors: c0 - 2 eta' delta + delta' Lambda delta on the factor's first entry)
     if (gp.F > REDUCE_SPLIT) {         // (the parts live behind the F_cap per-factor terms: upload_factors)
         double *parts = gp.d_chi2f.p + gp.F_cap;
         hipLaunchKernelGGL(k_reduce_parts, dim3(REDUCE_PARTS), dim3(TPB), 0, s, gp.F, gp.d_chi2f.p, parts);

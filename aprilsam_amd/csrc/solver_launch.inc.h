@@ -200,6 +200,21 @@ static void enqueue_polar(GraphPack &gp, hipStream_t s) { launch_polar(s, gp, k_
 // ... and every chi^2 is followed by their true terms at the states, in place of what k_chi2 made of the slot
 static void enqueue_chi2_polar(GraphPack &gp, hipStream_t s) { launch_polar(s, gp, k_chi2_polar, (const double *)gp.d_state.p, gp.d_chi2f.p); }
 
+// The kernels of gaussian.hip.h run one wave per dense Gaussian factor of the pack; `a` is what follows the table in
+// the kernel's arguments.  None for a pack without such factors
+template <class K, class... Args> static void launch_gaussian(hipStream_t s, GraphPack &gp, K kern, const Args &...a) {
+    const int G = gp.n_gaussian();
+    if (G == 0) return;
+    hipLaunchKernelGGL(kern, dim3(G), dim3(64), 0, s, gp.gauss_tab(), a...);
+}
+// every linearisation of a pack with Gaussian factors is FOLLOWED by their blocks and rhs segments at the l_points, in place of the zero
+// contributions k_linearize_t made of their null slots -- and before the fixed-node mask
+static void enqueue_gaussian(Context &c, GraphPack &gp, hipStream_t s) {
+    launch_gaussian(s, gp, k_gaussian_slot, (const double *)gp.d_lp.p, (const unsigned char *)c.d_swap.p, c.dp.slot_blk, c.dp.slot_rhs, c.d_H.p);
+}
+// ... and every chi^2 by their terms at the states, on each factor's first entry
+static void enqueue_chi2_gaussian(GraphPack &gp, hipStream_t s) { launch_gaussian(s, gp, k_chi2_gaussian, (const double *)gp.d_state.p, gp.d_chi2f.p); }
+
 // The kernels of polargate.hip.h, behind the path solves of a gating call: k_gate_polar runs one thread per candidate
 // (per_item = false: `work` candidates), k_associate_polar one workgroup per observation (per_item = true: `work` observations); `a` are the
 // kernel's arguments.  Nothing to gate: no launch
@@ -242,7 +257,8 @@ static void enqueue_linearise(Context &c, GraphPack &gp, hipStream_t s, bool una
         hipLaunchKernelGGL(k_scatter_host, dim3((nh + TPB - 1) / TPB), dim3(TPB), 0, s, nh, gp.d_host_idx.p, gp.d_hostH.p, gp.d_fb.p, c.d_swap.p,
                            c.dp.slot_blk, c.dp.slot_rhs, c.d_H.p);
     }
-    launch_fixed(s, c, gp);                          // fixed nodes: their slots zeroed, their diagonal 1.0 -- last, after everything that writes a slot
+    enqueue_gaussian(c, gp, s);                      // dense Gaussian factors: Lambda's blocks and eta - Lambda delta into the slots of their entries
+    launch_fixed(s, c, gp);                         // fixed nodes: their slots zeroed, their diagonal 1.0 -- last, after everything that writes a slot
 }
 
 // what a caller of the numeric phase asks for beyond the plain step; everything is off unless named

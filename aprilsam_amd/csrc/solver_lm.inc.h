@@ -44,6 +44,7 @@ static void lm_enqueue_cost(Context &c, GraphPack &gp, hipStream_t s, const doub
     if (gp.gc_n > 0)     // (candidates of an aprilsam_amd_optimize_gnc run: rho_mu(r^T W0 r), solver_gnc.inc.h)
         launch_gnc(s, gp, k_gnc_cost, (const int *)gp.d_fa.p, (const int *)gp.d_fb.p, (const double *)gp.d_z.p, st, terms);
     launch_polar(s, gp, k_lm_cost_polar, st, terms);      // (polar factors: r_p' Wp r_p in place of the slot's term)
+    launch_gaussian(s, gp, k_chi2_gaussian, st, terms);   // (dense Gaussian factors: the full term at st on the factor's first entry)
     lm_reduce(s, F, terms, terms + T, out);
 }
 static void lm_enqueue_commit(Context &c, GraphPack &gp, hipStream_t s) {
@@ -61,6 +62,7 @@ static void lm_enqueue_iteration(Context &c, GraphPack &gp, hipStream_t s) {
     lm_enqueue_cost(c, gp, s, c.d_lm_trial.p, &S->Ft);
     hipLaunchKernelGGL(k_lm_model, dim3((F + TPB - 1) / TPB), dim3(TPB), 0, s, F, gp.d_fa.p, gp.d_fb.p, gp.d_z.p, gp.d_W.p, (const double *)gp.d_lp.p,
                        (const double *)gp.d_dx.p, terms);
+    launch_gaussian(s, gp, k_lm_model_gaussian, (const double *)gp.d_lp.p, (const double *)gp.d_dx.p, terms);      // (their slots are null: h' (2 g - Lambda h) from the table)
     lm_reduce(s, F, terms, parts, &S->pred);
     hipLaunchKernelGGL(k_lm_norms, dim3((N + TPB - 1) / TPB), dim3(TPB), 0, s, N, (const double *)gp.d_dx.p, (const double *)gp.d_state.p, terms, terms + N);
     lm_reduce(s, N, terms, parts, &S->hh);

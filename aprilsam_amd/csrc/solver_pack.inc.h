@@ -30,7 +30,7 @@ static void park_stream(int slot, hipStream_t s) {
     } else (void)hipGetLastError();
     (void)hipStreamDestroy(s);
 }
-// The device table of one factor family (max-mixture, robust, polar): columns of ints or doubles, one row per factor of the family, kept on
+// The device table of one factor family (max-mixture, robust, polar, dense Gaussian): columns of ints or doubles, one row per factor of the family, kept on
 // the device append-only.  The host vectors and device buffers belong to the GraphPack, by name (kernels and the select_new_* rules read
 // them); the table knows how they go up.  `gen` changes whenever the table's size or device addresses do: captured graphs are keyed by
 // it (GraphPack::capture_key).
@@ -178,6 +178,16 @@ struct GraphPack {
     SideTable pl{ pl_f, nullptr, { { pl_z, d_pl_z, 2 }, { pl_W, d_pl_W, 4 }, { pl_f, d_pl_f }, { pl_kind, d_pl_kind } } };
     int n_polar() const { return (int)pl_f.size(); }
     void pl_clear() { pl.clear(); pl_of.clear(); }
+    // dense Gaussian factors (gaussian.hip.h): per Gaussian factor q its FIRST packed entry gs_f[q] (the entries of the
+    // clique of its node pairs follow), its node count gs_k[q] and, in fixed-width rows padded to GS_MAX nodes, the node ids gs_node[11q],
+    // xbar gs_xbar[33q], eta gs_eta[33q], Lambda gs_L[1089q] (3k x 3k, row stride 3k) and the chi^2 constant gs_c0[q].  The entries' slots
+    // of h_z / h_W hold null factors for good.  gs_of: per graph factor its q or -1
+    std::vector<int> gs_f, gs_k, gs_node, gs_of; std::vector<double> gs_xbar, gs_eta, gs_L, gs_c0;
+    DBuf<int> d_gs_f, d_gs_k, d_gs_node; DBuf<double> d_gs_xbar, d_gs_eta, d_gs_L, d_gs_c0;
+    SideTable gs{ gs_f, nullptr, { { gs_xbar, d_gs_xbar, GS_ROWS }, { gs_eta, d_gs_eta, GS_ROWS }, { gs_L, d_gs_L, GS_LSZ }, { gs_c0, d_gs_c0 }, { gs_f, d_gs_f }, { gs_k, d_gs_k }, { gs_node, d_gs_node, GS_MAX } } };
+    int n_gaussian() const { return (int)gs_f.size(); }
+    void gs_clear() { gs.clear(); gs_of.clear(); }
+    GaussTab gauss_tab() const { return GaussTab{ n_gaussian(), d_gs_f.p, d_gs_k.p, d_gs_node.p, d_gs_xbar.p, d_gs_eta.p, d_gs_L.p, d_gs_c0.p }; }
     // fixed nodes (fixed.hip.h): fx_nodes: the ids of the nodes held constant, ascending, as the last call's walk over
     // the node objects found them (sync_fixed); fx_rec: one record per packed entry with a fixed endpoint (.x the entry, .y the FX_* bits of
     // the slots k_fix_mask zeroes), built from the PACKED entries -- the pairs of a host-evaluated clique included -- at fx_topo =
@@ -189,7 +199,7 @@ struct GraphPack {
     // What every captured graph reads of the pack: the device arrays (d_state stands for all that grow with the nodes), this pack and no
     // other at the same addresses, and every side table where it lay at the capture.  Each generation only grows, so their sum changes
     // exactly when one of them does: a new table-keeping family adds its generation to this sum and is keyed everywhere
-    CaptureKey capture_key(std::array<size_t, 6> extra = {}) const { return CaptureKey{ d_state.p, serial, mx.gen + rb.gen + pl.gen + fx_gen, extra }; }
+    CaptureKey capture_key(std::array<size_t, 6> extra = {}) const { return CaptureKey{ d_state.p, serial, mx.gen + rb.gen + pl.gen + gs.gen + fx_gen, extra }; }
     // GNC candidates (gnc.hip.h): a table that exists on the device for the length of ONE aprilsam_amd_optimize_gnc
     // call -- gc_n > 0 only inside it.  d_gc_f / d_gc_W0 / d_gc_w: packed entry, plain W and last weight per candidate, d_gc_par: loss, c
     // and mu; d_gc_out / gc_stage: results and their pinned staging.  gc_gen changes with every run: captured LM iterations are keyed by it
@@ -209,6 +219,7 @@ struct GraphPack {
         mx.release(); mx_clear();
         rb.release(); rb_clear();
         pl.release(); pl_clear();
+        gs.release(); gs_clear();
         d_fx_nodes.release(); d_fx_rec.release(); fx_nodes.clear(); fx_rec.clear(); fx_topo = -1; fx_dirty = false;
         d_gc_f.release(); d_gc_W0.release(); d_gc_w.release(); d_gc_out.release(); d_gc_par.release(); gc_stage.release(); gc_n = 0;
         if (stream) { forget_stream(stream); park_stream(slot, stream); }
@@ -283,13 +294,13 @@ static void pack_factors(GraphPack &gp, const april_graph_t *g, bool validate_ol
     // (incremental calls only ever look at the factors added since the previous call, aprilsam.c:508-511: first and last packed pointer
     // as a sanity check instead of all of them -- the comparison of 5 000 pointers was a microsecond of every step)
     if (valid && trust) valid = from == 0 || (validate_old ? memcmp(gp.fptr.data(), fs, sizeof(void *) * from) == 0 : (gp.fptr[0] == fs[0] && gp.fptr[from - 1] == fs[from - 1]));
-    auto restart = [&]() { gp.topo_version++; from = 0; gp.F = 0; gp.F_on_device = 0; gp.host_idx.clear(); gp.host_evaluated = 0; gp.is_host.clear(); gp.p2g.clear(); gp.vslot.clear(); gp.g2p.assign(1, 0); gp.asym.clear(); gp.n_asym = 0; gp.mx_clear(); gp.rb_clear(); gp.pl_clear(); };
+    auto restart = [&]() { gp.topo_version++; from = 0; gp.F = 0; gp.F_on_device = 0; gp.host_idx.clear(); gp.host_evaluated = 0; gp.is_host.clear(); gp.p2g.clear(); gp.vslot.clear(); gp.g2p.assign(1, 0); gp.asym.clear(); gp.n_asym = 0; gp.mx_clear(); gp.rb_clear(); gp.pl_clear(); gp.gs_clear(); };
     if (!valid) restart();
     // one graph factor -> its packed entries (a, b, host flag, node slots of a host pair, what the pair carries)
     struct Ent { int a, b; bool host; unsigned short slots; unsigned char carry; };
-    Ent ents[64]; int ne = 0; bool is_max = false, is_rb = false, is_pl = false; int rb_kind = 0, pl_kind = 0; double rb_c = 0;
+    Ent ents[64]; int ne = 0; bool is_max = false, is_rb = false, is_pl = false, is_gs = false; int rb_kind = 0, pl_kind = 0, gs_k = 0; double rb_c = 0, gs_c0 = 0;
     auto classify = [&](const april_graph_factor_t *f, int i) {
-        ne = 0; is_max = false; is_rb = false; is_pl = false;
+        ne = 0; is_max = false; is_rb = false; is_pl = false; is_gs = false;
         if (is_native_max(f)) {        // (before anything reads u.common: u.max aliases it)
             char why[192];
             if (f->nnodes != 2 || !max_check(f, why, sizeof why)) fail(ERR_UNSUPPORTED, "factor %d: max factor: %s", i, f->nnodes != 2 ? "not binary" : why);
@@ -302,6 +313,20 @@ static void pack_factors(GraphPack &gp, const april_graph_t *g, bool validate_ol
             for (int k = 0; k < m && ok; k++) ok = std::isfinite(f->u.common.z[k]);     // (the constructor checked both; the caller may have edited them since)
             if (!ok) fail(ERR_UNSUPPORTED, "factor %d: a polar factor's z must be finite and its W finite, symmetric and positive definite (DESIGN.md section 19)", i);
             ents[ne++] = Ent{ f->nodes[0], f->nodes[1], false, 0, 3 }; is_pl = true;
+        }
+        else if (bool gs_ok = false; !g_opt.gaussian_on_host && gaussian_ever() && gaussian_of(f, &gs_k, &gs_c0, &gs_ok)) {      // this library's dense Gaussian factor
+            bool ok = gs_ok && gs_k >= 1 && gs_k <= GS_MAX;
+            for (int r = 0; r < 3 * gs_k && ok; r++) ok = std::isfinite(f->u.common.z[r]);      // (the constructor checked all of it; the caller may have edited xbar, eta or Lambda since)
+            if (!ok) fail(ERR_UNSUPPORTED, "factor %d: a Gaussian factor's xbar and eta must be finite and its Lambda finite, symmetric and positive semi-definite (DESIGN.md section 24)", i);
+            // the clique of its node pairs in the host clique's order, slots and carry bits -- device entries: their slots of z / W are null
+            // factors, k_gaussian_slot writes their contributions
+            if (gs_k == 1) ents[ne++] = Ent{ f->nodes[0], -1, false, 0xff, 3 };
+            for (int x = 0; x < gs_k; x++)
+                for (int y = x + 1; y < gs_k; y++) {
+                    const unsigned char carry = (unsigned char)(((x == 0 && y == 1) ? 1 : 0) | ((x == 0) ? 2 : 0));
+                    ents[ne++] = Ent{ f->nodes[x], f->nodes[y], false, (unsigned short)((x << 8) | y), carry };
+                }
+            is_gs = true;
         }
         else if ((f->nnodes == 1 || f->nnodes == 2) && f->eval)       // any other type: the factor's own eval(), on the host
             ents[ne++] = Ent{ f->nodes[0], f->nnodes == 2 ? f->nodes[1] : -1, true, (unsigned short)(f->nnodes == 2 ? 1 : 0xff), 3 };
@@ -341,9 +366,21 @@ static void pack_factors(GraphPack &gp, const april_graph_t *g, bool validate_ol
             if (!changed) changed = is_max != (gp.mx_of[i] >= 0) || (is_max && gp.mx_k[gp.mx_of[i] + 1] - gp.mx_k[gp.mx_of[i]] != f->u.max.nfactors);
             if (!changed) changed = is_rb != (i < (int)gp.rb_of.size() && gp.rb_of[i] >= 0);      // (a loss gained or lost: the table is packed again)
             if (!changed) changed = is_pl != (i < (int)gp.pl_of.size() && gp.pl_of[i] >= 0) || (is_pl && gp.pl_kind[gp.pl_of[i]] != pl_kind);
+            if (!changed) changed = is_gs != (i < (int)gp.gs_of.size() && gp.gs_of[i] >= 0) || (is_gs && gp.gs_k[gp.gs_of[i]] != gs_k);
             if (changed) break;
             gp.fptr[i] = f;
             if (ents[0].host) continue;
+            if (is_gs) {               // the slots hold null factors: the object against the table
+                const int q = gp.gs_of[i], n = 3 * gs_k;
+                double *tx = gp.gs_xbar.data() + (size_t)GS_ROWS * q, *te = gp.gs_eta.data() + (size_t)GS_ROWS * q, *tL = gp.gs_L.data() + (size_t)GS_LSZ * q;
+                if (memcmp(tx, f->u.common.z, (size_t)8 * n) != 0 || memcmp(te, f->u.common.z + n, (size_t)8 * n) != 0 ||
+                    memcmp(tL, f->u.common.W->data, (size_t)8 * n * n) != 0) {
+                    memcpy(tx, f->u.common.z, (size_t)8 * n); memcpy(te, f->u.common.z + n, (size_t)8 * n); memcpy(tL, f->u.common.W->data, (size_t)8 * n * n);
+                    gp.gs_c0[q] = gs_c0;
+                    gp.gs.dirty = true; lo = std::min(lo, p0); hi = std::max(hi, p0 + 1);
+                }
+                continue;
+            }
             if (is_max) {              // the components against the table: an edited one is copied and the table uploaded again
                 const int m = gp.mx_of[i];
                 bool edit = false;
@@ -392,7 +429,7 @@ static void pack_factors(GraphPack &gp, const april_graph_t *g, bool validate_ol
             gp.content_version++;
         }
     }
-    gp.fptr.resize(Fg); gp.g2p.resize((size_t)Fg + 1); gp.mx_of.resize(Fg, -1); gp.rb_of.resize(Fg, -1); gp.pl_of.resize(Fg, -1);
+    gp.fptr.resize(Fg); gp.g2p.resize((size_t)Fg + 1); gp.mx_of.resize(Fg, -1); gp.rb_of.resize(Fg, -1); gp.pl_of.resize(Fg, -1); gp.gs_of.resize(Fg, -1);
     int F = gp.g2p[from];
     {   // the pinned mirrors are sized ONCE for everything this call appends (a pinned reallocation costs a quarter of a millisecond)
         size_t total = (size_t)F;
@@ -417,6 +454,18 @@ static void pack_factors(GraphPack &gp, const april_graph_t *g, bool validate_ol
                 memset(gp.h_z.p + (size_t)3 * F, 0, 24); memset(gp.h_W.p + (size_t)9 * F, 0, 72);
                 gp.note_asym(F, gp.h_W.p + (size_t)9 * F, false);
                 gp.host_idx.push_back(F);
+            } else if (is_gs) {        // every entry of the clique holds a null factor (symmetric) for good; the factor's row goes in with its first entry
+                memset(gp.h_z.p + (size_t)3 * F, 0, 24); memset(gp.h_W.p + (size_t)9 * F, 0, 72);
+                gp.note_asym(F, gp.h_W.p + (size_t)9 * F, true);
+                if (e > 0) continue;
+                const int n = 3 * gs_k;
+                gp.gs_of[i] = gp.n_gaussian(); gp.gs_f.push_back(F); gp.gs_k.push_back(gs_k); gp.gs_c0.push_back(gs_c0);
+                const size_t q = gp.gs_k.size() - 1;
+                gp.gs_node.resize((q + 1) * GS_MAX, 0); gp.gs_xbar.resize((q + 1) * GS_ROWS, 0.0); gp.gs_eta.resize((q + 1) * GS_ROWS, 0.0); gp.gs_L.resize((q + 1) * GS_LSZ, 0.0);
+                memcpy(&gp.gs_node[q * GS_MAX], f->nodes, (size_t)4 * gs_k);
+                memcpy(&gp.gs_xbar[q * GS_ROWS], f->u.common.z, (size_t)8 * n); memcpy(&gp.gs_eta[q * GS_ROWS], f->u.common.z + n, (size_t)8 * n);
+                memcpy(&gp.gs_L[q * GS_LSZ], f->u.common.W->data, (size_t)8 * n * n);
+                gp.gs.gen++;
             } else if (is_max) {       // the slot holds component 0 until a selection writes it (k_select_mixture, select_new_max)
                 const april_graph_factor_t *c0 = f->u.max.factors[0];
                 memcpy(gp.h_z.p + (size_t)3 * F, c0->u.common.z, 24);
@@ -543,6 +592,21 @@ static int refuse_fixed(const char *who, const april_graph_t *g) {
     fprintf(stderr, "aprilsam_amd: ERROR %d: %s\n", (int)ERR_UNSUPPORTED, msg); fflush(stderr);
     return ERR_UNSUPPORTED;
 }
+// The entry points that do not take dense Gaussian factors: 0, or -12 with a message that names the first one.
+// Nothing was read or written before; the param keeps its plan and factor.  A process that never made such a factor does not walk
+static int refuse_gaussian(const char *who, const april_graph_t *g) {
+    if (!g || !gaussian_ever() || g_opt.gaussian_on_host) return 0;
+    april_graph_factor_t **fs = (april_graph_factor_t **)g->factors->data;
+    for (int i = 0, Fg = zsize(g->factors); i < Fg; i++) {
+        if (fs[i]->type != APRILSAM_AMD_FACTOR_GAUSSIAN_TYPE || !gaussian_of(fs[i], nullptr, nullptr, nullptr)) continue;
+        char msg[320];
+        snprintf(msg, sizeof msg, "%s: factor %d is a dense Gaussian factor (aprilsam_amd_factor_gaussian_create); this entry point does not take them (DESIGN.md section 24)", who, i);
+        set_last_error(ERR_UNSUPPORTED, msg);
+        fprintf(stderr, "aprilsam_amd: ERROR %d: %s\n", (int)ERR_UNSUPPORTED, msg); fflush(stderr);
+        return ERR_UNSUPPORTED;
+    }
+    return 0;
+}
 // the content check of the nodes' flags, once per call that linearises: a node fixed or freed since the last call is seen here
 static void sync_fixed(GraphPack &gp, const april_graph_t *g) {
     if (gp.fx_nodes.empty() && !fixed_ever()) return;
@@ -574,7 +638,7 @@ static void upload_fixed(GraphPack &gp) {
     gp.fx_dirty = false; gp.fx_topo = gp.topo_version;
 }
 // the families' tables -> device (SideTable::upload): rows appended or edited since the last call, for the kernels of the step that follows
-static void upload_tables(GraphPack &gp) { gp.mx.upload(gp.stream); gp.rb.upload(gp.stream); gp.pl.upload(gp.stream); }
+static void upload_tables(GraphPack &gp) { gp.mx.upload(gp.stream); gp.rb.upload(gp.stream); gp.pl.upload(gp.stream); gp.gs.upload(gp.stream); }
 static void upload_factors(GraphPack &gp) {
     const int F = gp.F;
     if (F > gp.F_cap) {           // reallocation loses the old content: re-upload everything

@@ -282,7 +282,8 @@ static int debug_stage_impl(april_graph_t *g, april_graph_cholesky_param_t *para
     enqueue_polar(gp, s);
     hipLaunchKernelGGL((k_linearize_t<false>), dim3((F + TPB - 1) / TPB), dim3(TPB), 0, s, 0, F, (const int *)nullptr, gp.d_fa.p, gp.d_fb.p, gp.d_z.p, gp.d_W.p,
                        gp.d_lp.p, gp.d_state.p, c.d_swap.p, c.dp.slot_blk, c.dp.slot_rhs, c.d_H.p, c.d_bad.p, (const double *)nullptr);
-    if (gp.n_fixed() > 0) {                       // (the mask writes d_lambda as every step's does: whatever runs next on this param rewrites it)
+    enqueue_gaussian(c, gp, s);
+    if (gp.n_fixed() > 0) {                      // (the mask writes d_lambda as every step's does: whatever runs next on this param rewrites it)
         set_lambda(c, gp, param->tikhanov);
         launch_fixed(s, c, gp);
         c.lambda_N = -1;

@@ -200,6 +200,7 @@ static int shard_begin_impl(april_graph_t *g, april_graph_cholesky_param_t *para
     if (gp.n_max() > 0) fail(ERR_UNSUPPORTED, "aprilsam_amd_shard_begin: max-mixture factors are not supported by sharded runs (DESIGN.md section 12)");
     if (gp.n_robust() > 0) fail(ERR_UNSUPPORTED, "aprilsam_amd_shard_begin: robust factors are not supported by sharded runs (DESIGN.md section 15)");
     if (gp.n_polar() > 0) fail(ERR_UNSUPPORTED, "aprilsam_amd_shard_begin: polar factors are not supported by sharded runs (DESIGN.md section 19)");
+    if (gp.n_gaussian() > 0) fail(ERR_UNSUPPORTED, "aprilsam_amd_shard_begin: dense Gaussian factors are not supported by sharded runs (DESIGN.md section 24)");
     pack_states(gp, g, false);
     c.have_plan = false;                      // the pool layout is per rank: never reuse an upload made for another layout
     orient_asymmetric(c, gp);

@@ -199,6 +199,16 @@ class SolverLib:
                 d.aprilsam_amd_factor_polar_create.argtypes = [C.c_int, C.c_int, C.c_int, _dp, _dp]
                 d.aprilsam_amd_factor_get_polar.argtypes = [C.POINTER(abi.Factor), C.POINTER(C.c_int)]
                 d.aprilsam_amd_debug_polar_slot.argtypes = [C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]
+            if hasattr(d, "aprilsam_amd_factor_gaussian_create"):
+                d.aprilsam_amd_factor_gaussian_create.restype = C.POINTER(abi.Factor)
+                d.aprilsam_amd_factor_gaussian_create.argtypes = [C.c_int, _ip, _dp, _dp, _dp]
+                d.aprilsam_amd_factor_get_gaussian.argtypes = [C.POINTER(abi.Factor), C.POINTER(C.c_int)]
+            if hasattr(d, "aprilsam_amd_graph_remove_nodes"):
+                d.aprilsam_amd_graph_remove_nodes.argtypes = [C.POINTER(abi.Graph), C.c_int, _ip, _ip]
+            if hasattr(d, "aprilsam_amd_marginal_prior"):         # (defined in the HIP translation unit)
+                d.aprilsam_amd_marginal_prior.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.c_int, _ip, C.c_int, C.POINTER(C.c_int), _ip,
+                                                          _dp, _dp, _dp]
+                d.aprilsam_amd_graph_marginalize.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.c_int, _ip, _ip]
             if hasattr(d, "aprilsam_amd_debug_polar_gate"):
                 d.aprilsam_amd_debug_polar_gate.argtypes = [C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]
             if hasattr(d, "aprilsam_amd_gate_polar"):             # (defined in the HIP translation unit)
@@ -475,6 +485,74 @@ class Graph:
         k = C.c_int(-1)
         self.lib.dll.aprilsam_amd_factor_get_polar(self.factor_ptr(i), C.byref(k))
         return k.value
+
+    def make_factor_gaussian(self, nodes, xbar, eta, Lambda):
+        """a dense Gaussian factor on the k listed nodes in information form (include/aprilsam_amd.h: aprilsam_amd_factor_gaussian_create;
+        DESIGN.md section 24), NOT added to the graph: xbar [k, 3], eta [3k], Lambda [3k, 3k].  Raises ValueError (message of the library)
+        when refused."""
+        nn = np.ascontiguousarray(nodes, dtype=np.int32).ravel()
+        k = len(nn)
+        xb = np.ascontiguousarray(xbar, float).ravel(); et = np.ascontiguousarray(eta, float).ravel(); L = np.ascontiguousarray(Lambda, float).ravel()
+        if len(xb) != 3 * k or len(et) != 3 * k or len(L) != 9 * k * k:
+            raise ValueError(f"{k} nodes take xbar and eta of {3 * k} entries and a {3 * k} x {3 * k} Lambda")
+        f = self.lib.dll.aprilsam_amd_factor_gaussian_create(k, _np_i(nn), _np_d(xb), _np_d(et), _np_d(L))
+        if not f:
+            code, msg = self.lib.last_error()
+            raise ValueError(f"aprilsam_amd_factor_gaussian_create refused its arguments ({code}): {msg}")
+        return f
+
+    def add_factor_gaussian(self, nodes, xbar, eta, Lambda):
+        """append a dense Gaussian factor (make_factor_gaussian); returns its factor index"""
+        self.lib._add_factor(self.ptr, self.make_factor_gaussian(nodes, xbar, eta, Lambda))
+        return self.n_factors - 1
+
+    def get_gaussian(self, i):
+        """node count of factor i when it is a dense Gaussian factor of this library, 0 for any other factor"""
+        k = C.c_int(-1)
+        self.lib.dll.aprilsam_amd_factor_get_gaussian(self.factor_ptr(i), C.byref(k))
+        return k.value
+
+    def marginal_prior(self, param, remove, cap=None):
+        """(keep [nb], xbar [nb, 3], eta [3 nb], Lambda [3 nb, 3 nb]): the dense Gaussian that eliminating the nodes `remove` leaves on their
+        Markov blanket, from the linearisation of the param's last factorisation (include/aprilsam_amd.h: aprilsam_amd_marginal_prior).
+        cap: room for blanket nodes (abi.MARGINAL_MAX_NODES by default).  Raises RuntimeError on a refusal (the code is its first argument)."""
+        rm = np.ascontiguousarray(remove, dtype=np.int32).ravel()
+        cap = abi.MARGINAL_MAX_NODES if cap is None else int(cap)
+        nk = C.c_int(-1)
+        keep = np.full(max(cap, 1), -1, np.int32); xbar = np.full(3 * max(cap, 1), np.nan); eta = np.full(3 * max(cap, 1), np.nan)
+        L = np.full(9 * max(cap, 1) ** 2, np.nan)
+        rc = self.lib.dll.aprilsam_amd_marginal_prior(self.ptr, param.ptr if param is not None else None, len(rm), _np_i(rm), cap, C.byref(nk), _np_i(keep),
+                                                      _np_d(xbar), _np_d(eta), _np_d(L))
+        if rc != 0:
+            raise RuntimeError(rc, f"aprilsam_amd_marginal_prior failed rc={rc}: {self.lib.last_error()}")
+        nb = nk.value
+        return keep[:nb].copy(), xbar[:3 * nb].reshape(nb, 3).copy(), eta[:3 * nb].copy(), L[:9 * nb * nb].reshape(3 * nb, 3 * nb).copy()
+
+    def remove_nodes(self, remove):
+        """destroy the listed nodes and every factor that names one, close the gaps, renumber (include/aprilsam_amd.h:
+        aprilsam_amd_graph_remove_nodes; host only).  Returns new_index [old N]: the new id of every old node, -1 for a removed one.
+        Raises ValueError when refused (the graph is untouched then)."""
+        rm = np.ascontiguousarray(remove, dtype=np.int32).ravel()
+        n_before = self.n_nodes
+        idx = np.full(max(n_before, 1), -2, np.int32)
+        rc = self.lib.dll.aprilsam_amd_graph_remove_nodes(self.ptr, len(rm), _np_i(rm), _np_i(idx))
+        if rc != 0:
+            raise ValueError(f"aprilsam_amd_graph_remove_nodes refused its arguments ({rc}): {self.lib.last_error()[1]}")
+        return idx[:n_before]
+
+    def marginalize(self, param, remove):
+        """take the listed nodes out of the graph and leave their marginal prior on the blanket as a dense Gaussian factor
+        (include/aprilsam_amd.h: aprilsam_amd_graph_marginalize).  Returns (factor index or None when the blanket is empty, new_index).
+        Raises RuntimeError on a refusal (the code is its first argument; the graph is untouched then)."""
+        rm = np.ascontiguousarray(remove, dtype=np.int32).ravel()
+        n_before = self.n_nodes
+        idx = np.full(max(n_before, 1), -2, np.int32)
+        rc = self.lib.dll.aprilsam_amd_graph_marginalize(self.ptr, param.ptr if param is not None else None, len(rm), _np_i(rm), _np_i(idx))
+        if rc < 0:
+            raise RuntimeError(rc, f"aprilsam_amd_graph_marginalize failed rc={rc}: {self.lib.last_error()}")
+        # (0 is "no factor" or index 0: the prior, when there is one, is the graph's last factor)
+        has_factor = len(rm) > 0 and self.n_factors > 0 and rc == self.n_factors - 1 and self.get_gaussian(rc) > 0
+        return (rc if has_factor else None), idx[:n_before]
 
     def add_factor_xytpos(self, a, z, W):
         zz = (C.c_double * 3)(*z)

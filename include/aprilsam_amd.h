@@ -703,6 +703,75 @@ int aprilsam_amd_factor_get_polar(const april_graph_factor_t *factor, int *kind)
  * share.  0, or -13 on a bad argument */
 int aprilsam_amd_debug_polar_slot(int kind, const double *pa, const double *pb, const double *z, const double *W, double *z_eff3, double *W_eff9);
 
+/* ---- dense Gaussian factor on k nodes, information form -----------------------------------------------------------
+ * What is left on the Markov blanket of poses that were eliminated from a graph: a dense Gaussian, usually rank-deficient (a relative
+ * constraint among the blanket nodes, no absolute information).  With delta = x (-) xbar the per-node difference (3 k entries, the heading
+ * components wrapped with mod2pi), the factor contributes
+ *     H = Lambda          g = eta - Lambda delta                     to the normal equations A dx = g
+ * with delta taken at the nodes' l_points when linearising, and the term
+ *     c0 - 2 eta' delta + delta' Lambda delta                        to chi^2 and to the LM objective
+ * with delta taken at the states.  c0 = d'd, where R'R = Lambda and R'd = eta (below): the smallest constant that keeps the term >= 0
+ * (the kernel's rounding is cut off at 0).
+ * Lambda (3 k x 3 k, row-major) must be finite, symmetric (mirror entries bitwise equal) and positive SEMI-definite -- singular is the
+ * normal case; xbar and eta finite; the node ids distinct; 1 <= k <= APRILSAM_AMD_GAUSSIAN_MAX_NODES.
+ * The object is a valid reference factor: nnodes = k, u.common.z holds xbar (3 k) followed by eta (3 k), u.common.W is Lambda as a
+ * 3 k x 3 k matd, copy is deep.  At creation a diagonally pivoted Cholesky of Lambda (LAPACK dpstrf's default stop: the largest
+ * remaining diagonal <= 3 k eps max diag Lambda; a remaining diagonal below minus that bound refuses the matrix) gives R (rank x 3 k)
+ * with R'R = Lambda and, by a triangular solve in pivot order, d with R'd = eta in the least-squares sense.  length = rank;
+ * eval / state_eval return length = rank, J = R split per node, W = I, r = d - R delta and chi2 = r'r at l_point / state.  z and W may
+ * be edited in place: every evaluation and every solver call compares them with what R was made from and factorises again on a change
+ * (a W that is no longer admissible fails that solver call with -12).
+ * The solver keeps the factor as the clique of its k (k - 1) / 2 node pairs (one entry for k <= 2), so ordering, symbolic analysis and
+ * factorisation do not know it; a kernel (one wave per factor) writes Lambda's blocks and g into the pairs' contribution slots after the
+ * linearisation kernel and before the fixed-node mask.
+ * Open: april_graph_cholesky, aprilsam_amd_batch_resident and the resident loop, LM, GNC (as a non-candidate), aprilsam_amd_debug_stage,
+ * aprilsam_amd_solve, marginals, joint covariances, both gating calls, fixed nodes, april_graph_chi2 / aprilsam_amd_resident_chi2.
+ * Refused with -12, nothing written: april_graph_cholesky_inc and april_graph_cholesky_inc_solver on a graph that holds such a factor,
+ * aprilsam_amd_initialize_chordal, sharded params, a robust loss on it, its use as a max component or GNC candidate, k > 11.
+ * aprilsam_amd_factor_audit counts it among the factors it cannot audit (four NaN).  .graph files cannot hold it (save returns 0 and
+ * writes nothing).  A factor is native only if type == APRILSAM_AMD_FACTOR_GAUSSIAN_TYPE AND its eval is this library's.  Debug option
+ * "gaussian_on_host" = 1 packs it as a host-evaluated clique through its own eval() (the A/B oracle of the tests; april_graph_chi2 then
+ * takes its term from state_eval). */
+#define APRILSAM_AMD_FACTOR_GAUSSIAN_TYPE 5
+#define APRILSAM_AMD_GAUSSIAN_MAX_NODES 11      /* the clique limit of factors with more than two nodes: 55 pairs */
+/* copies everything; NULL (+ aprilsam_amd_last_error: -12 for Lambda or k > 11, -13 otherwise) on a bad argument, owning nothing then */
+april_graph_factor_t *aprilsam_amd_factor_gaussian_create(int k, const int *nodes, const double *xbar /*3k*/, const double *eta /*3k*/,
+                                                          const double *Lambda /*3k x 3k row-major*/);
+int aprilsam_amd_factor_get_gaussian(const april_graph_factor_t *factor, int *k);   /* 0 for any other factor */
+
+/* ---- marginalising poses out of a graph ----------------------------------------------------------------------------
+ * aprilsam_amd_marginal_prior: the dense Gaussian that eliminating the nodes M = remove[0, m) (distinct, in range) leaves on their
+ * Markov blanket.  F_M = the packed factors with an endpoint in M; B = their other endpoints, ascending, returned in keep.  With H and g
+ * summed from the linearisation of F_M ONLY, as the param's last factorisation saw it (robust weights, the selected mixture component,
+ * polar slots and another Gaussian factor's blocks count as they stand; no tikhanov term, no LM damping), ordered M first:
+ *     Lambda = H_BB - H_BM H_MM^-1 H_MB        eta = g_B - H_BM H_MM^-1 g_M        xbar = the linearisation point of the nodes in B
+ * computed on the GPU by one workgroup from the contribution slots the factorisation left on the device (two calls give the same bits).
+ * THE PRIOR IS EXACT AT THE LINEARISATION POINT OF THE LAST SOLVE: a caller who wants the exact marginal marginalises after convergence,
+ * or with the states reset to the l_points.
+ * Available exactly when aprilsam_amd_factor_audit is, with its codes: -1 (no retained factor of this graph, or the graph's device copy no
+ * longer holds this param's linearisation), -12 (sharded param, asymmetric W, the retained factor is an incremental step's extended
+ * structure), -13 (bad argument, an id out of range or listed twice), -14.  Also -12, nothing written: |M| + |B| >
+ * APRILSAM_AMD_MARGINAL_MAX_NODES; |B| > cap; a fixed node in M or B (its slots are masked); a graph factor of more than two nodes -- a
+ * host-evaluated clique or a Gaussian factor with k >= 3 -- touching M (a host-evaluated factor of one or two nodes is fine).  A pivot of
+ * H_MM that is not positive or not finite: -2 through aprilsam_amd_last_error, nothing written; the param keeps its factorisation
+ * (the removed block is not what it factorised).  m == 0: returns 0 with *n_keep = 0.  B empty (a component removed whole): H_MM is still
+ * checked; returns 0 with *n_keep = 0 and nothing else written.
+ * Outputs: *n_keep = |B|, keep[|B|], xbar[3 |B|], eta[3 |B|], Lambda[(3 |B|)^2] row-major, written densely, symmetric bit for bit. */
+#define APRILSAM_AMD_MARGINAL_MAX_NODES 40      /* |M| + |B|: the system is 120 x 121 doubles = 116 KB of one workgroup's LDS */
+int aprilsam_amd_marginal_prior(april_graph_t *graph, april_graph_cholesky_param_t *param, int m, const int *remove, int cap, int *n_keep,
+                                int *keep /*cap*/, double *xbar /*3 cap*/, double *eta /*3 cap*/, double *Lambda /*(3 n_keep)^2*/);
+/* Host only, no device: destroys the nodes remove[0, m) and every factor with a node among them (a max-mixture factor is judged by its own
+ * nodes), closes the gaps in both arrays keeping their order, renumbers nodes[] of every remaining factor AND of every max component, and
+ * writes new_index[old] = new, or -1 for a removed node (old N entries; may be NULL).  The graph's device copy is dropped.  Everything is
+ * validated first: -13 (an id out of range or listed twice, a factor that names a node outside the graph) leaves the graph untouched.  0 on
+ * success. */
+int aprilsam_amd_graph_remove_nodes(april_graph_t *graph, int m, const int *remove, int *new_index /*old N entries or NULL*/);
+/* aprilsam_amd_marginal_prior, then aprilsam_amd_factor_gaussian_create on B, then aprilsam_amd_graph_remove_nodes, then the factor appended
+ * with renumbered ids.  All or nothing: every refusal above (and |B| > APRILSAM_AMD_GAUSSIAN_MAX_NODES: -12, the message names |B|)
+ * returns before the graph is touched.  Returns the new factor's index; 0 with no factor when B is empty; or the code.  The param's plan and
+ * retained factor are dropped: the next call plans the smaller graph. */
+int aprilsam_amd_graph_marginalize(april_graph_t *graph, april_graph_cholesky_param_t *param, int m, const int *remove, int *new_index);
+
 /* ---- gating and association of range / bearing observations against landmarks ------------------------------------
  * The step before aprilsam_amd_factor_polar_create: does a candidate measurement (kind, z, W as above; node a observes node b) agree
  * with what the solved graph predicts?  Per candidate, on the GPU right after the path solves of aprilsam_amd_marginals_joint_any:
