@@ -281,7 +281,8 @@ static void inc_impl(april_graph_t *g, april_graph_cholesky_param_t *param) {
     SlotLock lk(param, g);
     {
         auto it = g_ctx.find(param);
-        if (it == g_ctx.end() || !it->second->have_fact) return;         // aprilsam.c:382-383 (no prior chol)
+        // aprilsam.c:382-383 (no prior chol) -- also where a resident loop is open or planned anew and ended without a step
+        if (it == g_ctx.end() || !it->second->have_fact || it->second->fact_kind == FACT_NONE || it->second->resident_open) return;
     }
     if (param->factor_num == zsize(g->factors)) return;                  // aprilsam.c:384-385
     if (inc_refuse_fixed("april_graph_cholesky_inc", g, param)) return;  // (-12 through aprilsam_amd_last_error, nothing written)
@@ -521,7 +522,7 @@ void inc_solve_only(april_graph_t *g, april_graph_cholesky_param_t *param) {
     guarded(param, g, [&] {
         SlotLock lk(param, g);
         auto it = g_ctx.find(param);
-        if (it == g_ctx.end() || !it->second->have_fact || !param->nreordering) return;        // aprilsam.c:580
+        if (it == g_ctx.end() || !it->second->have_fact || it->second->fact_kind == FACT_NONE || it->second->resident_open || !param->nreordering) return;        // aprilsam.c:580
         if (inc_refuse_fixed("april_graph_cholesky_inc_solver", g, param)) return;
         if (refuse_gaussian("april_graph_cholesky_inc_solver", g)) return;
         ensure_device();

@@ -236,6 +236,7 @@ struct Context {
     long long fact_pack = -1; bool fact_upt = false;      // the pack (GraphPack::serial) the factorised system was linearised from; its priors were linearised at d_upt (factor audit)
     bool resident_stepped = false;                 // the current resident loop has enqueued a step (its failure record means something)
     bool resident_failed = false;                  // a step of the current resident loop met a non-positive pivot (resident_sync saw it): resident_end writes nothing
+    bool resident_open = false;                    // between aprilsam_amd_resident_begin and _end: the consumers of the retained factor answer -1 (no_retained_factor)
     DBuf<double> d_sigma, d_sel_scr; DBuf<SelFront> d_sel_fd; DBuf<int> d_sel_i32, d_sel_q; DBuf<int4> d_sel_ent; HBuf<double> h_cov;
     long long fact_serial = 0;                     // factorisations recorded so far (only grows)
     std::vector<SelLevel> sel_levels; int sel_tab_kind = 0, sel_N = 0;
@@ -350,6 +351,12 @@ static void set_const_granules(Context &c, hipStream_t s);
 // marginal covariances (solver_marginals.inc.h): what a successful solver call left in the front pool
 enum { FACT_NONE = 0, FACT_PLAN = 1, FACT_EXTENDED = 2 };      // no factor / the factor of c.plan / tail fronts appended by the incremental path
 static void record_factor(Context &c, int kind, GraphPack &gp);
+// what every consumer of the retained factor asks first: is the front pool still what the last successful solver call
+// on this param left there?  No after a failed call, LM / GNC / chordal (have_fact, fact_kind), after a phase that moved the step counter
+// on (fact_epoch), after a re-plan that no factorisation followed (upload_plan), and while a resident loop is open
+static bool no_retained_factor(const Context &c) {
+    return !c.have_fact || c.st.not_spd || c.fact_kind == FACT_NONE || c.fact_epoch != c.epoch_steps || c.resident_open;
+}
 // slack reserved at plan upload so that the incremental path can append without reallocating device buffers
 constexpr int INC_NODES = 4096, INC_FACT = 16384, INC_I32 = 4 << 20, INC_DEST = 1 << 20, INC_CHILD = 1 << 18, INC_TAB = 1 << 20;
 #define TAIL_POSES (g_opt.tail_poses)         // own poses per tail front of the incremental path (inc_fast_step), option tail_poses (>= 8)
@@ -536,6 +543,8 @@ static void upload_plan(Context &c, hipStream_t s, const ShardLayout *lay = null
     c.retire_captures();
     c.lambda_N = -1;
     c.release_sel();                          // (Sigma and its tables describe the plan being replaced)
+    c.fact_kind = FACT_NONE;                  // (... and so does the retained factor: its fronts are laid out anew.  The call that plans records its own
+                                              // factor when it succeeds; a resident loop that plans and ends without a step leaves the param without one)
     // ---- descriptors + index arrays ----------------------------------------------------------------------------
     std::vector<FrontDesc> &fd = c.inc.fd; fd.assign(P.nF, FrontDesc());
     std::vector<ChildRec> ch(std::max<size_t>(1, P.ch_idx.size()));

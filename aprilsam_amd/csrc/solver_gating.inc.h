@@ -200,7 +200,7 @@ static int ps_context(april_graph_cholesky_param_t *param, const char *who, Cont
     if (g_shard.find(param) != g_shard.end()) { snprintf(msg, sizeof msg, "%s: sharded params are not supported", who); return gate_refuse(ERR_UNSUPPORTED, msg); }
     auto it = g_ctx.find(param);
     if (it != g_ctx.end()) drop_factor_if_toggled(*it->second, g);
-    if (it == g_ctx.end() || !it->second->have_fact || it->second->st.not_spd || it->second->fact_kind == FACT_NONE || it->second->fact_epoch != it->second->epoch_steps) {
+    if (it == g_ctx.end() || no_retained_factor(*it->second)) {
         snprintf(msg, sizeof msg, "%s: no retained factor (no successful solver call since the param was created or last failed)", who);
         return gate_refuse(-1, msg);
     }

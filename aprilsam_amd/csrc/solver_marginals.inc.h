@@ -124,6 +124,7 @@ static void enqueue_selinv(Context &c, hipStream_t s) {
 // (rewind_epoch forgets the factor when it starts the counter over).  fact_serial numbers the factorisations: Sigma and its tables are
 // kept against it.
 static void record_factor(Context &c, int kind, GraphPack &gp) {
+    c.resident_open = false;                                // (a successful solver call: whatever loop was open before it is over)
     c.fact_kind = kind; c.fact_epoch = c.epoch_steps; c.fact_asym = gp.n_asym > 0 || c.wt_any; c.fact_serial++;
     c.fact_fixed = gp.fx_nodes;
     c.fact_pack = gp.serial; c.fact_upt = false;
@@ -168,7 +169,7 @@ static int marginals_impl(april_graph_t *g, april_graph_cholesky_param_t *param,
     if (g_shard.find(param) != g_shard.end()) return refuse(ERR_UNSUPPORTED, "aprilsam_amd_marginals: sharded params are not supported");
     auto it = g_ctx.find(param);
     if (it != g_ctx.end()) drop_factor_if_toggled(*it->second, g);
-    if (it == g_ctx.end() || !it->second->have_fact || it->second->st.not_spd || it->second->fact_kind == FACT_NONE || it->second->fact_epoch != it->second->epoch_steps)
+    if (it == g_ctx.end() || no_retained_factor(*it->second))
         return refuse(-1, "aprilsam_amd_marginals: no retained factor (no successful solver call since the param was created or last failed)");
     Context &c = *it->second;
     if (c.fact_asym) return refuse(ERR_UNSUPPORTED, "aprilsam_amd_marginals: the factorised graph holds factors with an asymmetric information matrix");

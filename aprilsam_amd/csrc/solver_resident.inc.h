@@ -28,6 +28,7 @@ static int resident_begin_impl(april_graph_t *g, april_graph_cholesky_param_t *p
     c.st.n_nodes = gp.N; c.st.n_factors = gp.F; c.st.symbolic_reused = reused; c.st.not_spd = 0; c.st.error_code = 0;
     c.resident_failed = false; c.resident_stepped = false;
     HIPCHECK(hipStreamSynchronize(gp.stream));
+    c.resident_open = true;                       // (include/aprilsam_amd.h: "a resident run in progress" -- also before its first step)
     return 0;
 }
 // enqueue n iterations.  mode 0: asynchronous (hipGraph replay when enabled), returns at once;
@@ -102,6 +103,7 @@ static int resident_end_impl(april_graph_t *g, april_graph_cholesky_param_t *par
     auto it = g_ctx.find(param);
     if (it == g_ctx.end()) return -1;
     Context &c = *it->second;
+    c.resident_open = false;
     GraphPack &gp = pack_for(g);
     hipStream_t s = gp.stream;
     const int N = gp.N, F = gp.F;

@@ -306,6 +306,6 @@ long long tree_solve_bytes(const april_graph_cholesky_param_t *param) {
 int factorised_nodes(const april_graph_cholesky_param_t *param) {
     SlotLock lk(param, nullptr);
     auto it = g_ctx.find(param);
-    if (it == g_ctx.end() || !it->second->have_fact || it->second->st.not_spd || it->second->fact_kind == FACT_NONE || it->second->fact_epoch != it->second->epoch_steps) return -1;
+    if (it == g_ctx.end() || no_retained_factor(*it->second)) return -1;
     return it->second->fact_kind == FACT_EXTENDED ? it->second->inc_N : it->second->plan.N;
 }

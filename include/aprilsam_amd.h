@@ -454,6 +454,11 @@ int aprilsam_amd_level_profile(const april_graph_cholesky_param_t *param, double
  * nodes == NULL: all nodes (n ignored; the graph must hold exactly the factorised nodes).  cov: 9 doubles per node, row-major
  * (x, y, theta: the unknowns of delta_X).  Returns 0, or < 0:
  *   -1   no retained factor (never solved, the last solver call failed or was not positive definite, a resident run in progress)
+ *        A resident run is in progress from aprilsam_amd_resident_begin to aprilsam_amd_resident_end, also before its first step.  A loop
+ *        that ended without a step leaves the factor that begin found -- unless begin had to plan a changed graph (factors or nodes added
+ *        since): the fronts were laid out anew, and the param is without a factor until its next successful solver call.  The same holds
+ *        after an aprilsam_amd_debug_stage call that had to plan.  In both states april_graph_cholesky_inc and april_graph_cholesky_inc_solver
+ *        return silently, as on a param without a factorisation.
  *   -12  sharded param; the factorised graph holds a factor with an asymmetric information matrix (the reference-order path
  *        factorises one triangle of an unsymmetric system: no covariance is defined)
  *   -13  a node id out of range of the factorised system (nodes added since the last solve), or a bad argument
@@ -461,7 +466,13 @@ int aprilsam_amd_level_profile(const april_graph_cholesky_param_t *param, double
  * It sets aprilsam_amd_last_error like every entry point, but -- unlike the solver entry points -- a failed marginals call leaves
  * the param's plan and factor in place: it only reads them, and the next solver call is unaffected.  Sigma is computed once per
  * factorisation and kept beside the factor (a second pool of stats.bytes_fronts bytes, allocated on the first call, freed with the
- * plan; option mem_cap_mb applies): a second call with no solver call in between only extracts.  Two calls give the same bits. */
+ * plan; option mem_cap_mb applies): a second call with no solver call in between only extracts.  Two calls give the same bits.
+ * The system is the PARAM's: `graph` only sizes the nodes == NULL form here and, in aprilsam_amd_gate_xyt, aprilsam_amd_gate_polar and
+ * aprilsam_amd_relative_covariances, supplies the CURRENT states.  After the param's last successful call was made with another graph, or
+ * after the graph was destroyed and built again, these calls (and aprilsam_amd_marginals_joint / _joint_any / _marginals_cross /
+ * aprilsam_amd_solve) still answer for the system that call factorised; only aprilsam_amd_factor_audit and aprilsam_amd_marginal_prior,
+ * which read the graph's device copy, return -1.  A factor's z / W edited in place, or a factor added between old poses, is not seen
+ * before the next solver call (or april_graph_chi2): every consumer keeps answering for the factorised system. */
 int aprilsam_amd_marginals(april_graph_t *graph, april_graph_cholesky_param_t *param, int n, const int *nodes, double *cov);
 /* Joint covariance [[S_aa S_ab]; [S_ba S_bb]] (36 doubles per pair, row-major, a's unknowns first) for pairs on the factor's
  * pattern -- every pair joined by a factor is.  Returns the number of pairs NOT on the pattern (their 36 values are NaN), or the
@@ -525,7 +536,9 @@ int aprilsam_amd_marginals_cross(april_graph_t *graph, april_graph_cholesky_para
  * the column solve, S_aa and S_ii from the selected inversion's Sigma pool: the first call after a solver call runs the inversion as
  * aprilsam_amd_marginals does.  i == anchor gives exact zeros. */
 int aprilsam_amd_relative_covariances(april_graph_t *graph, april_graph_cholesky_param_t *param, int anchor, int n, const int *nodes, double *cov);
-/* N of the calls above: the nodes of the system the retained factor of `param` was made for, or -1 when there is none (no device needed) */
+/* N of the calls above: the nodes of the system the retained factor of `param` was made for, or -1 when there is none (no device needed).
+ * It takes no graph, so it cannot see a node fixed or freed since the factorisation (fixed nodes, below): it answers N until a consumer
+ * that takes the graph has seen the toggle and dropped the factor, -1 from then on. */
 int aprilsam_amd_factorised_nodes(const april_graph_cholesky_param_t *param);
 /* debug: the largest whole-tree work buffer this param has used, in bytes (-1: no context) */
 long long aprilsam_amd_debug_solve_bytes(const april_graph_cholesky_param_t *param);
@@ -868,7 +881,9 @@ int aprilsam_amd_factor_audit(april_graph_t *graph, april_graph_cholesky_param_t
  * aprilsam_amd_gate_xyt: covariances of the free nodes are conditional on Phi, every row and column of a fixed node is exact zeros, so a
  * candidate between a new pose and a fixed map pose is gated with the new pose's covariance alone.  These consumers use the fixed set
  * the retained factor was made with; a toggle after the factorisation drops the retained factor and they answer as without one.
- * Refused with -12, nothing written: april_graph_cholesky_inc and _inc_solver (void: see aprilsam_amd_last_error),
+ * Refused with -12, nothing written: april_graph_cholesky_inc and _inc_solver (void: see aprilsam_amd_last_error; they look in the
+ * reference's order, aprilsam.c:380-385 and 580: a param without a factorisation -- also one whose factor a consumer has dropped after a
+ * toggle -- returns silently first, and so does april_graph_cholesky_inc on a graph without a factor the param has not seen),
  * aprilsam_amd_initialize_chordal, sharded params, aprilsam_amd_marginals_cross and aprilsam_amd_relative_covariances.
  * set_fixed: 0; -13 for a NULL node or a value other than 0 / 1; -12 when the node is not an xyt node of this library or node->impl is
  * in use by something else (node unchanged then).  set_fixed(node, 0) frees the block and leaves impl NULL. */
