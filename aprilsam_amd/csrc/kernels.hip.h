@@ -1288,6 +1288,9 @@ __device__ __forceinline__ void factor_front_blk(double *S, int ld, int nsb, int
 // LDS after the front / panel: the extend-add work lists
 __host__ __device__ inline size_t small_front_lds(int R, int C, int nw) { return (size_t)(R | 1) * C * 8 + wl_bytes(nw); }
 __host__ __device__ inline size_t panel_front_lds(int R, int ns, int nw) { return (size_t)(R | 1) * ns * 8 + wl_bytes(nw); }
+// full or panel mode of a front in a k_front_small launch of nw waves with this full_lds_limit (the kernel's own question; the host asks it
+// again only to report the answer, aprilsam_amd_debug_front_forms)
+__host__ __device__ inline bool front_runs_full(int R, int C, int nw, long long full_lds_limit) { return (long long)small_front_lds(R, C, nw) <= full_lds_limit; }
 
 // small fronts: one NT-thread workgroup per front (512 by default).  Two modes, chosen per front from its size:
 //   full  — the whole frontal array in LDS (assembly, rank-3 elimination steps, one store of the block-lower part);
@@ -1307,7 +1310,7 @@ __device__ __forceinline__ void front_small_body(const DevPlan &P, const int t, 
     if (P.prof && threadIdx.x == 0) P.prof[(size_t)t * PROF_SLOTS + PROF_XCD_UP] = 1 + xcc_id();
     // full_lds_limit (per launch): fronts whose whole array fits run fully in LDS, the others in panel mode.  On levels with
     // far more fronts than compute units the host lowers it, trading per-front latency for workgroups per CU.
-    if ((long long)small_front_lds(R, C, NT / 64) <= full_lds_limit) {
+    if (front_runs_full(R, C, NT / 64, full_lds_limit)) {
         int2 *wl = (int2 *)(S + (size_t)ld * C);
         if (P.prof && threadIdx.x == 0) P.prof[(size_t)t * PROF_SLOTS + 0] = wall_clock64();
         assemble_front<NT, ASM_LDS>(P, D, pool, Hc, 0, nbc, true, S, ld, nullptr, 0, wl, P.prof ? P.prof + (size_t)t * PROF_SLOTS : nullptr, wflags, bad, ev);

@@ -50,6 +50,15 @@ static void launch_backsolve_list(Context &c, hipStream_t s, BsForm form, const 
     else hipLaunchKernelGGL((k_backsolve_t<false>), dim3(n), dim3(TPB), lds, s, c.dp, list, c.d_pool.p, c.d_x.p, split, (int *)nullptr, 0, bad, upd);
 }
 
+// The form of a level's one-workgroup-per-front launch, whose list asks for solve_lds bytes in the 32-columns-at-a-time form.  Latency-bound
+// levels of small fronts: column-per-lane form with the L panel in LDS (at least two workgroups per CU).  (One place for launch_backsolve
+// and for what aprilsam_amd_debug_front_forms reports.)
+static BsForm level_bs_form(const LevelPlan &L, size_t solve_lds) {
+    const bool wave = g_opt.wave_backsolve && L.bs_gemv.grid == 0 && L.n_all < g_opt.tp_fronts && L.maxns <= BSW_MAX_NS && L.solve_w_lds <= 80 * 1024;
+    return wave ? BS_WAVE : solve_lds >= (size_t)(BS_TALL_ROWS + NB + 8 + NB * (NB + 1)) * 8 ? BS_THREAD_TALL : BS_THREAD;
+}
+// ... and of a multi-level back substitution whose widest own part has maxns columns: column-per-lane, or k_backsolve_t waiting on flags
+static bool multi_bs_wave(int maxns) { return g_opt.wave_backsolve && maxns <= BSW_MAX_NS; }
 // back substitution of one level: update-row products of the large fronts on many workgroups, then one workgroup per front
 // (list_off >= 0: the level's list of every front replaced by the list_n entries there -- an XCD-placed list of a level of small fronts only)
 static void launch_backsolve(Context &c, const LevelPlan &L, hipStream_t s, KTimer &kt, const int *tab = nullptr, UpdArgs upd = UpdArgs{}, int list_off = -1, int list_n = 0) {
@@ -67,17 +76,16 @@ static void launch_backsolve(Context &c, const LevelPlan &L, hipStream_t s, KTim
         n_all = L.n_rest; all_off = L.rest_off; solve_lds = L.rest_lds;
         if (!n_all) { kt.toc(); return; }
     }
-    // latency-bound levels of small fronts: column-per-lane form with the L panel in LDS (at least two workgroups per CU)
-    const bool wave = g_opt.wave_backsolve && L.bs_gemv.grid == 0 && L.n_all < g_opt.tp_fronts && L.maxns <= BSW_MAX_NS && L.solve_w_lds <= 80 * 1024;
-    const BsForm form = wave ? BS_WAVE : solve_lds >= (size_t)(BS_TALL_ROWS + NB + 8 + NB * (NB + 1)) * 8 ? BS_THREAD_TALL : BS_THREAD;
-    launch_backsolve_list(c, s, form, tab + all_off, n_all, wave ? L.solve_w_lds : solve_lds, L.bs_gemv.grid > 0 ? 1 : 0, c.d_bad.p, upd);
+    const BsForm form = level_bs_form(L, solve_lds);
+    launch_backsolve_list(c, s, form, tab + all_off, n_all, form == BS_WAVE ? L.solve_w_lds : solve_lds, L.bs_gemv.grid > 0 ? 1 : 0, c.d_bad.p, upd);
     kt.toc();
 }
 
 // The hand-over form of ONE multi-level back substitution whose tallest update block has max_upd_rows rows: granules are gathered one per lane
-// (kernels.hip.h gather_x), so a launch with a taller block takes the form every other flag uses.  (No plan met so far puts such a front into a
-// multi-level launch -- a front of 86 update blocks that still fits a workgroup's LDS needs four or more ancestors of at most 24-33 poses each
-// -- but an incremental step's fronts near the root collect rows without such a bound.)
+// (kernels.hip.h gather_x), so a launch with a taller block takes the form every other flag uses.  (Of the batch plans only a designed one puts such a front
+// into a multi-level launch -- a front of 86 update blocks that still fits a workgroup's LDS needs four or more ancestors of at most 24-33 poses
+// each: the seven-level clique tree of tests/support/clique_trees.py -- but an incremental step's fronts near the root collect rows without such
+// a bound.)
 static int launch_xmode(const Context &c, int max_upd_rows) { return c.dp.xmode == X_TAGGED && max_upd_rows > TPB ? (int)X_FLUSH : c.dp.xmode; }
 static int device_cus() {
     int cus = 0;
@@ -102,7 +110,7 @@ static DevPlan persist_plan(const Context &c) { DevPlan d = c.dp; d.flevel = c.d
 // and widest own part.
 static void launch_backsolve_multi(Context &c, hipStream_t s, const DevPlan &dp, const int *list, int n, size_t lds, int maxns, int *xflags, const UpdArgs &upd) {
     lds = handover_lds(dp.xmode, lds, n);
-    if (g_opt.wave_backsolve && maxns <= BSW_MAX_NS) hipLaunchKernelGGL(k_backsolve_w, dim3(n), dim3(TPB), lds, s, dp, list, c.d_pool.p, c.d_x.p, xflags, c.d_bad.p, upd);
+    if (multi_bs_wave(maxns)) hipLaunchKernelGGL(k_backsolve_w, dim3(n), dim3(TPB), lds, s, dp, list, c.d_pool.p, c.d_x.p, xflags, c.d_bad.p, upd);
     else hipLaunchKernelGGL((k_backsolve_t<true>), dim3(n), dim3(TPB), lds, s, dp, list, c.d_pool.p, c.d_x.p, 0, xflags, 1, c.d_bad.p, upd);
 }
 

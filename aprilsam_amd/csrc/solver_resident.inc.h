@@ -188,6 +188,65 @@ int level_profile(const april_graph_cholesky_param_t *param, double *out, int ca
     }
     return P.nLevels;
 }
+// The form every front of the batch plan takes in the launches of enqueue_numeric, READ from what those launches read -- the level tables
+// (LevelPlan, Context::base_tab), the multi-level launches' lists and limits (Context::p_*, u_*, persist_*_l0), persist_plan's hand-over
+// form -- through the predicates the launches and kernels themselves ask (front_runs_full, level_bs_form, multi_bs_wave): nothing is decided
+// here.  out (ints): [nF, nLevels, FF_FRONT, offset of the level records], FF_FRONT ints per front
+//   [level, factorisation 0 full-LDS / 1 panel / 2 multi-workgroup, 1 = inside the multi-level launch of the up-sweep, ... of the down-sweep,
+//    back substitution 0 k_backsolve_w / 1 k_backsolve_t / 2 k_backsolve_t TALL / 3 k_backsolve_blk, its helper workgroups,
+//    1 = k_backsolve_gemv precedes it, hand-over form of its down launch (X_FLUSH 0 / X_WT 1 / X_TAGGED 2; -1 behind a kernel boundary)]
+// then per level [n_big, 1 = wide updates grouped, outer blocks nob, nob x (rb of k_block_solve, tile of the closing wide update, of the
+// "ahead" update, of the single-block update; 0 = no such launch)].  Returns the ints it needs (out filled up to cap), -1 without a plan.
+constexpr int FF_FRONT = 8;
+int debug_front_forms(const april_graph_cholesky_param_t *param, int *out, int cap) {
+    SlotLock lk(param, nullptr);
+    auto it = g_ctx.find(param);
+    if (it == g_ctx.end() || !it->second->have_plan || (int)it->second->levels.size() != it->second->plan.nLevels || !it->second->inc.t_first.empty()) return -1;
+    Context &c = *it->second;
+    const Plan &P = c.plan;
+    const std::vector<int> &tab = c.base_tab;
+    std::vector<int> o((size_t)4 + (size_t)FF_FRONT * P.nF, -1);
+    o[0] = P.nF; o[1] = P.nLevels; o[2] = FF_FRONT; o[3] = (int)o.size();
+    const int l0 = c.persist_l0 >= 0 ? c.persist_l0 : P.nLevels;            // (as enqueue_numeric)
+    const int ul0 = l0 < P.nLevels ? c.persist_up_l0 : l0, dl0 = l0 < P.nLevels ? c.persist_dn_l0 : l0;
+    const int xmode = l0 < P.nLevels ? persist_plan(c).xmode : -1;
+    auto rec = [&](int t) { return o.data() + 4 + (size_t)FF_FRONT * t; };
+    for (int l = 0; l < P.nLevels; l++) {
+        const LevelPlan &L = c.levels[l];
+        const bool up_in = l >= ul0, dn_in = l >= dl0;
+        for (int k = 0; k < L.n_all; k++) { int *r = rec(tab[L.all_off + k]); r[0] = l; r[2] = up_in; r[3] = dn_in; r[5] = 0; r[6] = 0; r[7] = dn_in ? xmode : -1; }
+        // up-sweep: the level's own launch (its workgroup width and limit) or the multi-level one (p_nt, p_up_full)
+        const int nw = waves_of(up_in ? c.p_nt : L.small_nt);
+        const long long full = up_in ? c.p_up_full : L.full_limit;
+        for (int k = 0; k < L.n_small; k++) { const int t = tab[L.small_off + k]; rec(t)[1] = front_runs_full(P.rows(t), P.cols(t), nw, full) ? 0 : 1; }
+        for (int k = 0; k < L.asm_big.n; k++) rec(tab[L.asm_big.list_off + k])[1] = 2;
+        // down-sweep
+        if (dn_in) {
+            for (int k = 0; k < L.n_all; k++) rec(tab[L.all_off + k])[4] = multi_bs_wave(c.p_dn_maxns) ? 0 : 1;
+        } else {
+            for (int k = 0; k < L.bs_gemv.n; k++) rec(tab[L.bs_gemv.list_off + k])[6] = 1;
+            int n_all = L.n_all, all_off = L.all_off; size_t solve_lds = L.solve_lds;
+            if (L.bs_blk.grid > 0) {
+                for (int k = 0; k < L.bs_blk.n; k++) { int *r = rec(tab[L.bs_blk.list_off + k]); r[4] = 3; r[5] = tab[L.bs_blk.pre_off + k + 1] - tab[L.bs_blk.pre_off + k] - 1; }
+                n_all = L.n_rest; all_off = L.rest_off; solve_lds = L.rest_lds;
+            }
+            if (n_all) {
+                const BsForm form = level_bs_form(L, solve_lds);
+                for (int k = 0; k < n_all; k++) rec(tab[all_off + k])[4] = form == BS_WAVE ? 0 : form == BS_THREAD ? 1 : 2;
+            }
+        }
+    }
+    for (int l = 0; l < P.nLevels; l++) {
+        const LevelPlan &L = c.levels[l];
+        o.push_back(L.n_big); o.push_back(L.paired ? 1 : 0); o.push_back((int)L.bchain.size());
+        for (size_t b = 0; b < L.bchain.size(); b++) {
+            auto tile = [&](const std::vector<Launch> &v) { return b < v.size() && v[b].grid > 0 ? v[b].tile : 0; };
+            o.push_back(L.btile[b].grid > 0 ? L.btile[b].tile : 0); o.push_back(tile(L.syrkw)); o.push_back(tile(L.syrka)); o.push_back(tile(L.syrk1));
+        }
+    }
+    for (int i = 0; i < (int)o.size() && i < cap; i++) out[i] = o[i];
+    return (int)o.size();
+}
 // debug option pool_guard checking itself: declares ONE extra band that lies inside the first frontal array (which the last step
 // wrote) and runs the check, which must then report ERR_GUARD; the param's context is dropped by the failure path as for any error
 int debug_guard_selftest(const april_graph_cholesky_param_t *param) {

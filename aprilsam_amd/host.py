@@ -173,6 +173,8 @@ class SolverLib:
                                                         C.POINTER(abi.GncReport), _dp, _dp]
                 d.aprilsam_amd_debug_graph_captures.argtypes = [C.POINTER(abi.CholeskyParam)]
                 d.aprilsam_amd_debug_graph_captures.restype = C.c_longlong
+            if hasattr(d, "aprilsam_amd_debug_front_forms"):
+                d.aprilsam_amd_debug_front_forms.argtypes = [C.POINTER(abi.CholeskyParam), _ip, C.c_int]
             if hasattr(d, "aprilsam_amd_initialize_chordal"):    # (defined in the HIP translation unit)
                 d.aprilsam_amd_chordal_opts_init.argtypes = [C.POINTER(abi.ChordalOpts)]
                 d.aprilsam_amd_chordal_opts_init.restype = None
@@ -353,6 +355,24 @@ class Param:
     def graph_captures(self):
         """hipGraphs captured and instantiated for this param so far (aprilsam_amd_debug_graph_captures); -1: no context yet"""
         return int(self.lib.dll.aprilsam_amd_debug_graph_captures(self.ptr))
+
+    def front_forms(self):
+        """(fronts [nF, 8], levels): the form every front of this param's batch plan takes in a batch step's launches
+        (aprilsam_amd_debug_front_forms; columns as include/aprilsam_amd.h lists them), and per level a dict(n_big, grouped,
+        blocks = [(rb, tile of the closing wide update, of the "ahead" update, of the single-block update)])"""
+        n = int(self.lib.dll.aprilsam_amd_debug_front_forms(self.ptr, None, 0))
+        if n < 0:
+            raise RuntimeError("no batch plan for this param")
+        buf = np.zeros(n, np.int32)
+        assert int(self.lib.dll.aprilsam_amd_debug_front_forms(self.ptr, _np_i(buf), n)) == n
+        nF, nL, w, off = (int(v) for v in buf[:4])
+        fronts = buf[4:4 + w * nF].reshape(nF, w).copy()
+        levels, k = [], off
+        for _ in range(nL):
+            nob = int(buf[k + 2])
+            levels.append(dict(n_big=int(buf[k]), grouped=bool(buf[k + 1]), blocks=[tuple(int(v) for v in buf[k + 3 + 4 * b:k + 7 + 4 * b]) for b in range(nob)]))
+            k += 3 + 4 * nob
+        return fronts, levels
 
     def destroy(self):
         if self.ptr:

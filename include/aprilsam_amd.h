@@ -1082,6 +1082,18 @@ int aprilsam_amd_debug_stage(april_graph_t *graph, april_graph_cholesky_param_t 
 /* debug (env APRILSAM_AMD_KPROF=1): 16 wall-clock stamps (100 MHz ticks) per front from the last numeric pass */
 int aprilsam_amd_debug_front_times(const april_graph_cholesky_param_t *param, long long *out, int n_fronts);
 
+/* debug (tests/test_gpu_front_shapes.py): the form every front of the param's batch plan takes in a batch step's launches under the options
+ * the plan was made with, read from the launch tables themselves -- nothing is decided again.  out (ints):
+ *   [0] fronts nF   [1] levels   [2] ints per front (8)   [3] offset of the level records
+ *   per front t, at 4 + 8 t: level; factorisation 0 full-LDS / 1 panel / 2 multi-workgroup; 1 = inside the multi-level launch of the
+ *     up-sweep; the same of the down-sweep; back substitution 0 k_backsolve_w / 1 k_backsolve_t / 2 k_backsolve_t TALL / 3 k_backsolve_blk;
+ *     helper workgroups of k_backsolve_blk; 1 = k_backsolve_gemv precedes it; hand-over form of its down launch (0 flush, 1 write-through,
+ *     2 granules; -1: its launch follows a kernel boundary)
+ *   per level, from [3] on: fronts on the multi-workgroup path; 1 = wide updates grouped; outer blocks nob; then nob x { rb of k_block_solve,
+ *     tile of the wide update that closes the block, of the "ahead" update, of the single-block update; 0 = no such launch }
+ * Returns the number of ints the record takes (out is filled up to cap), or -1: no plan, or a plan extended by tail fronts. */
+int aprilsam_amd_debug_front_forms(const april_graph_cholesky_param_t *param, int *out, int cap);
+
 const char *aprilsam_amd_version(void);
 
 #ifdef __cplusplus
