@@ -13,6 +13,7 @@
 #include <chrono>
 #include <thread>
 #include <cmath>
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -254,6 +255,7 @@ struct PatchList {
 #include "solver_calls.inc.h"
 #include "solver_resident.inc.h"
 #include "solver_shard.inc.h"
+#include "solver_query.inc.h"
 #include "solver_marginals.inc.h"
 #include "solver_gating.inc.h"
 #include "solver_audit.inc.h"

@@ -588,53 +588,42 @@ static double chi2_impl(april_graph_t *g) {
 }
 
 
-// aprilsam_amd_max_selected (DESIGN.md section 12): which component each listed factor's most recent linearisation used -- k_select_mixture's
-// record (d_sel) for the factors on the device, the host's selection (select_new_max) or -1 for the others.  A bad index is refused before
-// anything is read, and (like every query) leaves the param's plan alone.
-int max_selected(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *factors, int *out) {
+// What aprilsam_amd_max_selected and aprilsam_amd_robust_weights share: the record a kernel keeps per factor of one family (side table
+// `side`, written column mirrored in `mirror`) read for the listed graph factors through the family's index map `of`; `none` for a factor
+// outside the family or a graph without a device copy.  A bad index is refused before anything is read.  Unlike the queries of the
+// retained factor these run under guarded_rc: a failure drops the param's state.
+template <class T>
+static int side_record(const char *who, april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *factors, T *out, SideTable GraphPack::*side,
+                       std::vector<T> GraphPack::*mirror, std::vector<int> GraphPack::*of, T none) {
     const int Fg = g ? zsize(g->factors) : 0;
-    if (!g || n < 0 || (n > 0 && (!factors || !out))) { set_last_error(ERR_BAD_GRAPH, "aprilsam_amd_max_selected: bad argument"); return ERR_BAD_GRAPH; }
+    if (!g || n < 0 || (n > 0 && (!factors || !out))) { set_last_error(ERR_BAD_GRAPH, std::string(who) + ": bad argument"); return ERR_BAD_GRAPH; }
     for (int i = 0; i < n; i++)
         if (factors[i] < 0 || factors[i] >= Fg) {
-            set_last_error(ERR_BAD_GRAPH, "aprilsam_amd_max_selected: factor " + std::to_string(factors[i]) + " out of range (" + std::to_string(Fg) + " factors)");
+            set_last_error(ERR_BAD_GRAPH, std::string(who) + ": factor " + std::to_string(factors[i]) + " out of range (" + std::to_string(Fg) + " factors)");
             return ERR_BAD_GRAPH;
         }
     return guarded_rc(param, g, [&]() -> int {
         SlotLock lk(param, g);
         auto it = g_packs.find(g);
-        if (it == g_packs.end() || it->second->slot != t_slot) { for (int i = 0; i < n; i++) out[i] = -1; return 0; }
+        if (it == g_packs.end() || it->second->slot != t_slot) { for (int i = 0; i < n; i++) out[i] = none; return 0; }
         GraphPack &gp = *it->second;
-        std::vector<int> sel(gp.mx_sel);
-        if (gp.mx.on_device > 0) { HIPCHECK(hipStreamSynchronize(gp.stream)); gp.mx.read_back(gp.stream, sel.data()); }
+        std::vector<T> rec(gp.*mirror);
+        if ((gp.*side).on_device > 0) { HIPCHECK(hipStreamSynchronize(gp.stream)); (gp.*side).read_back(gp.stream, rec.data()); }
+        const std::vector<int> &idx = gp.*of;
         for (int i = 0; i < n; i++) {
-            const int gi = factors[i], m = gi < (int)gp.mx_of.size() && gi < gp.Fg ? gp.mx_of[gi] : -1;
-            out[i] = m >= 0 ? sel[m] : -1;
+            const int gi = factors[i], q = gi < (int)idx.size() && gi < gp.Fg ? idx[gi] : -1;
+            out[i] = q >= 0 ? rec[q] : none;
         }
         return 0;
     });
 }
-
+// aprilsam_amd_max_selected (DESIGN.md section 12): which component each listed factor's most recent linearisation used -- k_select_mixture's
+// record (d_sel) for the factors on the device, the host's selection (select_new_max) or -1 for the others
+int max_selected(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *factors, int *out) {
+    return side_record("aprilsam_amd_max_selected", g, param, n, factors, out, &GraphPack::mx, &GraphPack::mx_sel, &GraphPack::mx_of, -1);
+}
 // aprilsam_amd_robust_weights: the weight each listed factor's most recent linearisation used -- k_robust_weight's
-// record (d_rb_w) for the factors on the device, the host's weight (select_new_robust) or -1 for the others.  The rule of max_selected.
+// record (d_rb_w) for the factors on the device, the host's weight (select_new_robust) or -1 for the others
 int robust_weights(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *factors, double *out) {
-    const int Fg = g ? zsize(g->factors) : 0;
-    if (!g || n < 0 || (n > 0 && (!factors || !out))) { set_last_error(ERR_BAD_GRAPH, "aprilsam_amd_robust_weights: bad argument"); return ERR_BAD_GRAPH; }
-    for (int i = 0; i < n; i++)
-        if (factors[i] < 0 || factors[i] >= Fg) {
-            set_last_error(ERR_BAD_GRAPH, "aprilsam_amd_robust_weights: factor " + std::to_string(factors[i]) + " out of range (" + std::to_string(Fg) + " factors)");
-            return ERR_BAD_GRAPH;
-        }
-    return guarded_rc(param, g, [&]() -> int {
-        SlotLock lk(param, g);
-        auto it = g_packs.find(g);
-        if (it == g_packs.end() || it->second->slot != t_slot) { for (int i = 0; i < n; i++) out[i] = -1; return 0; }
-        GraphPack &gp = *it->second;
-        std::vector<double> w(gp.rb_w);
-        if (gp.rb.on_device > 0) { HIPCHECK(hipStreamSynchronize(gp.stream)); gp.rb.read_back(gp.stream, w.data()); }
-        for (int i = 0; i < n; i++) {
-            const int gi = factors[i], q = gi < (int)gp.rb_of.size() && gi < gp.Fg ? gp.rb_of[gi] : -1;
-            out[i] = q >= 0 ? w[q] : -1.0;
-        }
-        return 0;
-    });
+    return side_record("aprilsam_amd_robust_weights", g, param, n, factors, out, &GraphPack::rb, &GraphPack::rb_w, &GraphPack::rb_of, -1.0);
 }

@@ -63,36 +63,47 @@ struct IncState {
 // marginal covariances (solver_marginals.inc.h): per level, the ranges of its work entries in the selected inversion's table
 struct SelLevel { int gat_off = 0, n_gat = 0, diag_off = 0, n_diag = 0, tri_off = 0, n_tri = 0, x_off = 0, n_x = 0, sus_off = 0, n_sus = 0, sss_off = 0, n_sss = 0; };
 
-// joint covariances of any pair and gating (solver_gating.inc.h): the fronts of the retained factor's structure (host), the scratch maps of
-// one call, and the device buffers of the path solves
+// The structure the retained factor lives in, derived once for all its readers (factor_view, solver_query.inc.h: builder and validity rule):
+// the fronts (scr: written by the selected inversion's table builder, read by its kernels alone), their depth below the root, the fronts of
+// every depth (root first), i32 = pos | pos_front (node -> elimination position, position -> owning front) of the N nodes with its one
+// device copy, the end of the pool the fronts occupy and the estimated flops of the selected inversion
+struct FactorView {
+    long long gen = 0;                     // grows with every rebuild: what the readers' own tables are kept against
+    int kind = 0; long long serial = -1;   // FACT_* and fact_serial it was built for (kind 0: none)
+    int N = 0; long long pool_end = 1; double flops = 0;
+    std::vector<SelFront> fr; std::vector<int> depth, i32; std::vector<std::vector<int>> lev;
+    DBuf<int> d_i32; bool on_device = false;
+    void release() { d_i32.release(); fr.clear(); depth.clear(); i32.clear(); lev.clear(); kind = 0; serial = -1; on_device = false; }
+};
+
+// joint covariances of any pair and gating (solver_gating.inc.h): the scratch maps of one call, and the device buffers of the path solves
 struct PathState {
-    long long serial = -1;                 // fact_serial the host tables describe
-    int N = 0;
-    std::vector<SelFront> fr; std::vector<int> depth, i32, rec, node_j;      // rec: front -> record, node_j: node -> column group (-1 between calls)
+    long long gen = -1;                    // FactorView::gen the scratch maps are sized for
+    std::vector<int> rec, node_j;          // rec: front -> record, node_j: node -> column group (both -1 between calls)
     DBuf<PsFront> d_fr; DBuf<int4> d_ent; DBuf<int> d_cmap; DBuf<long long> d_at; DBuf<PsPath> d_path; DBuf<PsPair> d_pair;
     DBuf<double> d_buf, d_cov, d_in; HBuf<double> h_out;
     DBuf<int> d_pidx;                      // k_gate_polar: candidate -> its pair's block in d_cov
     long long peak_doubles = 0;            // the largest work buffer a chunk has used
     void release() {
         d_fr.release(); d_ent.release(); d_cmap.release(); d_at.release(); d_path.release(); d_pair.release(); d_buf.release(); d_cov.release(); d_in.release(); h_out.release(); d_pidx.release();
-        fr.clear(); depth.clear(); i32.clear(); rec.clear(); node_j.clear(); serial = -1;
+        rec.clear(); node_j.clear(); gen = -1;
     }
 };
 
-// solves with the retained factor (solver_treesolve.inc.h): the tables of the whole-tree passes, kept against the factorisation counter,
+// solves with the retained factor (solver_treesolve.inc.h): the tables of the whole-tree passes, kept against the view's generation,
 // and the device / pinned buffers of one call
 struct TsLevel { int asm_off = 0, n_asm = 0, tr_off = 0, n_tr = 0, gm_off = 0, n_gm = 0, gat_off = 0, n_gat = 0, gt_off = 0, n_gt = 0; };
 struct TreeState {
-    long long serial = -1;                 // fact_serial the tables describe
+    long long gen = -1;                    // FactorView::gen the tables describe
     long long rows = 0;                    // sum over the fronts of s + u: the work buffer takes this many doubles per column
     std::vector<int> wrow; std::vector<TsLevel> lev;      // a front's first row in the work buffer; the levels, root first
-    DBuf<PsFront> d_fr; DBuf<TsFront> d_tf; DBuf<int2> d_ent; DBuf<int> d_cptr, d_npos, d_pos, d_nodes; DBuf<TsKid> d_cent;
+    DBuf<PsFront> d_fr; DBuf<TsFront> d_tf; DBuf<int2> d_ent; DBuf<int> d_cptr, d_npos, d_nodes; DBuf<TsKid> d_cent;
     DBuf<double> d_buf, d_B, d_st; HBuf<double> h_B, h_X;
     long long peak_bytes = 0;              // the largest work buffer a call has used
     void release() {
-        d_fr.release(); d_tf.release(); d_ent.release(); d_cptr.release(); d_npos.release(); d_pos.release(); d_nodes.release(); d_cent.release();
+        d_fr.release(); d_tf.release(); d_ent.release(); d_cptr.release(); d_npos.release(); d_nodes.release(); d_cent.release();
         d_buf.release(); d_B.release(); d_st.release(); h_B.release(); h_X.release();
-        wrow.clear(); lev.clear(); serial = -1;
+        wrow.clear(); lev.clear(); gen = -1;
     }
 };
 
@@ -231,22 +242,23 @@ struct Context {
     DBuf<int> d_fx_mask;                           // ... and which nodes of a covariance query are among them (k_fix_cov)
     std::vector<int> fact_fixed;                   // the fixed nodes the retained factor was made with (record_factor)
     // marginal covariances (solver_marginals.inc.h): what the last successful solver call left in d_pool (FACT_*), at which value of
-    // epoch_steps; the Sigma pool (front pool layout) and the step it was computed for; launch tables built per plan
+    // epoch_steps; the Sigma pool (front pool layout) and the step it was computed for; launch tables kept against the view's generation
     int fact_kind = 0; long long fact_epoch = -1; bool fact_asym = false;
     long long fact_pack = -1; bool fact_upt = false;      // the pack (GraphPack::serial) the factorised system was linearised from; its priors were linearised at d_upt (factor audit)
     bool resident_stepped = false;                 // the current resident loop has enqueued a step (its failure record means something)
     bool resident_failed = false;                  // a step of the current resident loop met a non-positive pivot (resident_sync saw it): resident_end writes nothing
     bool resident_open = false;                    // between aprilsam_amd_resident_begin and _end: the consumers of the retained factor answer -1 (no_retained_factor)
-    DBuf<double> d_sigma, d_sel_scr; DBuf<SelFront> d_sel_fd; DBuf<int> d_sel_i32, d_sel_q; DBuf<int4> d_sel_ent; HBuf<double> h_cov;
+    DBuf<double> d_sigma, d_sel_scr; DBuf<SelFront> d_sel_fd; DBuf<int> d_sel_q; DBuf<int4> d_sel_ent; HBuf<double> h_cov;
     long long fact_serial = 0;                     // factorisations recorded so far (only grows)
-    std::vector<SelLevel> sel_levels; int sel_tab_kind = 0, sel_N = 0;
-    long long sel_serial = -1, sel_tab_serial = -1, sel_runs = 0, sel_pool = 1; double sel_flops = 0;
+    std::vector<SelLevel> sel_levels;
+    long long sel_serial = -1, sel_tab_gen = -1, sel_runs = 0;      // sel_serial: the factorisation Sigma was computed for; sel_tab_gen: FactorView::gen of the tables
+    FactorView view;
     PathState ps;
     TreeState ts;
     void release_sel() {
-        d_sigma.release(); d_sel_scr.release(); d_sel_fd.release(); d_sel_i32.release(); d_sel_q.release(); d_sel_ent.release(); h_cov.release();
-        sel_levels.clear(); sel_serial = -1; sel_tab_serial = -1;
-        ps.release(); ts.release();
+        d_sigma.release(); d_sel_scr.release(); d_sel_fd.release(); d_sel_q.release(); d_sel_ent.release(); h_cov.release();
+        sel_levels.clear(); sel_serial = -1; sel_tab_gen = -1;
+        view.release(); ps.release(); ts.release();
     }
     void release() {
         release_sel();
@@ -277,6 +289,12 @@ void drop_context(const april_graph_cholesky_param_t *p) {
     SlotLock lk(p, nullptr);
     auto it = g_ctx.find(p);
     if (it != g_ctx.end()) { it->second->release(); g_ctx.erase(it); }
+}
+// the debug counters and their like: one field of the param's context, or -1 for a param without one
+template <class F> static long long context_field(const april_graph_cholesky_param_t *p, F f) {
+    SlotLock lk(p, nullptr);
+    auto it = g_ctx.find(p);
+    return it == g_ctx.end() ? -1 : (long long)f(*it->second);
 }
 bool get_stats(const april_graph_cholesky_param_t *p, aprilsam_amd_stats_t *out) {
     SlotLock lk(p, nullptr);

@@ -3,23 +3,12 @@
 // by triangular solves along assembly-tree paths (pathsolve.hip.h), and the Mahalanobis gating of candidate xyt measurements.
 // DESIGN.md section 13.  aprilsam_amd_gate_polar / aprilsam_amd_associate_polar: the same for range / bearing / range-bearing measurements,
 // and their nearest-neighbour association against landmarks (polargate.hip.h).  DESIGN.md section 21.
+// Admission, refusals, the guard and the structure the factor lives in: solver_query.inc.h (RetainedQuery, FactorView).
 // ------------------------------------------------------------------------------------------------------
-// The fronts of the factor's structure (sel_fronts, solver_marginals.inc.h: the plan or the incremental path's extended structure),
-// kept against the factorisation counter.
-static void ps_fronts(Context &c) {
-    PathState &S = c.ps;
-    if (S.serial == c.fact_serial) return;
-    S.serial = -1;
-    long long pool_end; double flops;
-    S.N = sel_fronts(c, S.fr, S.depth, S.i32, pool_end, flops);
-    S.rec.assign(S.fr.size(), -1);
-    S.serial = c.fact_serial;
-}
-
 // doubles of work buffer node q's three columns take: 3 (s + u) summed over its path
-static long long ps_path_doubles(const PathState &S, int q) {
+static long long ps_path_doubles(const FactorView &V, int q) {
     long long d = 0;
-    for (int t = S.i32[S.N + S.i32[q]]; t >= 0; t = S.fr[t].parent) d += 3ll * (S.fr[t].s + S.fr[t].u);
+    for (int t = V.i32[V.N + V.i32[q]]; t >= 0; t = V.fr[t].parent) d += 3ll * (V.fr[t].s + V.fr[t].u);
     return d;
 }
 
@@ -27,17 +16,18 @@ static long long ps_path_doubles(const PathState &S, int q) {
 // output slots out0, out0 + 1, ...: device S.d_cov and pinned S.h_out.
 static void ps_chunk(Context &c, hipStream_t s, const std::vector<int> &nodes, const std::vector<int2> &pj, int out0) {
     PathState &S = c.ps;
-    const std::vector<SelFront> &fr = S.fr;
-    const int N = S.N, nn = (int)nodes.size();
+    const FactorView &V = c.view;                               // (ps_run has made it current)
+    const std::vector<SelFront> &fr = V.fr;
+    const int N = V.N, nn = (int)nodes.size();
     std::vector<int> pbeg((size_t)nn + 1, 0), pfr;              // the fronts on each node's path, its own front first
     for (int j = 0; j < nn; j++) {
-        for (int t = S.i32[N + S.i32[nodes[j]]]; t >= 0; t = fr[t].parent) pfr.push_back(t);
+        for (int t = V.i32[N + V.i32[nodes[j]]]; t >= 0; t = fr[t].parent) pfr.push_back(t);
         pbeg[j + 1] = (int)pfr.size();
     }
     // records: the fronts the columns pass through, deepest level first (a parent's record comes after its children's)
     std::vector<int> touched;
     for (int t : pfr) if (S.rec[t] < 0) { S.rec[t] = 0; touched.push_back(t); }
-    std::sort(touched.begin(), touched.end(), [&](int x, int y) { return S.depth[x] != S.depth[y] ? S.depth[x] > S.depth[y] : x < y; });
+    std::sort(touched.begin(), touched.end(), [&](int x, int y) { return V.depth[x] != V.depth[y] ? V.depth[x] > V.depth[y] : x < y; });
     const int nr = (int)touched.size();
     for (int r = 0; r < nr; r++) S.rec[touched[r]] = r;
     // the nodes through each record, in node-list order: slot[e] = index of path entry e's node among its front's nodes
@@ -66,7 +56,7 @@ static void ps_chunk(Context &c, hipStream_t s, const std::vector<int> &nodes, c
             if (e + 1 < pbeg[j + 1])
                 for (int k = 0; k < 3; k++) cmap[R.cmap + 3 * slot[e] + k] = 3 * slot[e + 1] + k;
         }
-        const int e0 = pbeg[j], p = S.i32[nodes[j]];
+        const int e0 = pbeg[j], p = V.i32[nodes[j]];
         const SelFront &F = fr[pfr[e0]];
         const PsFront &R = rec[S.rec[pfr[e0]]];
         const int ld = R.s + R.u, l = 3 * (p - F.first);
@@ -86,7 +76,7 @@ static void ps_chunk(Context &c, hipStream_t s, const std::vector<int> &nodes, c
     std::vector<int4> ent;
     for (int r0 = 0; r0 < nr; ) {
         int r1 = r0;
-        while (r1 < nr && S.depth[touched[r1]] == S.depth[touched[r0]]) r1++;
+        while (r1 < nr && V.depth[touched[r1]] == V.depth[touched[r0]]) r1++;
         Lev L;
         L.tr_off = (int)ent.size();
         for (int r = r0; r < r1; r++) for (int y = 0; y * SEL_T < rec[r].ncol; y++) ent.push_back(int4{ r, y, 0, 0 });
@@ -138,12 +128,12 @@ struct PsTail { size_t extra = 0; std::function<void(hipStream_t)> enqueue; };
 // joint blocks of the n pairs (qa, qb) into S.d_cov / S.h_out (36 per pair); gate != null: then the gate of candidate i, in = 18
 // doubles each (k_gate_xyt), its d2 and S behind the blocks in S.h_out; tail != null (and gate_in null): the caller's kernel instead.
 static void ps_run(Context &c, hipStream_t s, int n, const int *qa, const int *qb, const double *gate_in, const PsTail *tail = nullptr) {
-    ps_fronts(c);
+    const FactorView &V = factor_view(c);
     PathState &S = c.ps;
+    if (S.gen != V.gen) { S.rec.assign(V.fr.size(), -1); S.node_j.assign((size_t)V.N, -1); S.gen = V.gen; }
     S.d_cov.need((size_t)36 * n);
     S.h_out.need((size_t)(gate_in ? 46 : 36) * n + (tail ? tail->extra : 0));
     const long long budget = ps_budget();
-    if ((int)S.node_j.size() != S.N) S.node_j.assign((size_t)S.N, -1);
     std::vector<int> nodes; std::vector<int2> pj;
     long long used = 0;
     int first = 0;
@@ -155,16 +145,16 @@ static void ps_run(Context &c, hipStream_t s, int n, const int *qa, const int *q
     try {
     for (int i = 0; i < n; i++) {
         long long add = 0;
-        if (S.node_j[qa[i]] < 0) add += ps_path_doubles(S, qa[i]);
-        if (qb[i] != qa[i] && S.node_j[qb[i]] < 0) add += ps_path_doubles(S, qb[i]);
+        if (S.node_j[qa[i]] < 0) add += ps_path_doubles(V, qa[i]);
+        if (qb[i] != qa[i] && S.node_j[qb[i]] < 0) add += ps_path_doubles(V, qb[i]);
         if (!pj.empty() && used + add > budget) flush(i);
         for (int q : { qa[i], qb[i] })
-            if (S.node_j[q] < 0) { S.node_j[q] = (int)nodes.size(); nodes.push_back(q); used += ps_path_doubles(S, q); }
+            if (S.node_j[q] < 0) { S.node_j[q] = (int)nodes.size(); nodes.push_back(q); used += ps_path_doubles(V, q); }
         pj.push_back(int2{ S.node_j[qa[i]], S.node_j[qb[i]] });
     }
     flush(n);
-    } catch (...) {                                         // (the maps are rebuilt by the next call)
-        S.node_j.clear(); S.serial = -1;
+    } catch (...) {                                         // (rec and node_j hold this call's marks: the next call sets both to -1 again)
+        S.node_j.clear(); S.gen = -1;
         throw;
     }
     std::vector<int> fmask;
@@ -190,45 +180,25 @@ static void ps_run(Context &c, hipStream_t s, int n, const int *qa, const int *q
     }
 }
 
-static int gate_refuse(int code, const char *msg) {
-    set_last_error(code, msg); fprintf(stderr, "aprilsam_amd: ERROR %d: %s\n", code, msg); fflush(stderr); return code;
-}
-
-// the checks aprilsam_amd_marginals makes (solver_marginals.inc.h), in the same order; 0 and the context, or the code
-static int ps_context(april_graph_cholesky_param_t *param, const char *who, Context *&out, const april_graph_t *g = nullptr) {
-    char msg[256];
-    if (g_shard.find(param) != g_shard.end()) { snprintf(msg, sizeof msg, "%s: sharded params are not supported", who); return gate_refuse(ERR_UNSUPPORTED, msg); }
-    auto it = g_ctx.find(param);
-    if (it != g_ctx.end()) drop_factor_if_toggled(*it->second, g);
-    if (it == g_ctx.end() || no_retained_factor(*it->second)) {
-        snprintf(msg, sizeof msg, "%s: no retained factor (no successful solver call since the param was created or last failed)", who);
-        return gate_refuse(-1, msg);
-    }
-    if (it->second->fact_asym) {
-        snprintf(msg, sizeof msg, "%s: the factorised graph holds factors with an asymmetric information matrix", who);
-        return gate_refuse(ERR_UNSUPPORTED, msg);
-    }
-    out = &*it->second;
-    return 0;
+// node ids against the factorised system and, for the calls that read states, the graph
+static const char *const PS_RANGE_MSG = "node id out of range of the factorised system (nodes added since the last solver call?)";
+static bool ps_ids_ok(const RetainedQuery &q, int n, const int *ids) {
+    const int N = q.N(), Ng = zsize(q.g->nodes);
+    for (int i = 0; i < n; i++) if (ids[i] < 0 || ids[i] >= N || ids[i] >= Ng) return false;
+    return true;
 }
 
 static int joint_any_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *qa, const int *qb, double *cov) {
-    (void)g;
     const char *who = "aprilsam_amd_marginals_joint_any";
-    if (!param || !cov || !qa || !qb || n < 0) return gate_refuse(ERR_BAD_GRAPH, "aprilsam_amd_marginals_joint_any: null argument or negative count");
-    ensure_device();
-    SlotLock lk(param, g);
-    Context *cp = nullptr;
-    if (int rc = ps_context(param, who, cp, g)) return rc;
-    Context &c = *cp;
-    const int N = c.fact_kind == FACT_EXTENDED ? c.inc_N : c.plan.N;
+    if (!param || !cov || !qa || !qb || n < 0) return refuse(ERR_BAD_GRAPH, who, "null argument or negative count");
+    RetainedQuery q(who, g, param);
+    if (int rc = q.admit()) return rc;
+    Context &c = q.c();
+    const int N = q.N();
     for (int i = 0; i < n; i++)
-        if (qa[i] < 0 || qa[i] >= N || qb[i] < 0 || qb[i] >= N)
-            return gate_refuse(ERR_BAD_GRAPH, "aprilsam_amd_marginals_joint_any: node id out of range of the factorised system (nodes added since the last solver call?)");
+        if (qa[i] < 0 || qa[i] >= N || qb[i] < 0 || qb[i] >= N) return q.refuse(ERR_BAD_GRAPH, "%s", PS_RANGE_MSG);
     if (n == 0) return 0;
-    hipStream_t s = take_stream(t_slot);
-    struct Park { int slot; hipStream_t s; ~Park() { park_stream(slot, s); } } park{ t_slot, s };
-    ps_run(c, s, n, qa, qb, nullptr);
+    ps_run(c, q.stream(), n, qa, qb, nullptr);
     memcpy(cov, c.ps.h_out.p, (size_t)8 * 36 * n);
     return 0;
 }
@@ -236,19 +206,15 @@ static int joint_any_impl(april_graph_t *g, april_graph_cholesky_param_t *param,
 static int gate_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *qa, const int *qb, const double *z, const double *W,
                      double *d2, double *Sout) {
     const char *who = "aprilsam_amd_gate_xyt";
-    if (!g || !param || !qa || !qb || !z || !W || !d2 || n < 0) return gate_refuse(ERR_BAD_GRAPH, "aprilsam_amd_gate_xyt: null argument or negative count");
-    ensure_device();
-    SlotLock lk(param, g);
-    Context *cp = nullptr;
-    if (int rc = ps_context(param, who, cp, g)) return rc;
-    Context &c = *cp;
-    const int N = c.fact_kind == FACT_EXTENDED ? c.inc_N : c.plan.N, Ng = zsize(g->nodes);
+    if (!g || !param || !qa || !qb || !z || !W || !d2 || n < 0) return refuse(ERR_BAD_GRAPH, who, "null argument or negative count");
+    RetainedQuery q(who, g, param);
+    if (int rc = q.admit()) return rc;
+    Context &c = q.c();
     for (int i = 0; i < n; i++) {
-        if (qa[i] < 0 || qa[i] >= N || qb[i] < 0 || qb[i] >= N || qa[i] >= Ng || qb[i] >= Ng)
-            return gate_refuse(ERR_BAD_GRAPH, "aprilsam_amd_gate_xyt: node id out of range of the factorised system (nodes added since the last solver call?)");
-        if (qa[i] == qb[i]) return gate_refuse(ERR_BAD_GRAPH, "aprilsam_amd_gate_xyt: a candidate joins a node to itself");
-        for (int k = 0; k < 3; k++) if (!std::isfinite(z[3 * i + k])) return gate_refuse(ERR_BAD_GRAPH, "aprilsam_amd_gate_xyt: a non-finite measurement");
-        for (int k = 0; k < 9; k++) if (!std::isfinite(W[9 * i + k])) return gate_refuse(ERR_BAD_GRAPH, "aprilsam_amd_gate_xyt: a non-finite information matrix");
+        if (!ps_ids_ok(q, 1, qa + i) || !ps_ids_ok(q, 1, qb + i)) return q.refuse(ERR_BAD_GRAPH, "%s", PS_RANGE_MSG);
+        if (qa[i] == qb[i]) return q.refuse(ERR_BAD_GRAPH, "a candidate joins a node to itself");
+        for (int k = 0; k < 3; k++) if (!std::isfinite(z[3 * i + k])) return q.refuse(ERR_BAD_GRAPH, "a non-finite measurement");
+        for (int k = 0; k < 9; k++) if (!std::isfinite(W[9 * i + k])) return q.refuse(ERR_BAD_GRAPH, "a non-finite information matrix");
     }
     for (int i = 0; i < n; i++) {                           // symmetric (mirror entries equal) and positive definite: a Cholesky factorisation
         const double *w = W + 9 * i;
@@ -259,7 +225,7 @@ static int gate_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int 
         ok = ok && p1 > 0;
         const double l11 = ok ? sqrt(p1) : 0, l21 = ok ? (w[7] - l20 * l10) / l11 : 0, p2 = w[8] - l20 * l20 - l21 * l21;
         ok = ok && p2 > 0;
-        if (!ok) return gate_refuse(ERR_UNSUPPORTED, "aprilsam_amd_gate_xyt: an information matrix that is not symmetric positive definite");
+        if (!ok) return q.refuse(ERR_UNSUPPORTED, "an information matrix that is not symmetric positive definite");
     }
     if (n == 0) return 0;
     std::vector<double> in((size_t)18 * n);
@@ -269,9 +235,7 @@ static int gate_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int 
         for (int k = 0; k < 3; k++) { q[k] = ns[qa[i]]->state[k]; q[3 + k] = ns[qb[i]]->state[k]; q[6 + k] = z[3 * i + k]; }
         for (int k = 0; k < 9; k++) q[9 + k] = W[9 * i + k];
     }
-    hipStream_t s = take_stream(t_slot);
-    struct Park { int slot; hipStream_t s; ~Park() { park_stream(slot, s); } } park{ t_slot, s };
-    ps_run(c, s, n, qa, qb, in.data());
+    ps_run(c, q.stream(), n, qa, qb, in.data());
     const double *o = c.ps.h_out.p + (size_t)36 * n;
     memcpy(d2, o, (size_t)8 * n);
     if (Sout) memcpy(Sout, o + n, (size_t)8 * 9 * n);
@@ -279,33 +243,18 @@ static int gate_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int 
 }
 
 // ---- polar gates ----------------------------------------------------------------------------------------------
-static int polar_refuse(int code, const char *who, const char *why) {
-    char msg[256];
-    snprintf(msg, sizeof msg, "%s: %s", who, why);
-    return gate_refuse(code, msg);
-}
-// node ids against the factorised system and the graph, as gate_xyt checks them
-static bool ps_ids_ok(const Context &c, const april_graph_t *g, int n, const int *q) {
-    const int N = c.fact_kind == FACT_EXTENDED ? c.inc_N : c.plan.N, Ng = zsize(g->nodes);
-    for (int i = 0; i < n; i++) if (q[i] < 0 || q[i] >= N || q[i] >= Ng) return false;
-    return true;
-}
-static const char *const PS_RANGE_MSG = "node id out of range of the factorised system (nodes added since the last solver call?)";
-
 // n candidates (kind, z, W) between a[i] and b[i]: every DISTINCT pair (a, b) is solved once, k_gate_polar reads a candidate's block through
 // its pair index.  What the checks can judge without the graph comes before the device is asked for.
 static int gate_polar_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *qa, const int *qb, const int *kind, const double *z,
                            const double *W, double *d2, double *Sout) {
     const char *who = "aprilsam_amd_gate_polar", *why = nullptr;
-    if (!g || !param || !qa || !qb || !kind || !z || !W || !d2 || n < 0) return polar_refuse(ERR_BAD_GRAPH, who, "null argument or negative count");
-    for (int i = 0; i < n; i++) if (qa[i] == qb[i]) return polar_refuse(ERR_BAD_GRAPH, who, "a candidate joins a node to itself");
-    if (int rc = polar_gate_args(n, kind, z, W, &why)) return polar_refuse(rc, who, why);
-    ensure_device();
-    SlotLock lk(param, g);
-    Context *cp = nullptr;
-    if (int rc = ps_context(param, who, cp, g)) return rc;
-    Context &c = *cp;
-    if (!ps_ids_ok(c, g, n, qa) || !ps_ids_ok(c, g, n, qb)) return polar_refuse(ERR_BAD_GRAPH, who, PS_RANGE_MSG);
+    if (!g || !param || !qa || !qb || !kind || !z || !W || !d2 || n < 0) return refuse(ERR_BAD_GRAPH, who, "null argument or negative count");
+    for (int i = 0; i < n; i++) if (qa[i] == qb[i]) return refuse(ERR_BAD_GRAPH, who, "a candidate joins a node to itself");
+    if (int rc = polar_gate_args(n, kind, z, W, &why)) return refuse(rc, who, "%s", why);
+    RetainedQuery q(who, g, param);
+    if (int rc = q.admit()) return rc;
+    Context &c = q.c();
+    if (!ps_ids_ok(q, n, qa) || !ps_ids_ok(q, n, qb)) return q.refuse(ERR_BAD_GRAPH, "%s", PS_RANGE_MSG);
     if (n == 0) return 0;
     std::vector<int> ua, ub, pidx((size_t)n);
     std::unordered_map<long long, int> seen;
@@ -325,8 +274,6 @@ static int gate_polar_impl(april_graph_t *g, april_graph_cholesky_param_t *param
         for (int k = 0; k < m; k++) q[7 + k] = z[2 * i + k];
         for (int k = 0; k < m * m; k++) q[9 + k] = W[4 * i + k];
     }
-    hipStream_t s = take_stream(t_slot);
-    struct Park { int slot; hipStream_t s; ~Park() { park_stream(slot, s); } } park{ t_slot, s };
     PathState &S = c.ps;
     PsTail tail;
     tail.extra = (size_t)6 * n;
@@ -336,7 +283,7 @@ static int gate_polar_impl(april_graph_t *g, april_graph_cholesky_param_t *param
         HIPCHECK(hipMemcpyAsync(S.d_pidx.p, pidx.data(), (size_t)4 * n, hipMemcpyHostToDevice, st));
         launch_polar_gate(st, k_gate_polar, n, false, n, (const double *)S.d_in.p, (const int *)S.d_pidx.p, (const double *)S.d_cov.p, S.h_out.p + (size_t)36 * np);
     };
-    ps_run(c, s, np, ua.data(), ub.data(), nullptr, &tail);
+    ps_run(c, q.stream(), np, ua.data(), ub.data(), nullptr, &tail);
     const double *o = S.h_out.p + (size_t)36 * np;
     memcpy(d2, o, (size_t)8 * n);
     if (Sout) memcpy(Sout, o + n, (size_t)8 * 4 * n);
@@ -351,16 +298,14 @@ static int associate_polar_impl(april_graph_t *g, april_graph_cholesky_param_t *
                                 int L, const int *landmarks, double gate1, double gate2, double *d2, int *best, double *d2_best, double *d2_second) {
     const char *who = "aprilsam_amd_associate_polar", *why = nullptr;
     if (!g || !param || !kind || !z || !W || !landmarks || !best || !d2_best || !d2_second || m < 0 || L < 0)
-        return polar_refuse(ERR_BAD_GRAPH, who, "null argument or negative count");
-    for (int l = 0; l < L; l++) if (landmarks[l] == observer) return polar_refuse(ERR_BAD_GRAPH, who, "the observer is among the landmarks");
-    if (!std::isfinite(gate1) || !std::isfinite(gate2)) return polar_refuse(ERR_BAD_GRAPH, who, "a non-finite gate");
-    if (int rc = polar_gate_args(m, kind, z, W, &why)) return polar_refuse(rc, who, why);
-    ensure_device();
-    SlotLock lk(param, g);
-    Context *cp = nullptr;
-    if (int rc = ps_context(param, who, cp, g)) return rc;
-    Context &c = *cp;
-    if (!ps_ids_ok(c, g, 1, &observer) || !ps_ids_ok(c, g, L, landmarks)) return polar_refuse(ERR_BAD_GRAPH, who, PS_RANGE_MSG);
+        return refuse(ERR_BAD_GRAPH, who, "null argument or negative count");
+    for (int l = 0; l < L; l++) if (landmarks[l] == observer) return refuse(ERR_BAD_GRAPH, who, "the observer is among the landmarks");
+    if (!std::isfinite(gate1) || !std::isfinite(gate2)) return refuse(ERR_BAD_GRAPH, who, "a non-finite gate");
+    if (int rc = polar_gate_args(m, kind, z, W, &why)) return refuse(rc, who, "%s", why);
+    RetainedQuery q(who, g, param);
+    if (int rc = q.admit()) return rc;
+    Context &c = q.c();
+    if (!ps_ids_ok(q, 1, &observer) || !ps_ids_ok(q, L, landmarks)) return q.refuse(ERR_BAD_GRAPH, "%s", PS_RANGE_MSG);
     if (m == 0) return 0;
     if (L == 0) {
         for (int i = 0; i < m; i++) { best[i] = -1; d2_best[i] = INFINITY; d2_second[i] = INFINITY; }
@@ -379,8 +324,6 @@ static int associate_polar_impl(april_graph_t *g, april_graph_cholesky_param_t *
     double *st = in.data() + (size_t)PG_OBS * m;
     for (int k = 0; k < 3; k++) st[k] = ns[observer]->state[k];
     for (int l = 0; l < L; l++) for (int k = 0; k < 3; k++) st[3 + 3 * (size_t)l + k] = ns[landmarks[l]]->state[k];
-    hipStream_t s = take_stream(t_slot);
-    struct Park { int slot; hipStream_t s; ~Park() { park_stream(slot, s); } } park{ t_slot, s };
     PathState &S = c.ps;
     const size_t nmat = d2 ? (size_t)m * L : 0;
     PsTail tail;
@@ -392,7 +335,7 @@ static int associate_polar_impl(april_graph_t *g, april_graph_cholesky_param_t *
         launch_polar_gate(sq, k_associate_polar, m, true, L, (const double *)S.d_in.p, (const double *)S.d_in.p + (size_t)PG_OBS * m, (const double *)S.d_cov.p,
                           gate1, gate2, d2 ? o : (double *)nullptr, (int2 *)(o + nmat + (size_t)2 * m), o + nmat, o + nmat + m);
     };
-    ps_run(c, s, L, qa.data(), landmarks, nullptr, &tail);
+    ps_run(c, q.stream(), L, qa.data(), landmarks, nullptr, &tail);
     const double *o = S.h_out.p + (size_t)36 * L;
     if (d2) memcpy(d2, o, 8 * nmat);
     memcpy(d2_best, o + nmat, (size_t)8 * m);
@@ -403,29 +346,18 @@ static int associate_polar_impl(april_graph_t *g, april_graph_cholesky_param_t *
     return (int)std::min<long long>(unavailable, 0x7fffffff);
 }
 
-// As marginals: a failed call only reads the param's plan and factor, records the error and leaves both in place.
-template <class F> static int ps_guard(F f) {
-    try { return f(); }
-    catch (const SolverError &e) { set_last_error(e.code, e.msg); fprintf(stderr, "aprilsam_amd: ERROR %d: %s\n", e.code, e.msg.c_str()); fflush(stderr); (void)hipGetLastError(); return e.code; }
-    catch (const std::bad_alloc &) { set_last_error(ERR_OOM, "host memory exhausted (std::bad_alloc)"); return ERR_OOM; }
-    catch (const std::exception &e) { set_last_error(ERR_INTERNAL, e.what()); return ERR_INTERNAL; }
-}
 int marginals_joint_any(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, double *cov) {
-    return ps_guard([&] { return joint_any_impl(g, param, n, a, b, cov); });
+    return query_guard([&] { return joint_any_impl(g, param, n, a, b, cov); });
 }
 int gate_xyt(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, const double *z, const double *W, double *d2, double *S) {
-    return ps_guard([&] { return gate_impl(g, param, n, a, b, z, W, d2, S); });
+    return query_guard([&] { return gate_impl(g, param, n, a, b, z, W, d2, S); });
 }
 int gate_polar(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, const int *kind, const double *z, const double *W,
                double *d2, double *S) {
-    return ps_guard([&] { return gate_polar_impl(g, param, n, a, b, kind, z, W, d2, S); });
+    return query_guard([&] { return gate_polar_impl(g, param, n, a, b, kind, z, W, d2, S); });
 }
 int associate_polar(april_graph_t *g, april_graph_cholesky_param_t *param, int observer, int m, const int *kind, const double *z, const double *W, int L,
                     const int *landmarks, double gate1, double gate2, double *d2, int *best, double *d2_best, double *d2_second) {
-    return ps_guard([&] { return associate_polar_impl(g, param, observer, m, kind, z, W, L, landmarks, gate1, gate2, d2, best, d2_best, d2_second); });
+    return query_guard([&] { return associate_polar_impl(g, param, observer, m, kind, z, W, L, landmarks, gate1, gate2, d2, best, d2_best, d2_second); });
 }
-long long path_solve_bytes(const april_graph_cholesky_param_t *param) {
-    SlotLock lk(param, nullptr);
-    auto it = g_ctx.find(param);
-    return it == g_ctx.end() ? -1 : 8 * it->second->ps.peak_doubles;
-}
+long long path_solve_bytes(const april_graph_cholesky_param_t *param) { return context_field(param, [](const Context &c) { return 8 * c.ps.peak_doubles; }); }

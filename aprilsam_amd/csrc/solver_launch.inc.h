@@ -356,11 +356,7 @@ template <class Enqueue> static void replay_captured(Context &c, Context::Captur
     HIPCHECK(hipGraphLaunch(g.exec, s));
 }
 
-long long graph_captures(const april_graph_cholesky_param_t *param) {
-    SlotLock lk(param, nullptr);
-    auto it = g_ctx.find(param);
-    return it == g_ctx.end() ? -1 : it->second->n_captures;
-}
+long long graph_captures(const april_graph_cholesky_param_t *param) { return context_field(param, [](const Context &c) { return c.n_captures; }); }
 
 // run the numeric phase, replaying a captured hipGraph when enabled.  timing: record the stage events c.ev; ktime: an event pair around every
 // kernel (neither is ever captured); the rest as NumericArgs (io_host: the other two do not apply)

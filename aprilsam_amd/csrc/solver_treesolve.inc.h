@@ -2,18 +2,17 @@
 // Contents: aprilsam_amd_solve / aprilsam_amd_marginals_cross / aprilsam_amd_relative_covariances: solves with the retained factor for
 // right-hand sides the caller supplies, as two whole-tree passes (treesolve.hip.h), and what is read from the solve of an anchor pose's
 // unit columns.  DESIGN.md section 18.
+// Admission, refusals, the guard and the structure the factor lives in: solver_query.inc.h (RetainedQuery, FactorView).
 // ------------------------------------------------------------------------------------------------------
-// The tables of the two passes for the structure the factor lives in (sel_fronts through ps_fronts: the plan, or the incremental
-// path's extended structure), kept against the factorisation counter: the fronts' rows in the work buffer, the children of every parent
-// block row (CSR, ascending front id: the order k_ts_assemble sums in), pos / pos_front / position -> node, and the work entries level
-// by level.  None of them depends on the number of columns: PsFront::buf holds a front's first row in the work buffer, the kernels take
-// the column count as an argument.
-static void ts_tables(Context &c, hipStream_t s) {
+// The tables of the two passes for the current view, kept against its generation: the fronts' rows in the work buffer, the children of
+// every parent block row (CSR, ascending front id: the order k_ts_assemble sums in), position -> node, and the work entries level by
+// level.  None of them depends on the number of columns: PsFront::buf holds a front's first row in the work buffer, the kernels take
+// the column count as an argument.  Returns pos | pos_front on the device (view_pos).
+static const int *ts_tables(Context &c, hipStream_t s) {
     TreeState &T = c.ts;
-    ps_fronts(c);
-    if (T.serial == c.fact_serial) return;
-    T.serial = -1;
-    const PathState &S = c.ps;
+    const FactorView &S = factor_view(c);
+    if (T.gen == S.gen) return view_pos(c, s);
+    T.gen = -1;
     const std::vector<SelFront> &fr = S.fr;
     const int nFr = (int)fr.size(), N = S.N;
     T.wrow.assign((size_t)nFr + 1, 0);
@@ -68,14 +67,12 @@ static void ts_tables(Context &c, hipStream_t s) {
         if (p < F.first || 3 * (p - F.first) + 3 > F.s) fail(ERR_INTERNAL, "aprilsam_amd_solve: node %d is not among its front's own rows", i);
     }
     // work entries, level by level (root first)
-    const int nLev = nFr ? *std::max_element(S.depth.begin(), S.depth.end()) + 1 : 0;
-    std::vector<std::vector<int>> lf((size_t)nLev);
-    for (int t = 0; t < nFr; t++) lf[S.depth[t]].push_back(t);
+    const int nLev = (int)S.lev.size();
     std::vector<int2> ent;
     T.lev.assign((size_t)nLev, TsLevel());
     for (int l = 0; l < nLev; l++) {
         TsLevel &L = T.lev[l];
-        const std::vector<int> &fl = lf[l];
+        const std::vector<int> &fl = S.lev[l];
         L.asm_off = (int)ent.size();
         for (int t : fl) for (int b = 0; b * TS_BAND < fr[t].s + fr[t].u; b++) ent.push_back(int2{ t, b });
         L.n_asm = (int)ent.size() - L.asm_off;
@@ -103,16 +100,17 @@ static void ts_tables(Context &c, hipStream_t s) {
         pf[t] = PsFront{ F.off, T.wrow[t], F.s, F.u, F.R, 0, F.parent, F.rel_begin, 0, 0 };
     }
     T.d_fr.need(std::max<size_t>(1, (size_t)nFr)); T.d_tf.need(tf.size()); T.d_ent.need(ent.size()); T.d_cptr.need(cptr.size()); T.d_cent.need(cent.size());
-    T.d_npos.need(npos.size()); T.d_pos.need(std::max<size_t>(1, S.i32.size()));
+    T.d_npos.need(npos.size());
+    const int *pos = view_pos(c, s);
     HIPCHECK(hipMemcpyAsync(T.d_fr.p, pf.data(), pf.size() * sizeof(PsFront), hipMemcpyHostToDevice, s));
     HIPCHECK(hipMemcpyAsync(T.d_tf.p, tf.data(), tf.size() * sizeof(TsFront), hipMemcpyHostToDevice, s));
     HIPCHECK(hipMemcpyAsync(T.d_ent.p, ent.data(), ent.size() * sizeof(int2), hipMemcpyHostToDevice, s));
     HIPCHECK(hipMemcpyAsync(T.d_cptr.p, cptr.data(), cptr.size() * 4, hipMemcpyHostToDevice, s));
     HIPCHECK(hipMemcpyAsync(T.d_cent.p, cent.data(), cent.size() * sizeof(TsKid), hipMemcpyHostToDevice, s));
     HIPCHECK(hipMemcpyAsync(T.d_npos.p, npos.data(), npos.size() * 4, hipMemcpyHostToDevice, s));
-    if (!S.i32.empty()) HIPCHECK(hipMemcpyAsync(T.d_pos.p, S.i32.data(), S.i32.size() * 4, hipMemcpyHostToDevice, s));
     HIPCHECK(hipStreamSynchronize(s));                      // (the host vectors go out of scope)
-    T.serial = c.fact_serial;
+    T.gen = S.gen;
+    return pos;
 }
 
 // the columns of one chunk: how many keep the work buffer under 1 GB / mem_cap_mb (ps_budget), a multiple of 16 and at least 16; option
@@ -129,7 +127,7 @@ static void ts_passes(Context &c, hipStream_t s, int mode, int ncol, const doubl
     TreeState &T = c.ts;
     const PsFront *fr = T.d_fr.p; const TsFront *tf = T.d_tf.p; const int2 *ent = T.d_ent.p;
     const double *pool = c.d_pool.p; double *buf = T.d_buf.p;
-    const long long n3 = 3ll * c.ps.N;
+    const long long n3 = 3ll * c.view.N;
     const unsigned ct = (unsigned)((ncol + SEL_T - 1) / SEL_T);
     auto waves = [&](int n) { return dim3((unsigned)((n + 3) / 4), ct); };
     const int nLev = (int)T.lev.size();
@@ -165,17 +163,15 @@ static void ts_buffer(Context &c, int w) {
 static int solve_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int mode, int nrhs, const double *B, double *X) {
     const char *who = "aprilsam_amd_solve";
     if (!param || !B || !X || nrhs < 1 || mode < APRILSAM_AMD_SOLVE_FULL || mode > APRILSAM_AMD_SOLVE_BACKWARD)
-        return gate_refuse(ERR_BAD_GRAPH, "aprilsam_amd_solve: null argument, mode outside 0..2 or nrhs < 1");
-    ensure_device();
-    SlotLock lk(param, g);
-    Context *cp = nullptr;
-    if (int rc = ps_context(param, who, cp, g)) return rc;
-    Context &c = *cp;
-    hipStream_t s = take_stream(t_slot);
-    struct Park { int slot; hipStream_t s; ~Park() { park_stream(slot, s); } } park{ t_slot, s };
-    ts_tables(c, s);
+        return refuse(ERR_BAD_GRAPH, who, "null argument, mode outside 0..2 or nrhs < 1");
+    RetainedQuery q(who, g, param);
+    if (int rc = q.admit()) return rc;
+    Context &c = q.c();
+    hipStream_t s = q.stream();
+    const int *pos = ts_tables(c, s);
     TreeState &T = c.ts;
-    const size_t n3 = (size_t)3 * c.ps.N;
+    const int N = q.N();
+    const size_t n3 = (size_t)3 * N;
     const int w = ts_chunk_cols(T, nrhs);
     ts_buffer(c, w);
     T.d_B.need(n3 * w); T.h_B.need(n3 * w); T.h_X.need(n3 * w);
@@ -190,7 +186,7 @@ static int solve_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int
         ts_passes(c, s, mode, nc, T.d_B.p);
         const long long nv = (long long)n3 * nc;
         hipLaunchKernelGGL(k_ts_store, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, s, (const PsFront *)T.d_fr.p, (const TsFront *)T.d_tf.p,
-                           (const int *)T.d_pos.p, (const int *)T.d_pos.p + c.ps.N, (const double *)T.d_buf.p, c.ps.N, nc, T.h_X.p);
+                           pos, pos + N, (const double *)T.d_buf.p, N, nc, T.h_X.p);
         HIPCHECK(hipGetLastError());
         HIPCHECK(hipStreamSynchronize(s));
         memcpy(out + n3 * c0, T.h_X.p, 8 * n3 * nc);
@@ -199,29 +195,23 @@ static int solve_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int
     return 0;
 }
 
-// what marginals_cross / relative_covariances share: the checks, the node list on the device (null: all nodes) and the FULL solve of
-// the anchor's three unit columns, left in the work buffer.  0 and the context, the stream and n, or the code.
-static int ts_anchor(april_graph_t *g, april_graph_cholesky_param_t *param, const char *who, int anchor, int &n, const int *nodes, bool need_graph,
-                     Context *&cp, hipStream_t s) {
-    char msg[256];
+// what marginals_cross / relative_covariances share: the admission of a fresh session and the checks, the node list on the device (null: all
+// nodes) and the FULL solve of the anchor's three unit columns, left in the work buffer.  0 with n and pos | pos_front on the device, or the code.
+static int ts_anchor(RetainedQuery &q, int anchor, int &n, const int *nodes, bool need_graph, const int *&pos) {
     // fixed nodes: not taken yet, neither in the graph nor in the factor at hand
-    if (int rc = refuse_fixed(who, g)) return rc;
-    if (int rc = ps_context(param, who, cp, g)) return rc;
-    Context &c = *cp;
-    if (!c.fact_fixed.empty()) {
-        snprintf(msg, sizeof msg, "%s: the retained factor was made with node %d fixed; this entry point does not take fixed nodes yet (DESIGN.md section 20)", who, c.fact_fixed[0]);
-        return gate_refuse(ERR_UNSUPPORTED, msg);
-    }
-    const int N = c.fact_kind == FACT_EXTENDED ? c.inc_N : c.plan.N, Ng = need_graph ? zsize(g->nodes) : N;
+    if (int rc = refuse_fixed(q.who, q.g)) return rc;
+    if (int rc = q.admit()) return rc;
+    Context &c = q.c();
+    if (!c.fact_fixed.empty())
+        return q.refuse(ERR_UNSUPPORTED, "the retained factor was made with node %d fixed; this entry point does not take fixed nodes yet (DESIGN.md section 20)", c.fact_fixed[0]);
+    const int N = q.N(), Ng = need_graph ? zsize(q.g->nodes) : N;
     bool ok = anchor >= 0 && anchor < N && anchor < Ng && (nodes || N <= Ng) && (!nodes || n >= 0);
     if (!nodes) n = N;
     for (int i = 0; ok && nodes && i < n; i++) ok = nodes[i] >= 0 && nodes[i] < N && nodes[i] < Ng;
-    if (!ok) {
-        snprintf(msg, sizeof msg, "%s: anchor or node id out of range of the factorised system (nodes added since the last solver call?), or a negative count", who);
-        return gate_refuse(ERR_BAD_GRAPH, msg);
-    }
+    if (!ok) return q.refuse(ERR_BAD_GRAPH, "anchor or node id out of range of the factorised system (nodes added since the last solver call?), or a negative count");
     if (n == 0) return 0;
-    ts_tables(c, s);
+    hipStream_t s = q.stream();
+    pos = ts_tables(c, s);
     TreeState &T = c.ts;
     const size_t n3 = (size_t)3 * N;
     ts_buffer(c, 3);
@@ -243,18 +233,15 @@ static int ts_anchor(april_graph_t *g, april_graph_cholesky_param_t *param, cons
 
 static int cross_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int anchor, int n, const int *nodes, double *cov) {
     const char *who = "aprilsam_amd_marginals_cross";
-    if (!param || !cov) return gate_refuse(ERR_BAD_GRAPH, "aprilsam_amd_marginals_cross: null argument");
-    ensure_device();
-    SlotLock lk(param, g);
-    hipStream_t s = take_stream(t_slot);
-    struct Park { int slot; hipStream_t s; ~Park() { park_stream(slot, s); } } park{ t_slot, s };
-    Context *cp = nullptr;
-    if (int rc = ts_anchor(g, param, who, anchor, n, nodes, false, cp, s)) return rc;
+    if (!param || !cov) return refuse(ERR_BAD_GRAPH, who, "null argument");
+    RetainedQuery q(who, g, param);
+    const int *pos = nullptr;
+    if (int rc = ts_anchor(q, anchor, n, nodes, false, pos)) return rc;
     if (n == 0) return 0;
-    Context &c = *cp; TreeState &T = c.ts;
+    TreeState &T = q.c().ts;
+    hipStream_t s = q.stream();
     hipLaunchKernelGGL(k_cross_extract, dim3((unsigned)((9ll * n + 255) / 256)), dim3(256), 0, s, n, nodes ? (const int *)T.d_nodes.p : (const int *)nullptr,
-                       (const PsFront *)T.d_fr.p, (const TsFront *)T.d_tf.p, (const int *)T.d_pos.p, (const int *)T.d_pos.p + c.ps.N, (const double *)T.d_buf.p,
-                       T.h_X.p);
+                       (const PsFront *)T.d_fr.p, (const TsFront *)T.d_tf.p, pos, pos + q.N(), (const double *)T.d_buf.p, T.h_X.p);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(s));
     memcpy(cov, T.h_X.p, (size_t)8 * 9 * n);
@@ -263,15 +250,13 @@ static int cross_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int
 
 static int relative_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int anchor, int n, const int *nodes, double *cov) {
     const char *who = "aprilsam_amd_relative_covariances";
-    if (!g || !param || !cov) return gate_refuse(ERR_BAD_GRAPH, "aprilsam_amd_relative_covariances: null argument");
-    ensure_device();
-    SlotLock lk(param, g);
-    hipStream_t s = take_stream(t_slot);
-    struct Park { int slot; hipStream_t s; ~Park() { park_stream(slot, s); } } park{ t_slot, s };
-    Context *cp = nullptr;
-    if (int rc = ts_anchor(g, param, who, anchor, n, nodes, true, cp, s)) return rc;
+    if (!g || !param || !cov) return refuse(ERR_BAD_GRAPH, who, "null argument");
+    RetainedQuery q(who, g, param);
+    const int *pos = nullptr;
+    if (int rc = ts_anchor(q, anchor, n, nodes, true, pos)) return rc;
     if (n == 0) return 0;
-    Context &c = *cp; TreeState &T = c.ts;
+    Context &c = q.c(); TreeState &T = c.ts;
+    hipStream_t s = q.stream();
     sel_ensure(c, s);                                       // Sig_aa, Sig_ii: the selected inversion's Sigma pool, as aprilsam_amd_marginals
     std::vector<double> st((size_t)3 * (n + 1));            // the anchor's state, then the listed nodes'
     april_graph_node_t **ns = (april_graph_node_t **)g->nodes->data;
@@ -280,8 +265,8 @@ static int relative_impl(april_graph_t *g, april_graph_cholesky_param_t *param, 
     T.d_st.need(st.size());
     HIPCHECK(hipMemcpyAsync(T.d_st.p, st.data(), 8 * st.size(), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_relative_cov, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, nodes ? (const int *)T.d_nodes.p : (const int *)nullptr, anchor,
-                       (const double *)T.d_st.p, (const double *)T.d_st.p + 3, (const PsFront *)T.d_fr.p, (const TsFront *)T.d_tf.p, (const int *)T.d_pos.p,
-                       (const int *)T.d_pos.p + c.ps.N, (const double *)T.d_buf.p, (const double *)c.d_sigma.p, T.h_X.p);
+                       (const double *)T.d_st.p, (const double *)T.d_st.p + 3, (const PsFront *)T.d_fr.p, (const TsFront *)T.d_tf.p, pos,
+                       pos + q.N(), (const double *)T.d_buf.p, (const double *)c.d_sigma.p, T.h_X.p);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(s));
     c.sel_serial = c.fact_serial;
@@ -290,22 +275,15 @@ static int relative_impl(april_graph_t *g, april_graph_cholesky_param_t *param, 
 }
 
 int tree_solve(april_graph_t *g, april_graph_cholesky_param_t *param, int mode, int nrhs, const double *B, double *X) {
-    return ps_guard([&] { return solve_impl(g, param, mode, nrhs, B, X); });
+    return query_guard([&] { return solve_impl(g, param, mode, nrhs, B, X); });
 }
 int marginals_cross(april_graph_t *g, april_graph_cholesky_param_t *param, int anchor, int n, const int *nodes, double *cov) {
-    return ps_guard([&] { return cross_impl(g, param, anchor, n, nodes, cov); });
+    return query_guard([&] { return cross_impl(g, param, anchor, n, nodes, cov); });
 }
 int relative_covariances(april_graph_t *g, april_graph_cholesky_param_t *param, int anchor, int n, const int *nodes, double *cov) {
-    return ps_guard([&] { return relative_impl(g, param, anchor, n, nodes, cov); });
+    return query_guard([&] { return relative_impl(g, param, anchor, n, nodes, cov); });
 }
-long long tree_solve_bytes(const april_graph_cholesky_param_t *param) {
-    SlotLock lk(param, nullptr);
-    auto it = g_ctx.find(param);
-    return it == g_ctx.end() ? -1 : it->second->ts.peak_bytes;
-}
+long long tree_solve_bytes(const april_graph_cholesky_param_t *param) { return context_field(param, [](const Context &c) { return c.ts.peak_bytes; }); }
 int factorised_nodes(const april_graph_cholesky_param_t *param) {
-    SlotLock lk(param, nullptr);
-    auto it = g_ctx.find(param);
-    if (it == g_ctx.end() || no_retained_factor(*it->second)) return -1;
-    return it->second->fact_kind == FACT_EXTENDED ? it->second->inc_N : it->second->plan.N;
+    return (int)context_field(param, [](const Context &c) { return no_retained_factor(c) ? -1 : retained_N(c); });
 }
