@@ -1,11 +1,11 @@
-// chordal.hip.h -- part of solver.hip.cpp (included after kernels.hip.h, whose TPB / REDUCE_PARTS it uses).
+// chordal.hip.h -- part of solver.hip.cpp (included after kernels.hip.h, whose TPB it uses).
 // Chordal initialisation of the poses: two linear least-squares problems on the graph's own sparsity pattern,
 // solved by the existing assembly, factorisation and back substitution.  Only what fills the contribution slots is new:
 //   k_chordal_rot      per factor: stage 1, unknown u_i = (cos, sin) of pose i          -> the slots k_linearize fills
 //   k_chordal_heading  per pose:   theta = atan2(s, c) of the stage-1 solution, |u|^2, degenerate flag
 //   k_chordal_trans    per factor: stage 2, unknown t_i with the headings held fixed     -> the same slots
 //   k_chordal_commit   per pose:   state = l_point = (t, theta)
-//   k_chordal_min      the smallest of n doubles (k_reduce sums): one value per workgroup, launched twice
+// (min |u|^2 is the min op of the one reducer, k_chordal_min / k_chordal_min_parts in kernels.hip.h: one stage up to REDUCE_SPLIT poses)
 // The third unknown of every pose is padding: a contributing factor writes 1.0 into element [2][2] of its diagonal blocks and zeros into
 // the rest of the third row and column, so the padded unknown comes out exactly 0 and the 2-unknown system is otherwise unchanged.  A factor
 // that fails a stage's condition writes zeros everywhere.  Every kernel is elementwise or a reduction of its own: no cross-workgroup flag.
@@ -122,22 +122,6 @@ __global__ void __launch_bounds__(TPB) k_chordal_commit(int N, const double *__r
     const double x = t ? t[e] : st[e], y = t ? t[e + 1] : st[e + 1], th = theta[i];
     st[e] = x; st[e + 1] = y; st[e + 2] = th;
     lp[e] = x; lp[e + 1] = y; lp[e + 2] = th;
-}
-
-// the smallest of n doubles: workgroup g takes one contiguous chunk -> out[g] (REDUCE_PARTS workgroups, then one over their results)
-__global__ void __launch_bounds__(TPB) k_chordal_min(int n, const double *__restrict__ in, double *__restrict__ out) {
-    __shared__ double s[TPB];
-    const int chunk = (n + (int)gridDim.x - 1) / (int)gridDim.x;
-    const int i0 = (int)blockIdx.x * chunk, i1 = min(n, i0 + chunk);
-    double m = __longlong_as_double(0x7ff0000000000000ll);
-    for (int i = i0 + (int)threadIdx.x; i < i1; i += TPB) m = fmin(m, in[i]);
-    s[threadIdx.x] = m;
-    __syncthreads();
-    for (int h = TPB / 2; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) s[threadIdx.x] = fmin(s[threadIdx.x], s[threadIdx.x + h]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[blockIdx.x] = s[0];
 }
 
 }  // namespace asam

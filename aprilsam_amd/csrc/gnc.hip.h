@@ -9,8 +9,9 @@
 //   par        GncPar: loss, c and mu.  mu is READ FROM MEMORY by every kernel below, so that a captured LM iteration is the same graph
 //              for every stage; k_gnc_set_mu (one thread, launched between stages, never captured) writes it
 // k_gnc_weight writes W_eff = w_mu(s) W0 into the slot before k_linearize_t reads it and k_gnc_cost replaces the candidates' terms of
-// k_lm_cost, as k_robust_weight / k_lm_cost_robust do for a factor's own loss.  One thread per candidate, plain loads and stores; the two
-// reductions (largest s, any weight strictly between 0 and 1) have the shape of k_reduce_parts / k_reduce.
+// k_lm_cost: the bodies k_robust_weight / k_lm_cost_robust run for a factor's own loss, with GncLoss for the policy.  One thread per
+// candidate, plain loads and stores; the two reductions (largest s, any weight strictly between 0 and 1) are k_gnc_max / k_gnc_max_parts,
+// the max op of the one reducer (kernels.hip.h).
 #pragma once
 #include "robust.h"
 
@@ -22,35 +23,28 @@ __global__ void k_gnc_set_mu(GncPar *__restrict__ par, double mu) {
     if (blockIdx.x == 0 && threadIdx.x == 0) par->mu = mu;
 }
 
+// the surrogate at the run's current mu: loss_weight_body / loss_term_body's policy for a candidate (robust.hip.h)
+struct GncLoss {
+    const GncPar *par;
+    __device__ __forceinline__ double weight(double s) const { return gnc_weight(par->loss, par->c, par->mu, s); }
+    __device__ __forceinline__ double rho(double s) const { return gnc_rho(par->loss, par->c, par->mu, s); }
+};
+
 // W_eff = w_mu(s) W0 into the candidates' slots of Wm, w -> gw; s where k_robust_weight takes it
 __global__ void __launch_bounds__(TPB) k_gnc_weight(int n, const int *__restrict__ gf, const double *__restrict__ gW0, const GncPar *__restrict__ par,
                                                     const int *__restrict__ fa, const int *__restrict__ fb, const double *__restrict__ Z,
                                                     const double *__restrict__ lp, const double *__restrict__ st, const double *__restrict__ upt,
                                                     double *__restrict__ Wm, double *__restrict__ gw) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int p = gf[i], a = fa[p], b = fb[p];
-    double w0[9];
-#pragma unroll
-    for (int k = 0; k < 9; k++) w0[k] = gW0[(size_t)9 * i + k];
-    const double *srca = b >= 0 ? lp + (size_t)3 * a : (upt ? upt + (size_t)3 * p : st + (size_t)3 * a);
-    const double w = gnc_weight(par->loss, par->c, par->mu, robust_s(p, a, b, Z, w0, srca, lp));
-#pragma unroll
-    for (int k = 0; k < 9; k++) Wm[(size_t)9 * p + k] = w * w0[k];
-    gw[i] = w;
+    if (i < n) loss_weight_body(i, gf, gW0, GncLoss{ par }, fa, fb, Z, lp, st, upt, Wm, gw);
 }
 
-// rho_mu(r^T W0 r) at st (the LM objective term) -> out[gf[i]]
+// rho_mu(r^T W0 r) at st (the LM objective term; the chi^2 convention never counts the surrogate) -> out[gf[i]]
 __global__ void __launch_bounds__(TPB) k_gnc_cost(int n, const int *__restrict__ gf, const double *__restrict__ gW0, const GncPar *__restrict__ par,
                                                   const int *__restrict__ fa, const int *__restrict__ fb, const double *__restrict__ Z,
                                                   const double *__restrict__ st, double *__restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int p = gf[i], a = fa[p], b = fb[p];
-    double w0[9];
-#pragma unroll
-    for (int k = 0; k < 9; k++) w0[k] = gW0[(size_t)9 * i + k];
-    out[p] = gnc_rho(par->loss, par->c, par->mu, robust_s(p, a, b, Z, w0, st + (size_t)3 * a, st));
+    if (i < n) loss_term_body<false>(i, gf, gW0, GncLoss{ par }, fa, fb, Z, st, out);
 }
 
 // what = 0: s at st -> out[i] (the start: its maximum is s_max)
@@ -68,37 +62,6 @@ __global__ void __launch_bounds__(TPB) k_gnc_probe(int n, const int *__restrict_
     if (what == 0) { out[i] = s; return; }
     const double w = gnc_weight(par->loss, par->c, par->mu, s);
     out[i] = (w == 0.0 || w == 1.0) ? 0.0 : 1.0;
-}
-
-// the larger of two, a NaN winning over everything (as numpy's max)
-__device__ __forceinline__ double gnc_max2(double a, double b) { return (b > a || b != b) ? b : a; }
-// out[0] = max of n >= 1 doubles (k_reduce's shape)
-__global__ void __launch_bounds__(1024) k_gnc_max(int n, const double *__restrict__ in, double *__restrict__ out) {
-    __shared__ double s[1024];
-    double acc = in[0];
-    for (int i = threadIdx.x; i < n; i += 1024) acc = gnc_max2(acc, in[i]);
-    s[threadIdx.x] = acc;
-    __syncthreads();
-    for (int h = 512; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) s[threadIdx.x] = gnc_max2(s[threadIdx.x], s[threadIdx.x + h]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = s[0];
-}
-// ... of many (k_reduce_parts' shape): workgroup j -> parts[j], the maximum of its contiguous chunk (in[0] where the chunk is empty)
-__global__ void __launch_bounds__(TPB) k_gnc_max_parts(int n, const double *__restrict__ in, double *__restrict__ parts) {
-    __shared__ double s[TPB];
-    const int chunk = (n + (int)gridDim.x - 1) / (int)gridDim.x;
-    const int i0 = (int)blockIdx.x * chunk, i1 = min(n, i0 + chunk);
-    double acc = in[0];
-    for (int i = i0 + (int)threadIdx.x; i < i1; i += TPB) acc = gnc_max2(acc, in[i]);
-    s[threadIdx.x] = acc;
-    __syncthreads();
-    for (int h = TPB / 2; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) s[threadIdx.x] = gnc_max2(s[threadIdx.x], s[threadIdx.x + h]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) parts[blockIdx.x] = s[0];
 }
 
 // the end of the call: w_mu(s) at st -> out[i], inlier (s <= c^2) as 1.0 / 0.0 -> out[n + i], and the plain W back into the slot

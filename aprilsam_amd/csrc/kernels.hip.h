@@ -22,7 +22,8 @@
 //   k_backsolve_gemv / k_backsolve_t   the same for all other fronts, 32 columns at a time, level by level
 //   k_update_states    state = l_point + dx, theta wrap, NaN guard (april_graph_xyt.c:302-314); on the batch path this
 //                      rides on the back substitution (backsolve_finish)
-//   k_chi2 / k_reduce (+ k_reduce_parts)  chi^2 with the 1/2-on-xyt convention (april_graph.c:79-98), deterministic sum
+//   k_chi2             factor_term<true>: chi^2 with the 1/2-on-xyt convention (april_graph.c:79-98); k_lm_cost (lm.hip.h) is factor_term<false>
+//   k_reduce / k_gnc_max / k_chordal_min (+ their _parts)   reduce_one / reduce_parts over sum, max, min: the one deterministic reducer
 //   k_scatter_host     blocks of host-evaluated (foreign-type) factors into the contribution slots
 //   k_pack_update      packed Schur update of a front for the multi-GPU exchange
 //   k_inc_prologue / k_inc_one / front_update_body   the incremental path: patches + linearisation of the new factors, a whole small
@@ -492,13 +493,14 @@ __global__ void __launch_bounds__(TPB) k_debug_dest(int nd, const DestRec *__res
     out[e] = acc;
 }
 
-// per-factor chi^2 at `st` (april_graph.c:79-98: 0.5 r'Wr for xyt via state_eval, r'Wr otherwise)
-__global__ void __launch_bounds__(TPB) k_chi2(int F, const int *__restrict__ fa, const int *__restrict__ fb,
-                                              const double *__restrict__ Z, const double *__restrict__ Wm,
-                                              const double *__restrict__ st, double *__restrict__ out) {
-    int f = blockIdx.x * blockDim.x + threadIdx.x;
+// One packed xyt / xytpos factor's term of the objective at `st`: r'Wr of slot f -> out[f] (0 for a null slot).  HALF_BINARY: the chi^2
+// convention, 0.5 r'Wr for xyt via state_eval (april_graph.c:79-98); without it the LM convention, r'Wr for every type.  The table of
+// every family's term under both conventions is DESIGN.md section 27
+template <bool HALF_BINARY>
+__device__ __forceinline__ void factor_term(int F, const int *fa, const int *fb, const double *Z, const double *Wm, const double *st, double *out) {
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= F) return;
-    int a = fa[f], b = fb[f];
+    const int a = fa[f], b = fb[f];
     if (a < 0) { out[f] = 0; return; }
     double w[9], z[3], J0[9], J1[9], r[3], pa[3], pb[3] = { 0, 0, 0 };
 #pragma unroll
@@ -510,41 +512,73 @@ __global__ void __launch_bounds__(TPB) k_chi2(int F, const int *__restrict__ fa,
         for (int k = 0; k < 3; k++) pb[k] = st[(size_t)3 * b + k];
     }
     factor_residual(b >= 0, pa, pb, z, J0, J1, r);
-    double c = rtWr(w, r);
-    out[f] = (b >= 0) ? 0.5 * c : c;
+    const double c = rtWr(w, r);
+    out[f] = (HALF_BINARY && b >= 0) ? 0.5 * c : c;
+}
+// per-factor chi^2 at `st` (k_lm_cost, lm.hip.h, is the other convention)
+__global__ void __launch_bounds__(TPB) k_chi2(int F, const int *__restrict__ fa, const int *__restrict__ fb,
+                                              const double *__restrict__ Z, const double *__restrict__ Wm,
+                                              const double *__restrict__ st, double *__restrict__ out) {
+    factor_term<true>(F, fa, fb, Z, Wm, st, out);
 }
 
-// deterministic sum of n doubles into out[0]: ONE workgroup, fixed strided partials + fixed tree
-__global__ void __launch_bounds__(1024) k_reduce(int n, const double *__restrict__ in, double *__restrict__ out) {
+// Deterministic reductions of n doubles.  An op gives the value an accumulator starts from and folds one more value into it:
+//   sum   0, +                                        every chi^2, every LM scalar (the bits of both depend on the shapes below)
+//   max   in[0] (so n >= 1), a NaN wins over everything as in numpy's max      GNC: s_max, the "not all binary" flag
+//   min   +inf, fmin, which ignores a NaN             chordal initialisation: min |u|^2
+// (into() takes references and the bodies below take plain pointers so that each named kernel compiles to the code it had when it was
+// written out by hand: the wrappers' __restrict__ carries through the inlining)
+struct ReduceSum {
+    static __device__ __forceinline__ double seed(const double *) { return 0; }
+    static __device__ __forceinline__ void into(double &a, const double &b) { a += b; }
+};
+struct ReduceMax {
+    static __device__ __forceinline__ double seed(const double *in) { return in[0]; }
+    static __device__ __forceinline__ double max2(double a, double b) { return (b > a || b != b) ? b : a; }
+    static __device__ __forceinline__ void into(double &a, const double &b) { a = max2(a, b); }
+};
+struct ReduceMin {
+    static __device__ __forceinline__ double seed(const double *) { return __longlong_as_double(0x7ff0000000000000ll); }
+    static __device__ __forceinline__ void into(double &a, const double &b) { a = fmin(a, b); }
+};
+// ... into out[0]: ONE workgroup of 1024 threads, fixed strided partials + fixed tree
+template <class Op> __device__ __forceinline__ void reduce_one(int n, const double *in, double *out) {
     __shared__ double s[1024];
-    double acc = 0;
-    for (int i = threadIdx.x; i < n; i += 1024) acc += in[i];
+    double acc = Op::seed(in);
+    for (int i = threadIdx.x; i < n; i += 1024) Op::into(acc, in[i]);
     s[threadIdx.x] = acc;
     __syncthreads();
     for (int h = 512; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) s[threadIdx.x] += s[threadIdx.x + h];
+        if ((int)threadIdx.x < h) Op::into(s[threadIdx.x], s[threadIdx.x + h]);
         __syncthreads();
     }
     if (threadIdx.x == 0) out[0] = s[0];
 }
 // ... of MANY doubles (the 10^6-pose lattice has 3 x 10^6 factors: one workgroup read them at 19 GB/s, 1.3 ms -- fifteen times k_chi2 itself):
-// REDUCE_PARTS workgroups sum one contiguous chunk each into parts[], k_reduce adds the parts.  The chunks and both trees depend on n alone, so the
-// sum is as reproducible as the one-stage form; sums of at most REDUCE_SPLIT terms keep that form (and their bits: M3500, the incremental demo).
+// REDUCE_PARTS workgroups of TPB threads reduce one contiguous chunk each into parts[] (the seed where the chunk is empty), reduce_one
+// combines the parts.  The chunks and both trees depend on n alone, so the result is as reproducible as the one-stage form; reductions of at
+// most REDUCE_SPLIT terms keep that form (and their bits: M3500, the incremental demo).  The split rule is enqueue_reduce's (solver_launch.inc.h)
 constexpr int REDUCE_SPLIT = 1 << 16, REDUCE_PARTS = 1024;
-__global__ void __launch_bounds__(TPB) k_reduce_parts(int n, const double *__restrict__ in, double *__restrict__ parts) {
+template <class Op> __device__ __forceinline__ void reduce_parts(int n, const double *in, double *parts) {
     __shared__ double s[TPB];
     const int chunk = (n + (int)gridDim.x - 1) / (int)gridDim.x;
     const int i0 = (int)blockIdx.x * chunk, i1 = min(n, i0 + chunk);
-    double acc = 0;
-    for (int i = i0 + (int)threadIdx.x; i < i1; i += TPB) acc += in[i];
+    double acc = Op::seed(in);
+    for (int i = i0 + (int)threadIdx.x; i < i1; i += TPB) Op::into(acc, in[i]);
     s[threadIdx.x] = acc;
     __syncthreads();
     for (int h = TPB / 2; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) s[threadIdx.x] += s[threadIdx.x + h];
+        if ((int)threadIdx.x < h) Op::into(s[threadIdx.x], s[threadIdx.x + h]);
         __syncthreads();
     }
     if (threadIdx.x == 0) parts[blockIdx.x] = s[0];
 }
+__global__ void __launch_bounds__(1024) k_reduce(int n, const double *__restrict__ in, double *__restrict__ out) { reduce_one<ReduceSum>(n, in, out); }
+__global__ void __launch_bounds__(TPB) k_reduce_parts(int n, const double *__restrict__ in, double *__restrict__ parts) { reduce_parts<ReduceSum>(n, in, parts); }
+__global__ void __launch_bounds__(1024) k_gnc_max(int n, const double *__restrict__ in, double *__restrict__ out) { reduce_one<ReduceMax>(n, in, out); }
+__global__ void __launch_bounds__(TPB) k_gnc_max_parts(int n, const double *__restrict__ in, double *__restrict__ parts) { reduce_parts<ReduceMax>(n, in, parts); }
+__global__ void __launch_bounds__(1024) k_chordal_min(int n, const double *__restrict__ in, double *__restrict__ out) { reduce_one<ReduceMin>(n, in, out); }
+__global__ void __launch_bounds__(TPB) k_chordal_min_parts(int n, const double *__restrict__ in, double *__restrict__ parts) { reduce_parts<ReduceMin>(n, in, parts); }
 
 // ------------------------------------------------------------------------------------------------------
 // gather-assembly of block columns [bc0, bc1) of front t into dst (column-major, leading dimension ld):

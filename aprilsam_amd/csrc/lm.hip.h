@@ -1,10 +1,11 @@
 // lm.hip.h -- part of solver.hip.cpp (included after kernels.hip.h and maxmix.hip.h, whose factor_residual / rtWr it uses).
 // Levenberg-Marquardt optimisation on the device.  One LM iteration is the existing numeric phase with its state
 // update pointed at a trial buffer (enqueue_numeric's st_dest), followed by the kernels below:
-//   k_lm_cost (+ k_lm_cost_mixture)  per factor r^T W r at the trial states (no 0.5; max factors: min_k r^T W_k r + c_k)
+//   k_lm_cost                        per factor r^T W r at the trial states (no 0.5); the other families' terms replace theirs in place, each
+//                                    from its own header -- enqueue_objective's LM convention (solver_launch.inc.h)
 //   k_lm_model                       per factor delta^T W (2 r - delta), delta = J_a h_a + J_b h_b, at the l_points (= x)
 //   k_lm_norms                       per node |h_i|^2 and |x_i|^2
-//   (k_reduce / k_reduce_parts sum each array into its own LmScalars field, the split rule of device_chi2)
+//   (enqueue_reduce sums each array into its own LmScalars field: k_reduce, behind k_reduce_parts above REDUCE_SPLIT terms)
 //   k_lm_decide                      one thread: accept / reject (Nielsen), lambda, nu, stop tests, latch, counters, trace row; a
 //                                    dependency time-out latches LM_FAULT instead (the call fails with ERR_DEP_TIMEOUT)
 //   k_lm_commit                      per node: x <- trial if accepted, d_lambda <- lambda, trial <- x, failure record cleared
@@ -27,49 +28,10 @@ struct LmScalars {
     int fault[4];                        // the failure record of the iteration that timed out (LM_FAULT), as d_bad held it
 };
 
-// per factor r^T W r at st (k_chi2's residual without the 1/2 on xyt terms)
+// per factor r^T W r at st (k_chi2 without the 1/2 on xyt terms: the other convention of factor_term, kernels.hip.h)
 __global__ void __launch_bounds__(TPB) k_lm_cost(int F, const int *__restrict__ fa, const int *__restrict__ fb, const double *__restrict__ Z,
                                                  const double *__restrict__ Wm, const double *__restrict__ st, double *__restrict__ out) {
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= F) return;
-    const int a = fa[f], b = fb[f];
-    if (a < 0) { out[f] = 0; return; }
-    double w[9], z[3], J0[9], J1[9], r[3], pa[3], pb[3] = { 0, 0, 0 };
-#pragma unroll
-    for (int k = 0; k < 9; k++) w[k] = Wm[(size_t)9 * f + k];
-#pragma unroll
-    for (int k = 0; k < 3; k++) { z[k] = Z[(size_t)3 * f + k]; pa[k] = st[(size_t)3 * a + k]; }
-    if (b >= 0) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) pb[k] = st[(size_t)3 * b + k];
-    }
-    factor_residual(b >= 0, pa, pb, z, J0, J1, r);
-    out[f] = rtWr(w, r);
-}
-
-// one thread per max factor: min_k (r_k^T W_k r_k + c_k) at st -> out[mf[m]] (the score k_select_mixture minimises)
-__global__ void __launch_bounds__(TPB) k_lm_cost_mixture(int M, const int *__restrict__ mf, const int *__restrict__ mk, const double *__restrict__ mz,
-                                                         const double *__restrict__ mW, const double *__restrict__ mc, const int *__restrict__ fa,
-                                                         const int *__restrict__ fb, const double *__restrict__ st, double *__restrict__ out) {
-    const int m = blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= M) return;
-    const int p = mf[m], k0 = mk[m], k1 = mk[m + 1];
-    const int a = fa[p], b = fb[p];
-    double pa[3], pb[3], J0[9], J1[9];
-#pragma unroll
-    for (int k = 0; k < 3; k++) { pa[k] = st[(size_t)3 * a + k]; pb[k] = st[(size_t)3 * b + k]; }
-    double sbest = 0;
-    for (int k = k0; k < k1; k++) {
-        double z[3], w[9], r[3];
-#pragma unroll
-        for (int i = 0; i < 3; i++) z[i] = mz[(size_t)3 * k + i];
-#pragma unroll
-        for (int i = 0; i < 9; i++) w[i] = mW[(size_t)9 * k + i];
-        factor_residual(true, pa, pb, z, J0, J1, r);
-        const double s = rtWr(w, r) + mc[k];
-        if (k == k0 || s < sbest) sbest = s;
-    }
-    out[p] = sbest;
+    factor_term<false>(F, fa, fb, Z, Wm, st, out);
 }
 
 // per factor delta^T W (2 r - delta) at lp, delta = J_a h_a + J_b h_b (xytpos: J = I); h = dx in node order.  Z / Wm: the slots as the

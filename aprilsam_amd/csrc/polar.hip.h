@@ -7,8 +7,8 @@
 //   pz[2p]     the measurement (one or two entries used)
 //   pW[4p]     its information matrix (RANGE / BEARING: entry 0; RANGE_BEARING: 2 x 2 row-major)
 // k_polar_slot writes the point-dependent xyt slot (z_eff, W_eff: polar.h) before k_linearize_t reads it, so the linearisation kernel (and
-// its VGPR budget), assembly, factorisation and solves stay as they are; k_chi2_polar and k_lm_cost_polar replace the polar factors' terms of
-// k_chi2 / k_lm_cost before the sums.  The formulas are polar.h's, shared with the host.  One thread per polar factor, plain loads and
+// its VGPR budget), assembly, factorisation and solves stay as they are; k_chi2_polar replaces the polar factors' terms of
+// k_chi2 / k_lm_cost before the sums (one term under both conventions).  The formulas are polar.h's, shared with the host.  One thread per polar factor, plain loads and
 // stores, no flags.
 #pragma once
 #include "polar.h"
@@ -46,23 +46,10 @@ __global__ void __launch_bounds__(TPB) k_polar_slot(int P, const int *__restrict
 }
 
 // one thread per polar factor: r_p' Wp r_p at st -> out[pf[p]] (april_graph_chi2: the full term, the rule of every type but xyt; the LM
-// objective counts the same term: k_lm_cost_polar below, at the state array LM gives it)
+// objective counts the same term, so both conventions launch this kernel, LM at the state array it is evaluating)
 __global__ void __launch_bounds__(TPB) k_chi2_polar(int P, const int *__restrict__ pf, const int *__restrict__ pkind, const double *__restrict__ pz,
                                                     const double *__restrict__ pW, const int *__restrict__ fa, const int *__restrict__ fb,
                                                     const double *__restrict__ st, double *__restrict__ out) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= P) return;
-    const int f = pf[p];
-    const double z[2] = { pz[(size_t)2 * p], pz[(size_t)2 * p + 1] };
-    double w[4], q0, q1, zh2;
-#pragma unroll
-    for (int i = 0; i < 4; i++) w[i] = pW[(size_t)4 * p + i];
-    polar_q(st, fa[f], fb[f], &q0, &q1, &zh2);
-    out[f] = polar_cost(pkind[p], z, w, q0, q1);
-}
-__global__ void __launch_bounds__(TPB) k_lm_cost_polar(int P, const int *__restrict__ pf, const int *__restrict__ pkind, const double *__restrict__ pz,
-                                                       const double *__restrict__ pW, const int *__restrict__ fa, const int *__restrict__ fb,
-                                                       const double *__restrict__ st, double *__restrict__ out) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= P) return;
     const int f = pf[p];

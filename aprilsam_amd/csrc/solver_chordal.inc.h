@@ -142,9 +142,8 @@ static int initialize_chordal_impl(april_graph_t *g, april_graph_cholesky_param_
     std::vector<double> raw;
     if (rot_out || raw_out) { raw.resize((size_t)6 * N); HIPCHECK(hipMemcpyAsync(raw.data(), gp.d_dx.p, (size_t)24 * N, hipMemcpyDeviceToHost, s)); }
     hipLaunchKernelGGL(k_chordal_heading, dim3((N + TPB - 1) / TPB), dim3(TPB), 0, s, N, (const double *)gp.d_dx.p, (const double *)gp.d_state.p, theta, terms, terms + N);
-    lm_reduce(s, N, terms + N, parts, scal + 2);
-    hipLaunchKernelGGL(k_chordal_min, dim3(REDUCE_PARTS), dim3(TPB), 0, s, N, (const double *)terms, parts);
-    hipLaunchKernelGGL(k_chordal_min, dim3(1), dim3(TPB), 0, s, REDUCE_PARTS, (const double *)parts, scal + 3);
+    enqueue_reduce(REDUCE_SUM, s, N, terms + N, parts, scal + 2);
+    enqueue_reduce(REDUCE_MIN, s, N, terms, parts, scal + 3);
     HIPCHECK(hipGetLastError());
 
     // stage 2: positions with the headings held fixed

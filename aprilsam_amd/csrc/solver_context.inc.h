@@ -879,26 +879,6 @@ static void rewind_epoch(Context &c, hipStream_t s, long long phases) {
     c.epoch_steps = phases;
 }
 
-static void enqueue_chi2_polar(GraphPack &gp, hipStream_t s);      // solver_launch.inc.h (launch_polar)
-static void enqueue_chi2_gaussian(GraphPack &gp, hipStream_t s);   // solver_launch.inc.h (launch_gaussian)
-static double device_chi2(GraphPack &gp) {     // chi^2 at d_state; synchronises the stream
-    hipStream_t s = gp.stream;
-    if (gp.F == 0) return 0;
-    hipLaunchKernelGGL(k_chi2, dim3((gp.F + TPB - 1) / TPB), dim3(TPB), 0, s, gp.F, gp.d_fa.p, gp.d_fb.p, gp.d_z.p, gp.d_W.p, gp.d_state.p, gp.d_chi2f.p);
-    enqueue_chi2_mixture(gp, s);       // (max factors: their terms selected at the states, in place -- the sums below keep their order)
-    enqueue_chi2_robust(gp, s);        // (robust factors: rho(s) in place of s)
-    enqueue_chi2_polar(gp, s);         // (polar factors: r_p' Wp r_p in place of the slot's term)
-    enqueue_chi2_gaussian(gp, s);      // (dense Gaussian factors: c0 - 2 eta' delta + delta' Lambda delta on the factor's first entry)
-    if (gp.F > REDUCE_SPLIT) {         // (the parts live behind the F_cap per-factor terms: upload_factors)
-        double *parts = gp.d_chi2f.p + gp.F_cap;
-        hipLaunchKernelGGL(k_reduce_parts, dim3(REDUCE_PARTS), dim3(TPB), 0, s, gp.F, gp.d_chi2f.p, parts);
-        hipLaunchKernelGGL(k_reduce, dim3(1), dim3(1024), 0, s, REDUCE_PARTS, parts, gp.d_scalar.p);
-    } else hipLaunchKernelGGL(k_reduce, dim3(1), dim3(1024), 0, s, gp.F, gp.d_chi2f.p, gp.d_scalar.p);
-    HIPCHECK(hipMemcpyAsync(gp.h_scalar.p, gp.d_scalar.p, 8, hipMemcpyDeviceToHost, s));
-    HIPCHECK(hipStreamSynchronize(s));
-    return gp.h_scalar.p[0];
-}
-
 // Options are baked into the launch tables at plan time (build_level: small / panel / big classification, tile counts,
 // diagonal-block slots) AND read again when the kernels are enqueued or captured into a hipGraph.  Every change of an option
 // that touches either (api_set_option bumps g_opt_epoch) therefore forces a re-plan and a re-capture on every param.

@@ -3,7 +3,7 @@
 //
 // Set-up is optimize_lm's (solver_lm.inc.h: lm_refuse_graph, resident_begin_impl, lm_enter).  The candidates' table goes to the device
 // once; from then until the call returns gp.gc_n > 0, which makes every linearisation weight them (enqueue_gnc_weight) and every
-// objective count rho_mu for them (lm_enqueue_cost).  A stage = k_gnc_set_mu, lm_enqueue_start, lm_iterate: the captured LM iteration is
+// objective of the LM convention count rho_mu for them (enqueue_objective).  A stage = k_gnc_set_mu, lm_enqueue_start, lm_iterate: the captured LM iteration is
 // the same graph for every stage, mu being read from device memory.  The host synchronises once for s_max, once per check_every
 // iterations, and for TLS once per stage (the "not all binary" flag); the per-stage entry objectives stay on the device until the end.
 
@@ -20,14 +20,6 @@ static const char *gnc_bad_options(const aprilsam_amd_gnc_opts_t *o) {
     if (!(o->mu_step > 1) || !std::isfinite(o->mu_step)) return "mu_step must be finite and > 1";
     if (o->max_stages < 1) return "max_stages must be >= 1";
     return lm_bad_options(&o->lm);
-}
-
-// max of n >= 1 doubles at `in` into *out: lm_reduce's split rule
-static void gnc_reduce_max(hipStream_t s, int n, const double *in, double *parts, double *out) {
-    if (n > REDUCE_SPLIT) {
-        hipLaunchKernelGGL(k_gnc_max_parts, dim3(REDUCE_PARTS), dim3(TPB), 0, s, n, in, parts);
-        hipLaunchKernelGGL(k_gnc_max, dim3(1), dim3(1024), 0, s, REDUCE_PARTS, (const double *)parts, out);
-    } else hipLaunchKernelGGL(k_gnc_max, dim3(1), dim3(1024), 0, s, n, in, out);
 }
 
 static int optimize_gnc_impl(april_graph_t *g, april_graph_cholesky_param_t *param, const aprilsam_amd_gnc_opts_t *o, int n, const int *cand,
@@ -72,7 +64,7 @@ static int optimize_gnc_impl(april_graph_t *g, april_graph_cholesky_param_t *par
     const int *fa = gp.d_fa.p, *fb = gp.d_fb.p; const double *Z = gp.d_z.p, *st = gp.d_state.p;
     // the start: s_max over the candidates at the incoming states
     launch_gnc(s, gp, k_gnc_probe, 0, fa, fb, Z, st, out);
-    gnc_reduce_max(s, n, out, out + o_parts, out + o_scal);
+    enqueue_reduce(REDUCE_MAX, s, n, out, out + o_parts, out + o_scal);
     HIPCHECK(hipMemcpyAsync(stg, out + o_scal, 8, hipMemcpyDeviceToHost, s));
     HIPCHECK(hipStreamSynchronize(s));
     const double s_max = stg[0];
@@ -91,7 +83,7 @@ static int optimize_gnc_impl(april_graph_t *g, april_graph_cholesky_param_t *par
         bool done = mu == 1.0;
         if (tls) {        // every weight exactly 0 or 1 at the stage's final x?
             launch_gnc(s, gp, k_gnc_probe, 1, fa, fb, Z, st, out);
-            gnc_reduce_max(s, n, out, out + o_parts, out + o_scal + 1);
+            enqueue_reduce(REDUCE_MAX, s, n, out, out + o_parts, out + o_scal + 1);
             HIPCHECK(hipMemcpyAsync(stg, out + o_scal + 1, 8, hipMemcpyDeviceToHost, s));
             HIPCHECK(hipStreamSynchronize(s));
             done = stg[0] == 0.0;

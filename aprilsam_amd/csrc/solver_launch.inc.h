@@ -184,44 +184,66 @@ static void enqueue_factor_level(Context &c, const LevelPlan &L, hipStream_t s, 
     }
 }
 
-// The kernels of gnc.hip.h that run one thread per candidate of an aprilsam_amd_optimize_gnc run (gp.gc_n of them): `a` is what follows the
-// table (n, gf, gW0, par) in the kernel's arguments
+// ---- the factor families: one launcher each, and each family's hooks side by side ----------------------------------------------------
+// A family rides on the plain xyt / xytpos slots with up to three hooks, each one launch over the family's table and none for a pack
+// without it: what k_linearize_t reads from the slot BEFORE the linearisation, what replaces the contributions it wrote AFTER it, and the
+// TERM that replaces the slot's term of the objective.
+//   family            table                launcher          before              after              term (CHI2 / LM)
+//   max-mixture       gp.d_mx_*            launch_mixture    k_select_mixture    --                 k_chi2_mixture / k_lm_cost_mixture
+//   robust            gp.d_rb_*            launch_robust     k_robust_weight     --                 k_chi2_robust / k_lm_cost_robust
+//   GNC candidates    gp.d_gc_* (gc_n)     launch_gnc        k_gnc_weight        --                 -- / k_gnc_cost
+//   polar             gp.d_pl_*            launch_polar      k_polar_slot        --                 k_chi2_polar (both)
+//   dense Gaussian    gp.gauss_tab()       launch_gaussian   --                  k_gaussian_slot    k_chi2_gaussian (both)
+// `a` is what follows the table (and, where the kernel takes them, the endpoints fa, fb and the slots' z) in the kernel's arguments.
+template <class K, class... Args> static void launch_mixture(hipStream_t s, GraphPack &gp, K kern, const Args &...a) {
+    const int M = gp.n_max();
+    if (M == 0) return;
+    hipLaunchKernelGGL(kern, dim3((M + TPB - 1) / TPB), dim3(TPB), 0, s, M, (const int *)gp.d_mx_f.p, (const int *)gp.d_mx_k.p, (const double *)gp.d_mx_z.p,
+                       (const double *)gp.d_mx_W.p, (const double *)gp.d_mx_c.p, (const int *)gp.d_fa.p, (const int *)gp.d_fb.p, a...);
+}
+template <class K, class... Args> static void launch_robust(hipStream_t s, GraphPack &gp, K kern, const Args &...a) {
+    const int R = gp.n_robust();
+    if (R == 0) return;
+    hipLaunchKernelGGL(kern, dim3((R + TPB - 1) / TPB), dim3(TPB), 0, s, R, (const int *)gp.d_rb_f.p, (const int *)gp.d_rb_kind.p, (const double *)gp.d_rb_c.p,
+                       (const double *)gp.d_rb_W0.p, (const int *)gp.d_fa.p, (const int *)gp.d_fb.p, (const double *)gp.d_z.p, a...);
+}
+// (the candidates of an aprilsam_amd_optimize_gnc run, gp.gc_n of them: the caller asks for gc_n > 0)
 template <class K, class... Args> static void launch_gnc(hipStream_t s, GraphPack &gp, K kern, const Args &...a) {
     hipLaunchKernelGGL(kern, dim3((gp.gc_n + TPB - 1) / TPB), dim3(TPB), 0, s, gp.gc_n, (const int *)gp.d_gc_f.p, (const double *)gp.d_gc_W0.p, (const GncPar *)gp.d_gc_par.p, a...);
 }
-// inside such a run every linearisation is preceded by the candidates' surrogate weights (none outside: gc_n = 0)
-static void enqueue_gnc_weight(GraphPack &gp, hipStream_t s, const double *upt) {
-    if (gp.gc_n == 0) return;
-    launch_gnc(s, gp, k_gnc_weight, (const int *)gp.d_fa.p, (const int *)gp.d_fb.p, (const double *)gp.d_z.p, (const double *)gp.d_lp.p, (const double *)gp.d_state.p, upt, gp.d_W.p, gp.d_gc_w.p);
-}
-
-// The kernels of polar.hip.h that run one thread per polar factor of the pack: `a` is what follows the table (n, pf, pkind, pz, pW) and the
-// endpoints (fa, fb) in the kernel's arguments.  None for a pack without polar factors
 template <class K, class... Args> static void launch_polar(hipStream_t s, GraphPack &gp, K kern, const Args &...a) {
     const int P = gp.n_polar();
     if (P == 0) return;
     hipLaunchKernelGGL(kern, dim3((P + TPB - 1) / TPB), dim3(TPB), 0, s, P, (const int *)gp.d_pl_f.p, (const int *)gp.d_pl_kind.p, (const double *)gp.d_pl_z.p,
                        (const double *)gp.d_pl_W.p, (const int *)gp.d_fa.p, (const int *)gp.d_fb.p, a...);
 }
-// every linearisation of a pack with polar factors is preceded by their slots at the l_points (what k_linearize_t reads for a binary factor)
-static void enqueue_polar(GraphPack &gp, hipStream_t s) { launch_polar(s, gp, k_polar_slot, (const double *)gp.d_lp.p, gp.d_z.p, gp.d_W.p); }
-// ... and every chi^2 is followed by their true terms at the states, in place of what k_chi2 made of the slot
-static void enqueue_chi2_polar(GraphPack &gp, hipStream_t s) { launch_polar(s, gp, k_chi2_polar, (const double *)gp.d_state.p, gp.d_chi2f.p); }
-
-// The kernels of gaussian.hip.h run one wave per dense Gaussian factor of the pack; `a` is what follows the table in
-// the kernel's arguments.  None for a pack without such factors
+// (one wave per dense Gaussian factor)
 template <class K, class... Args> static void launch_gaussian(hipStream_t s, GraphPack &gp, K kern, const Args &...a) {
     const int G = gp.n_gaussian();
     if (G == 0) return;
     hipLaunchKernelGGL(kern, dim3(G), dim3(64), 0, s, gp.gauss_tab(), a...);
 }
-// every linearisation of a pack with Gaussian factors is FOLLOWED by their blocks and rhs segments at the l_points, in place of the zero
-// contributions k_linearize_t made of their null slots -- and before the fixed-node mask
-static void enqueue_gaussian(Context &c, GraphPack &gp, hipStream_t s) {
-    launch_gaussian(s, gp, k_gaussian_slot, (const double *)gp.d_lp.p, (const unsigned char *)c.d_swap.p, c.dp.slot_blk, c.dp.slot_rhs, c.d_H.p);
+
+// BEFORE: every linearisation is preceded by ...
+// max factors: the component selected at the l_point into the factor's slot
+static void enqueue_select(GraphPack &gp, hipStream_t s) { launch_mixture(s, gp, k_select_mixture, (const double *)gp.d_lp.p, gp.d_z.p, gp.d_W.p, gp.d_sel.p); }
+// robust factors: W_eff = w(s) W0 into the factor's slot; upt: the unary factors' points as the linearisation that follows reads them
+static void enqueue_robust(GraphPack &gp, hipStream_t s, const double *upt) {
+    launch_robust(s, gp, k_robust_weight, (const double *)gp.d_lp.p, (const double *)gp.d_state.p, upt, gp.d_W.p, gp.d_rb_w.p);
 }
-// ... and every chi^2 by their terms at the states, on each factor's first entry
-static void enqueue_chi2_gaussian(GraphPack &gp, hipStream_t s) { launch_gaussian(s, gp, k_chi2_gaussian, (const double *)gp.d_state.p, gp.d_chi2f.p); }
+// GNC candidates: W_eff = w_mu(s) W0 (none outside an aprilsam_amd_optimize_gnc run: gc_n = 0)
+static void enqueue_gnc_weight(GraphPack &gp, hipStream_t s, const double *upt) {
+    if (gp.gc_n == 0) return;
+    launch_gnc(s, gp, k_gnc_weight, (const int *)gp.d_fa.p, (const int *)gp.d_fb.p, (const double *)gp.d_z.p, (const double *)gp.d_lp.p, (const double *)gp.d_state.p, upt, gp.d_W.p, gp.d_gc_w.p);
+}
+// polar factors: z_eff, W_eff at the l_points (what k_linearize_t reads for a binary factor) into the factor's slot
+static void enqueue_polar(GraphPack &gp, hipStream_t s) { launch_polar(s, gp, k_polar_slot, (const double *)gp.d_lp.p, gp.d_z.p, gp.d_W.p); }
+static void enqueue_families_before(GraphPack &gp, hipStream_t s, const double *upt) {
+    enqueue_select(gp, s);
+    enqueue_robust(gp, s, upt);
+    enqueue_gnc_weight(gp, s, upt);
+    enqueue_polar(gp, s);
+}
 
 // The kernels of polargate.hip.h, behind the path solves of a gating call: k_gate_polar runs one thread per candidate
 // (per_item = false: `work` candidates), k_associate_polar one workgroup per observation (per_item = true: `work` observations); `a` are the
@@ -245,13 +267,57 @@ static void launch_fixed(hipStream_t s, Context &c, GraphPack &gp) {
                        c.dp.slot_blk, c.dp.slot_rhs, c.d_H.p, c.d_lambda.p);
 }
 
-// what fills the contribution slots of a Gauss-Newton step: selection, robust weights, linearisation (+ the host-evaluated factors' blocks)
+// AFTER: every linearisation is followed by the dense Gaussian factors' blocks and rhs segments at the l_points, in place of the zero
+// contributions k_linearize_t made of their null slots, and then by the fixed-node mask -- last, after everything that writes a slot
+static void enqueue_families_after(Context &c, GraphPack &gp, hipStream_t s) {
+    launch_gaussian(s, gp, k_gaussian_slot, (const double *)gp.d_lp.p, (const unsigned char *)c.d_swap.p, c.dp.slot_blk, c.dp.slot_rhs, c.d_H.p);
+    launch_fixed(s, c, gp);
+}
+
+// TERM: the per-factor terms of the objective at the state array `st` -> terms[0 .. F), under one of two conventions:
+// CHI2 is april_graph_chi2's (1/2 on binary xyt terms, a max factor without its c_k), LM the least-squares objective the optimisers
+// minimise (no 1/2, min_k of the score, rho_mu for the candidates of a GNC run).  The plain kernel writes every slot's term, then each
+// family replaces its own in place, so the sum that follows keeps its order.  The one list of families
+enum class Convention { CHI2, LM };
+static void enqueue_objective(GraphPack &gp, hipStream_t s, Convention cv, const double *st, double *terms) {
+    const int F = gp.F;
+    const bool lm = cv == Convention::LM;
+    hipLaunchKernelGGL(lm ? k_lm_cost : k_chi2, dim3((F + TPB - 1) / TPB), dim3(TPB), 0, s, F, gp.d_fa.p, gp.d_fb.p, gp.d_z.p, gp.d_W.p, st, terms);
+    launch_mixture(s, gp, lm ? k_lm_cost_mixture : k_chi2_mixture, st, terms);      // the component selected at st
+    launch_robust(s, gp, lm ? k_lm_cost_robust : k_chi2_robust, st, terms);         // rho(r^T W0 r) in place of the weighted slot's term
+    if (lm && gp.gc_n > 0)            // rho_mu(r^T W0 r): the surrogate is LM's alone -- a chi^2 inside a GNC run is the plain one (k_gnc_final put the plain W back)
+        launch_gnc(s, gp, k_gnc_cost, (const int *)gp.d_fa.p, (const int *)gp.d_fb.p, (const double *)gp.d_z.p, st, terms);
+    launch_polar(s, gp, k_chi2_polar, st, terms);                                   // r_p' Wp r_p in place of the slot's term
+    launch_gaussian(s, gp, k_chi2_gaussian, st, terms);                             // c0 - 2 eta' delta + delta' Lambda delta on the factor's first entry
+}
+
+// The one reducer: n doubles at `in` -> *out by sum, max (n >= 1) or min, in one stage up to REDUCE_SPLIT terms and through REDUCE_PARTS
+// partial results at `parts` above it (kernels.hip.h: reduce_one / reduce_parts)
+enum ReduceOp { REDUCE_SUM, REDUCE_MAX, REDUCE_MIN };
+static void enqueue_reduce(ReduceOp op, hipStream_t s, int n, const double *in, double *parts, double *out) {
+    auto *const one = op == REDUCE_SUM ? k_reduce : op == REDUCE_MAX ? k_gnc_max : k_chordal_min;
+    auto *const many = op == REDUCE_SUM ? k_reduce_parts : op == REDUCE_MAX ? k_gnc_max_parts : k_chordal_min_parts;
+    if (n > REDUCE_SPLIT) {
+        hipLaunchKernelGGL(many, dim3(REDUCE_PARTS), dim3(TPB), 0, s, n, in, parts);
+        hipLaunchKernelGGL(one, dim3(1), dim3(1024), 0, s, REDUCE_PARTS, (const double *)parts, out);
+    } else hipLaunchKernelGGL(one, dim3(1), dim3(1024), 0, s, n, in, out);
+}
+
+static double device_chi2(GraphPack &gp) {     // chi^2 at d_state; synchronises the stream
+    hipStream_t s = gp.stream;
+    if (gp.F == 0) return 0;
+    enqueue_objective(gp, s, Convention::CHI2, gp.d_state.p, gp.d_chi2f.p);
+    enqueue_reduce(REDUCE_SUM, s, gp.F, gp.d_chi2f.p, gp.d_chi2f.p + gp.F_cap, gp.d_scalar.p);      // (the parts live behind the F_cap per-factor terms: upload_factors)
+    HIPCHECK(hipMemcpyAsync(gp.h_scalar.p, gp.d_scalar.p, 8, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    return gp.h_scalar.p[0];
+}
+
+// what fills the contribution slots of a Gauss-Newton step: the families' slots, the linearisation (+ the host-evaluated factors' blocks),
+// the families' contributions and the fixed-node mask
 static void enqueue_linearise(Context &c, GraphPack &gp, hipStream_t s, bool unary_at_lp) {
     const int F = c.plan.F;
-    enqueue_select(gp, s);                           // max-mixture factors: the component selected at l_point goes into the factor's slot
-    enqueue_robust(gp, s, unary_at_lp ? gp.d_upt.p : (const double *)nullptr);      // robust factors: W_eff = w(s) W0 into the factor's slot
-    enqueue_gnc_weight(gp, s, unary_at_lp ? gp.d_upt.p : (const double *)nullptr);  // GNC candidates: W_eff = w_mu(s) W0
-    enqueue_polar(gp, s);                            // polar factors: z_eff, W_eff at the l_points into the factor's slot
+    enqueue_families_before(gp, s, unary_at_lp ? gp.d_upt.p : (const double *)nullptr);
     // (a variant of the kernel without the asymmetric-W orientation branch, for graphs that have no such factor, was measured in round 6: no
     // difference -- 0.79 ms on the 1 M lattice either way)
     auto launch = [&](auto kern) {
@@ -265,8 +331,7 @@ static void enqueue_linearise(Context &c, GraphPack &gp, hipStream_t s, bool una
         hipLaunchKernelGGL(k_scatter_host, dim3((nh + TPB - 1) / TPB), dim3(TPB), 0, s, nh, gp.d_host_idx.p, gp.d_hostH.p, gp.d_fb.p, c.d_swap.p,
                            c.dp.slot_blk, c.dp.slot_rhs, c.d_H.p);
     }
-    enqueue_gaussian(c, gp, s);                      // dense Gaussian factors: Lambda's blocks and eta - Lambda delta into the slots of their entries
-    launch_fixed(s, c, gp);                         // fixed nodes: their slots zeroed, their diagonal 1.0 -- last, after everything that writes a slot
+    enqueue_families_after(c, gp, s);
 }
 
 // what a caller of the numeric phase asks for beyond the plain step; everything is off unless named

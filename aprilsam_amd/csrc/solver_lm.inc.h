@@ -23,29 +23,12 @@ static const char *lm_bad_options(const aprilsam_amd_lm_opts_t *o) {
     return nullptr;
 }
 
-// sum of n doubles at `in` into *out: the split rule of device_chi2 (parts behind the n terms)
-static void lm_reduce(hipStream_t s, int n, const double *in, double *parts, double *out) {
-    if (n > REDUCE_SPLIT) {
-        hipLaunchKernelGGL(k_reduce_parts, dim3(REDUCE_PARTS), dim3(TPB), 0, s, n, in, parts);
-        hipLaunchKernelGGL(k_reduce, dim3(1), dim3(1024), 0, s, REDUCE_PARTS, (const double *)parts, out);
-    } else hipLaunchKernelGGL(k_reduce, dim3(1), dim3(1024), 0, s, n, in, out);
-}
 // F at st -> *out
 static void lm_enqueue_cost(Context &c, GraphPack &gp, hipStream_t s, const double *st, double *out) {
-    const int F = gp.F, M = gp.n_max(), R = gp.n_robust(), T = std::max(F, 2 * gp.N);
+    const int F = gp.F, T = std::max(F, 2 * gp.N);
     double *terms = c.d_lm_terms.p;
-    hipLaunchKernelGGL(k_lm_cost, dim3((F + TPB - 1) / TPB), dim3(TPB), 0, s, F, gp.d_fa.p, gp.d_fb.p, gp.d_z.p, gp.d_W.p, st, terms);
-    if (M > 0)
-        hipLaunchKernelGGL(k_lm_cost_mixture, dim3((M + TPB - 1) / TPB), dim3(TPB), 0, s, M, gp.d_mx_f.p, gp.d_mx_k.p, gp.d_mx_z.p, gp.d_mx_W.p,
-                           gp.d_mx_c.p, gp.d_fa.p, gp.d_fb.p, st, terms);
-    if (R > 0)           // (robust factors: rho(r^T W0 r) in place of the weighted slot's term)
-        hipLaunchKernelGGL(k_lm_cost_robust, dim3((R + TPB - 1) / TPB), dim3(TPB), 0, s, R, gp.d_rb_f.p, gp.d_rb_kind.p, gp.d_rb_c.p, gp.d_rb_W0.p,
-                           gp.d_fa.p, gp.d_fb.p, gp.d_z.p, st, terms);
-    if (gp.gc_n > 0)     // (candidates of an aprilsam_amd_optimize_gnc run: rho_mu(r^T W0 r), solver_gnc.inc.h)
-        launch_gnc(s, gp, k_gnc_cost, (const int *)gp.d_fa.p, (const int *)gp.d_fb.p, (const double *)gp.d_z.p, st, terms);
-    launch_polar(s, gp, k_lm_cost_polar, st, terms);      // (polar factors: r_p' Wp r_p in place of the slot's term)
-    launch_gaussian(s, gp, k_chi2_gaussian, st, terms);   // (dense Gaussian factors: the full term at st on the factor's first entry)
-    lm_reduce(s, F, terms, terms + T, out);
+    enqueue_objective(gp, s, Convention::LM, st, terms);
+    enqueue_reduce(REDUCE_SUM, s, F, terms, terms + T, out);
 }
 static void lm_enqueue_commit(Context &c, GraphPack &gp, hipStream_t s) {
     const int N = gp.N;
@@ -63,10 +46,10 @@ static void lm_enqueue_iteration(Context &c, GraphPack &gp, hipStream_t s) {
     hipLaunchKernelGGL(k_lm_model, dim3((F + TPB - 1) / TPB), dim3(TPB), 0, s, F, gp.d_fa.p, gp.d_fb.p, gp.d_z.p, gp.d_W.p, (const double *)gp.d_lp.p,
                        (const double *)gp.d_dx.p, terms);
     launch_gaussian(s, gp, k_lm_model_gaussian, (const double *)gp.d_lp.p, (const double *)gp.d_dx.p, terms);      // (their slots are null: h' (2 g - Lambda h) from the table)
-    lm_reduce(s, F, terms, parts, &S->pred);
+    enqueue_reduce(REDUCE_SUM, s, F, terms, parts, &S->pred);
     hipLaunchKernelGGL(k_lm_norms, dim3((N + TPB - 1) / TPB), dim3(TPB), 0, s, N, (const double *)gp.d_dx.p, (const double *)gp.d_state.p, terms, terms + N);
-    lm_reduce(s, N, terms, parts, &S->hh);
-    lm_reduce(s, N, terms + N, parts, &S->xx);
+    enqueue_reduce(REDUCE_SUM, s, N, terms, parts, &S->hh);
+    enqueue_reduce(REDUCE_SUM, s, N, terms + N, parts, &S->xx);
     hipLaunchKernelGGL(k_lm_decide, dim3(1), dim3(64), 0, s, S, c.h_lm.p, (const int *)c.d_bad.p, c.d_lm_trace.p);
     lm_enqueue_commit(c, gp, s);
     HIPCHECK(hipGetLastError());

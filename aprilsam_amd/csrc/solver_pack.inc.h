@@ -517,19 +517,6 @@ static void select_new_max(GraphPack &gp, const april_graph_t *g, int f_from) {
         memcpy(gp.h_W.p + (size_t)9 * p, &gp.mx_W[(size_t)9 * (gp.mx_k[m] + k)], 72);
     }
 }
-// the launches every linearisation / chi^2 of a pack with max factors is bracketed with (none for a pack without)
-static void enqueue_select(GraphPack &gp, hipStream_t s) {
-    const int M = gp.n_max();
-    if (M == 0) return;
-    hipLaunchKernelGGL(k_select_mixture, dim3((M + TPB - 1) / TPB), dim3(TPB), 0, s, M, gp.d_mx_f.p, gp.d_mx_k.p, gp.d_mx_z.p, gp.d_mx_W.p, gp.d_mx_c.p,
-                       gp.d_fa.p, gp.d_fb.p, gp.d_lp.p, gp.d_z.p, gp.d_W.p, gp.d_sel.p);
-}
-static void enqueue_chi2_mixture(GraphPack &gp, hipStream_t s) {
-    const int M = gp.n_max();
-    if (M == 0) return;
-    hipLaunchKernelGGL(k_chi2_mixture, dim3((M + TPB - 1) / TPB), dim3(TPB), 0, s, M, gp.d_mx_f.p, gp.d_mx_k.p, gp.d_mx_z.p, gp.d_mx_W.p, gp.d_mx_c.p,
-                       gp.d_fa.p, gp.d_fb.p, gp.d_state.p, gp.d_chi2f.p);
-}
 // incremental steps: the robust factors packed at or after entry f_from are weighted on the host (robust_host_s + robust_weight, the rule
 // k_robust_weight applies) at the point the fast path linearises them -- the l_point mirror (xyt) or the state mirror (xytpos, as
 // record_unary_points) -- and their slots of h_W take W_eff = w W0
@@ -543,20 +530,6 @@ static void select_new_robust(GraphPack &gp, int f_from) {
         gp.rb_w[q] = w;
         for (int k = 0; k < 9; k++) gp.h_W.p[(size_t)9 * p + k] = w * W0[k];
     }
-}
-// the launch every linearisation of a pack with robust factors is preceded by (none for a pack without); upt: the unary factors' points
-// as the linearisation that follows reads them (k_linearize_t's argument)
-static void enqueue_robust(GraphPack &gp, hipStream_t s, const double *upt) {
-    const int R = gp.n_robust();
-    if (R == 0) return;
-    hipLaunchKernelGGL(k_robust_weight, dim3((R + TPB - 1) / TPB), dim3(TPB), 0, s, R, gp.d_rb_f.p, gp.d_rb_kind.p, gp.d_rb_c.p, gp.d_rb_W0.p,
-                       gp.d_fa.p, gp.d_fb.p, gp.d_z.p, gp.d_lp.p, gp.d_state.p, upt, gp.d_W.p, gp.d_rb_w.p);
-}
-static void enqueue_chi2_robust(GraphPack &gp, hipStream_t s) {
-    const int R = gp.n_robust();
-    if (R == 0) return;
-    hipLaunchKernelGGL(k_chi2_robust, dim3((R + TPB - 1) / TPB), dim3(TPB), 0, s, R, gp.d_rb_f.p, gp.d_rb_kind.p, gp.d_rb_c.p, gp.d_rb_W0.p,
-                       gp.d_fa.p, gp.d_fb.p, gp.d_z.p, gp.d_state.p, gp.d_chi2f.p);
 }
 // incremental steps: the slots of the polar factors packed at or after entry f_from are written on the host (polar.h, the formulas
 // k_polar_slot applies) at the l_point mirror -- the fast path uploads and linearises them as plain xyt factors

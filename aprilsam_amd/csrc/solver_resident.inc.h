@@ -338,17 +338,14 @@ static int debug_stage_impl(april_graph_t *g, april_graph_cholesky_param_t *para
     hipStream_t s = gp.stream;
     gp.mirror_sync = false;
     HIPCHECK(hipMemcpyAsync(gp.d_lp.p, gp.d_state.p, (size_t)24 * N, hipMemcpyDeviceToDevice, s));
-    enqueue_select(gp, s);
-    enqueue_robust(gp, s, nullptr);
-    enqueue_polar(gp, s);
+    enqueue_families_before(gp, s, nullptr);
     hipLaunchKernelGGL((k_linearize_t<false>), dim3((F + TPB - 1) / TPB), dim3(TPB), 0, s, 0, F, (const int *)nullptr, gp.d_fa.p, gp.d_fb.p, gp.d_z.p, gp.d_W.p,
                        gp.d_lp.p, gp.d_state.p, c.d_swap.p, c.dp.slot_blk, c.dp.slot_rhs, c.d_H.p, c.d_bad.p, (const double *)nullptr);
-    enqueue_gaussian(c, gp, s);
     if (gp.n_fixed() > 0) {                      // (the mask writes d_lambda as every step's does: whatever runs next on this param rewrites it)
         set_lambda(c, gp, param->tikhanov);
-        launch_fixed(s, c, gp);
         c.lambda_N = -1;
     }
+    enqueue_families_after(c, gp, s);
     if (what == 0) {
         std::vector<double> H((size_t)9 * std::max(1, P.n_slots));
         HIPCHECK(hipMemcpyAsync(H.data(), c.d_H.p, H.size() * 8, hipMemcpyDeviceToHost, s));

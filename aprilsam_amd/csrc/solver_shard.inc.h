@@ -485,8 +485,7 @@ static double shard_chi2_impl(april_graph_t *g, april_graph_cholesky_param_t *pa
     GraphPack &gp = pack_for(g);
     const Plan &P = ic->second->plan; ShardState &S = *it->second;
     hipStream_t s = gp.stream;
-    
-    hipLaunchKernelGGL(k_chi2, dim3((gp.F + TPB - 1) / TPB), dim3(TPB), 0, s, gp.F, gp.d_fa.p, gp.d_fb.p, gp.d_z.p, gp.d_W.p, gp.d_state.p, gp.d_chi2f.p);
+    enqueue_objective(gp, s, Convention::CHI2, gp.d_state.p, gp.d_chi2f.p);      // (every family is refused at shard_begin: the plain launch alone)
     std::vector<double> h(gp.F);
     HIPCHECK(hipMemcpyAsync(h.data(), gp.d_chi2f.p, (size_t)8 * gp.F, hipMemcpyDeviceToHost, s));
     HIPCHECK(hipStreamSynchronize(s));
