@@ -26,58 +26,23 @@ struct PsFront {
     int parent;                // record of the parent front (-1: root)
     int rel_begin;             // the struct rows' blocks inside the parent's row list (front_rel) at this offset of the int arena
     int cmap;                  // per column: its index among the parent's columns, at this offset of the column map
-    int pad;
+    int first;                 // first own position (the tree solve's tables: treesolve.hip.h)
 };
 static_assert(sizeof(PsFront) == 48, "PsFront layout");
 
 struct PsPath { long long col0; int ld, s; };         // one front on a node's path: its first column's own rows
 struct PsPair { int pa, na, pb, nb, nc, out; };       // path entries of a and b, the common ancestors (the last nc of both), output slot
 
-// One wave per ent = { record, column tile }: V_S = L_SS^-1 V_S on 16 columns, row block by row block.  Block i0:
-// T = V_i - L_i,<i0 V_<i0 (MFMA), then the 16 x 16 lower triangle L_ii by substitution, lane per column (T staged in LDS).
-// The wave reads back what it wrote in earlier row blocks (the fence makes those stores visible to its loads).
+// One wave per ent = { record, column tile }: V_S = L_SS^-1 V_S on 16 columns (tile_trsm, selinv.hip.h).
 __global__ void __launch_bounds__(256) k_path_trsm(const PsFront *__restrict__ fr, const int4 *__restrict__ ent, int n, const double *__restrict__ pool,
                                                    double *__restrict__ buf) {
     __shared__ double T[4][SEL_T][SEL_T + 1];
-    const int wv = threadIdx.x >> 6, w = blockIdx.x * 4 + wv;
-    if (w >= n) return;
-    const int lane = threadIdx.x & 63, l15 = lane & 15, l4 = lane >> 4;
+    const int w = sel_wave(n);
+    if (w < 0) return;
     const int4 e = ent[w];
     const PsFront F = fr[e.x];
-    const int s = F.s, R = F.R, ld = F.s + F.u, c0 = SEL_T * e.y, nc = min(SEL_T, F.ncol - c0);
-    const double *L = pool + F.off;                       // L_SS[r][k] = L[r + k R]
-    double *V = buf + F.buf + (long long)c0 * ld;
-    for (int i0 = 0; i0 < s; i0 += SEL_T) {
-        const int m = min(SEL_T, s - i0);
-        sel_d4 acc = (sel_d4){ 0, 0, 0, 0 };
-        if (i0 > 0)
-            acc = sel_mma([&](int i, int k) { return i0 + i < s ? L[(long long)k * R + i0 + i] : 0.0; },
-                          [&](int k, int c) { return c < nc ? V[(long long)c * ld + k] : 0.0; }, 0, i0, acc);
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int row = l4 + 4 * r;
-            T[wv][row][l15] = (row < m && l15 < nc) ? V[(long long)l15 * ld + i0 + row] - acc[r] : 0.0;
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (wave-private tile: the wave's own LDS operations are in order)
-        __builtin_amdgcn_sched_barrier(0);
-        if (lane < nc) {
-            double x[SEL_T];
-#pragma unroll
-            for (int r = 0; r < SEL_T; r++) {
-                double v = 0.0;
-                if (r < m) {
-                    v = T[wv][r][lane];
-#pragma unroll
-                    for (int k = 0; k < r; k++) v -= L[(long long)(i0 + k) * R + i0 + r] * x[k];
-                    v = v / L[(long long)(i0 + r) * R + i0 + r];
-                }
-                x[r] = v;
-            }
-#pragma unroll
-            for (int r = 0; r < SEL_T; r++) if (r < m) V[(long long)lane * ld + i0 + r] = x[r];
-        }
-        __threadfence();
-    }
+    const int ld = F.s + F.u, c0 = SEL_T * e.y;
+    tile_trsm<false>(pool + F.off, F.R, F.s, buf + F.buf + (long long)c0 * ld, ld, min(SEL_T, F.ncol - c0), T[threadIdx.x >> 6]);
 }
 
 // One wave per ent = { record, struct-row tile, column tile }: W = V_U - L_US V_S, element (a, c) stored at the parent's local row
@@ -85,9 +50,8 @@ __global__ void __launch_bounds__(256) k_path_trsm(const PsFront *__restrict__ f
 // its path, so every element of a parent's local vectors is written at most once; the rest stay zero.
 __global__ void __launch_bounds__(256) k_path_gemm(const PsFront *__restrict__ fr, const int4 *__restrict__ ent, int n, const double *__restrict__ pool,
                                                    const int *__restrict__ rel, const int *__restrict__ cmap, double *__restrict__ buf) {
-    const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (w >= n) return;
-    const int lane = threadIdx.x & 63, l15 = lane & 15, l4 = lane >> 4;
+    const int w = sel_wave(n);
+    if (w < 0) return;
     const int4 e = ent[w];
     const PsFront F = fr[e.x], P = fr[F.parent];
     const int s = F.s, u = F.u, R = F.R, ld = s + u, ldp = P.s + P.u, i0 = SEL_T * e.y, c0 = SEL_T * e.z;
@@ -97,15 +61,11 @@ __global__ void __launch_bounds__(256) k_path_gemm(const PsFront *__restrict__ f
     acc = sel_mma([&](int i, int k) { return i0 + i < u ? Lus[(long long)k * R + i0 + i] : 0.0; },
                   [&](int k, int c) { return c0 + c < F.ncol ? V[(long long)(c0 + c) * ld + k] : 0.0; }, 0, s, acc);
     const int *rl = rel + F.rel_begin;
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const int row = i0 + l4 + 4 * r, col = c0 + l15;
-        if (row < u && col < F.ncol) {
-            const int pr = 3 * rl[row / 3] + row % 3, pc = cmap[F.cmap + col];
-            if (pr < ldp && pc >= 0 && pc < P.ncol)            // (the host tables promise both; a broken map must not write elsewhere)
-                buf[P.buf + (long long)pc * ldp + pr] = V[(long long)col * ld + s + row] - acc[r];
-        }
-    }
+    sel_tile_store(i0, c0, u, F.ncol, acc, [&](int row, int col, double v) {
+        const int pr = 3 * rl[row / 3] + row % 3, pc = cmap[F.cmap + col];
+        if (pr < ldp && pc >= 0 && pc < P.ncol)                // (the host tables promise both; a broken map must not write elsewhere)
+            buf[P.buf + (long long)pc * ldp + pr] = V[(long long)col * ld + s + row] - v;
+    });
 }
 
 // the right-hand sides: a one at each listed element of the zeroed work buffer (three per node, in its own front)
@@ -178,6 +138,34 @@ __global__ void __launch_bounds__(256) k_path_gram(const PsPair *__restrict__ pa
     }
 }
 
+// out (3 x 3, row-major) = [J0 J1] C [J0 J1]': the covariance of an xyt prediction with the Jacobians J0, J1 (3 x 3 each) under the joint
+// block C (6 x 6) of its two poses.  Jc = [J0 J1], then Jc C, then the product with Jc', every sum over k ascending.
+__device__ __forceinline__ void xyt_joint_cov(const double *J0, const double *J1, const double *C, double *out) {
+    double Jc[18], JC[18];                                // 3 x 6 row-major
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = 0; b < 3; b++) { Jc[6 * a + b] = J0[3 * a + b]; Jc[6 * a + 3 + b] = J1[3 * a + b]; }
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = 0; b < 6; b++) {
+            double v = 0.0;
+#pragma unroll
+            for (int k = 0; k < 6; k++) v += Jc[6 * a + k] * C[6 * k + b];
+            JC[6 * a + b] = v;
+        }
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = 0; b < 3; b++) {
+            double v = 0.0;
+#pragma unroll
+            for (int k = 0; k < 6; k++) v += JC[6 * a + k] * Jc[6 * b + k];
+            out[3 * a + b] = v;
+        }
+}
+
 // One thread per candidate (a, b, z, W): in = { state a (3), state b (3), z (3), W (9, row-major) }, cov its joint block.
 //   r, J_a, J_b    the xyt factor's residual (theta wrapped) and Jacobians at the states (factor_residual)
 //   S = [J_a J_b] cov [J_a J_b]' + W^-1,   d2 = r' S^-1 r   (Cholesky of S)
@@ -188,36 +176,15 @@ __global__ void __launch_bounds__(256) k_gate_xyt(int n, const double *__restric
     const double *q = in + 18ll * i, *C = cov + 36ll * i;
     double J0[9], J1[9], r[3];
     factor_residual(true, q, q + 3, q + 6, J0, J1, r);
-    double Jc[18];                                        // [J_a J_b], 3 x 6 row-major
-#pragma unroll
-    for (int a = 0; a < 3; a++)
-#pragma unroll
-        for (int b = 0; b < 3; b++) { Jc[6 * a + b] = J0[3 * a + b]; Jc[6 * a + 3 + b] = J1[3 * a + b]; }
-    double JC[18];                                        // Jc C
-#pragma unroll
-    for (int a = 0; a < 3; a++)
-#pragma unroll
-        for (int b = 0; b < 6; b++) {
-            double v = 0.0;
-#pragma unroll
-            for (int k = 0; k < 6; k++) v += Jc[6 * a + k] * C[6 * k + b];
-            JC[6 * a + b] = v;
-        }
     const double *W = q + 9;                              // W^-1 by the adjugate (W was checked positive definite on the host)
     const double det = W[0] * (W[4] * W[8] - W[5] * W[7]) - W[1] * (W[3] * W[8] - W[5] * W[6]) + W[2] * (W[3] * W[7] - W[4] * W[6]);
     const double Wi[9] = { (W[4] * W[8] - W[5] * W[7]) / det, (W[2] * W[7] - W[1] * W[8]) / det, (W[1] * W[5] - W[2] * W[4]) / det,
                            (W[5] * W[6] - W[3] * W[8]) / det, (W[0] * W[8] - W[2] * W[6]) / det, (W[2] * W[3] - W[0] * W[5]) / det,
                            (W[3] * W[7] - W[4] * W[6]) / det, (W[1] * W[6] - W[0] * W[7]) / det, (W[0] * W[4] - W[1] * W[3]) / det };
     double S[9];
+    xyt_joint_cov(J0, J1, C, S);
 #pragma unroll
-    for (int a = 0; a < 3; a++)
-#pragma unroll
-        for (int b = 0; b < 3; b++) {
-            double v = 0.0;
-#pragma unroll
-            for (int k = 0; k < 6; k++) v += JC[6 * a + k] * Jc[6 * b + k];
-            S[3 * a + b] = v + Wi[3 * a + b];
-        }
+    for (int k = 0; k < 9; k++) S[k] = S[k] + Wi[k];
     const double l00 = sqrt(S[0]), l10 = S[3] / l00, l20 = S[6] / l00;
     const double l11 = sqrt(S[4] - l10 * l10), l21 = (S[7] - l20 * l10) / l11;
     const double l22 = sqrt(S[8] - l20 * l20 - l21 * l21);

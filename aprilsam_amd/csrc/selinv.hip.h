@@ -59,6 +59,69 @@ __device__ __forceinline__ sel_d4 sel_mma(FA a, FB b, int k_lo, int k_hi, sel_d4
     return acc;
 }
 
+// The frame of a one-wave-per-entry kernel (four waves per workgroup): the wave's entry among the launch's n, -1 for an idle wave ...
+__device__ __forceinline__ int sel_wave(int n) {
+    const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
+    return w < n ? w : -1;
+}
+// ... and sel_mma's result handed out element by element: f(row, col, acc[r]) for the lane's four elements of the tile at (i0, c0)
+// that lie inside rows x cols, r ascending.
+template <class F>
+__device__ __forceinline__ void sel_tile_store(int i0, int c0, int rows, int cols, sel_d4 acc, F f) {
+    const int lane = threadIdx.x & 63, l15 = lane & 15, l4 = lane >> 4;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const int row = i0 + l4 + 4 * r, col = c0 + l15;
+        if (row < rows && col < cols) f(row, col, acc[r]);
+    }
+}
+
+// One wave: V = L_SS^-1 V (TRANS: L_SS^-T V) in place on nc <= 16 columns of s rows (column-major, leading dimension ld), row block
+// by row block: the first block first, TRANS the last.  L_SS[r][k] = L[r + k R].  Block i0: T = V_i - (the solved blocks' part of
+// row block i) V_solved (MFMA), then the 16 x 16 triangle on the diagonal by substitution, lane per column (T: the wave's own LDS
+// tile).  The wave reads back what it wrote in the blocks before (the fence makes those stores visible to its loads).  What the
+// two directions differ in: the block order, the k range of the product, the order of the substitution, and tri.
+template <bool TRANS>
+__device__ __forceinline__ void tile_trsm(const double *__restrict__ L, int R, int s, double *V, int ld, int nc, double (*T)[SEL_T + 1]) {
+    const int lane = threadIdx.x & 63, l15 = lane & 15, l4 = lane >> 4;
+    // element (r0 + r, k0 + k) of the triangle solved with: L_SS, TRANS its transpose
+    auto tri = [&](int r0, int r, int k0, int k) { return TRANS ? L[(long long)(r0 + r) * R + k0 + k] : L[(long long)(k0 + k) * R + r0 + r]; };
+    for (int i0 = TRANS ? ((s - 1) / SEL_T) * SEL_T : 0; TRANS ? i0 >= 0 : i0 < s; i0 += TRANS ? -SEL_T : SEL_T) {
+        const int m = min(SEL_T, s - i0);
+        const int k_lo = TRANS ? i0 + SEL_T : 0, k_hi = TRANS ? s : i0;      // the rows solved already
+        sel_d4 acc = (sel_d4){ 0, 0, 0, 0 };
+        if (k_lo < k_hi)
+            acc = sel_mma([&](int i, int k) { return i0 + i < s ? tri(i0, i, 0, k) : 0.0; },
+                          [&](int k, int c) { return c < nc ? V[(long long)c * ld + k] : 0.0; }, k_lo, k_hi, acc);
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int row = l4 + 4 * r;
+            T[row][l15] = (row < m && l15 < nc) ? V[(long long)l15 * ld + i0 + row] - acc[r] : 0.0;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (wave-private tile: the wave's own LDS operations are in order)
+        __builtin_amdgcn_sched_barrier(0);
+        if (lane < nc) {
+            double x[SEL_T];
+#pragma unroll
+            for (int q = 0; q < SEL_T; q++) {
+                const int r = TRANS ? SEL_T - 1 - q : q;       // the row solved q-th, after the rows k above it (TRANS: below it)
+                double v = 0.0;
+                if (r < m) {
+                    v = T[r][lane];
+#pragma unroll
+                    for (int k = TRANS ? r + 1 : 0; k < (TRANS ? SEL_T : r); k++)
+                        if (!TRANS || k < m) v -= tri(i0, r, i0, k) * x[k];
+                    v = v / tri(i0, r, i0, r);
+                }
+                x[r] = v;
+            }
+#pragma unroll
+            for (int r = 0; r < SEL_T; r++) if (r < m) V[(long long)lane * ld + i0 + r] = x[r];
+        }
+        __threadfence();
+    }
+}
+
 // Sig_UU of every front of a level from its parent's Sig_FF: child struct row a is row 3 rel[a / 3] + a % 3 of the parent (the
 // extend-add's map, read the other way).  One workgroup per (front, chunk of 1024 elements): ent = { front, chunk }.  Only the
 // front's first u struct rows take part: the phantom rows the incremental path appends to its last tail front (zero rows of L)
@@ -146,9 +209,8 @@ __global__ void __launch_bounds__(256) k_selinv_trinv(const SelFront *__restrict
 // X = L_US Linv: ent = { front, row tile (of u), column tile (of s) }, one wave per 16 x 16 tile.
 __global__ void __launch_bounds__(256) k_selinv_x(const SelFront *__restrict__ fr, const int4 *__restrict__ ent, int n, const double *__restrict__ pool,
                                                   double *__restrict__ scr) {
-    const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (w >= n) return;
-    const int lane = threadIdx.x & 63, l15 = lane & 15, l4 = lane >> 4;
+    const int w = sel_wave(n);
+    if (w < 0) return;
     const int4 e = ent[w];
     const SelFront F = fr[e.x];
     const int s = F.s, u = F.u, R = F.R, ls = sel_round16(s), lu = sel_round16(u), i0 = SEL_T * e.y, j0 = SEL_T * e.z;
@@ -158,19 +220,14 @@ __global__ void __launch_bounds__(256) k_selinv_x(const SelFront *__restrict__ f
     sel_d4 acc = (sel_d4){ 0, 0, 0, 0 };
     acc = sel_mma([&](int i, int k) { return i0 + i < u ? Lus[(long long)k * R + i0 + i] : 0.0; },
                   [&](int k, int c) { return j0 + c < s ? Li[(long long)(j0 + c) * ls + k] : 0.0; }, j0, s, acc);
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const int row = i0 + l4 + 4 * r, col = j0 + l15;
-        if (row < u && col < s) X[(long long)col * lu + row] = acc[r];
-    }
+    sel_tile_store(i0, j0, u, s, acc, [&](int row, int col, double v) { X[(long long)col * lu + row] = v; });
 }
 
 // Sig_US = -Sig_UU X, stored twice (rows U / columns S and its transpose): ent = { front, row tile (of u), column tile (of s) }.
 __global__ void __launch_bounds__(256) k_selinv_sus(const SelFront *__restrict__ fr, const int4 *__restrict__ ent, int n, const double *__restrict__ scr,
                                                     double *__restrict__ sig) {
-    const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (w >= n) return;
-    const int lane = threadIdx.x & 63, l15 = lane & 15, l4 = lane >> 4;
+    const int w = sel_wave(n);
+    if (w < 0) return;
     const int4 e = ent[w];
     const SelFront F = fr[e.x];
     const int s = F.s, u = F.u, R = F.R, ls = sel_round16(s), lu = sel_round16(u), i0 = SEL_T * e.y, j0 = SEL_T * e.z;
@@ -179,20 +236,15 @@ __global__ void __launch_bounds__(256) k_selinv_sus(const SelFront *__restrict__
     sel_d4 acc = (sel_d4){ 0, 0, 0, 0 };
     acc = sel_mma([&](int i, int k) { return i0 + i < u ? S[(long long)(s + k) * R + s + i0 + i] : 0.0; },
                   [&](int k, int c) { return j0 + c < s ? X[(long long)(j0 + c) * lu + k] : 0.0; }, 0, u, acc);
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const int row = i0 + l4 + 4 * r, col = j0 + l15;
-        if (row < u && col < s) { S[(long long)col * R + s + row] = -acc[r]; S[(long long)(s + row) * R + col] = -acc[r]; }
-    }
+    sel_tile_store(i0, j0, u, s, acc, [&](int row, int col, double v) { S[(long long)col * R + s + row] = -v; S[(long long)(s + row) * R + col] = -v; });
 }
 
 // Sig_SS = Linv^T Linv - X^T Sig_US on the lower tiles (ent = { front, row tile, column tile }, row >= column), each element
 // (a >= c) stored at (a, c) and (c, a).
 __global__ void __launch_bounds__(256) k_selinv_sss(const SelFront *__restrict__ fr, const int4 *__restrict__ ent, int n, const double *__restrict__ scr,
                                                     double *__restrict__ sig) {
-    const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (w >= n) return;
-    const int lane = threadIdx.x & 63, l15 = lane & 15, l4 = lane >> 4;
+    const int w = sel_wave(n);
+    if (w < 0) return;
     const int4 e = ent[w];
     const SelFront F = fr[e.x];
     const int s = F.s, u = F.u, R = F.R, ls = sel_round16(s), lu = sel_round16(u), i0 = SEL_T * e.y, j0 = SEL_T * e.z;
@@ -205,11 +257,7 @@ __global__ void __launch_bounds__(256) k_selinv_sss(const SelFront *__restrict__
     if (u > 0)
         acx = sel_mma([&](int i, int k) { return i0 + i < s ? X[(long long)(i0 + i) * lu + k] : 0.0; },
                       [&](int k, int c) { return j0 + c < s ? S[(long long)(j0 + c) * R + s + k] : 0.0; }, 0, u, acx);
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const int row = i0 + l4 + 4 * r, col = j0 + l15;
-        if (row < s && col < s && row >= col) { const double v = acc[r] - acx[r]; S[(long long)col * R + row] = v; S[(long long)row * R + col] = v; }
-    }
+    sel_tile_store(i0, j0, s, s, acc - acx, [&](int row, int col, double v) { if (row >= col) { S[(long long)col * R + row] = v; S[(long long)row * R + col] = v; } });
 }
 
 // Requested blocks, straight into pinned host memory in node order and node coordinates (x, y, theta: the unknowns of dx).

@@ -60,8 +60,18 @@ struct IncState {
     std::vector<char> st_mid, st_mode; std::vector<int> st_owner, st_mask, st_wout, st_slot; std::vector<UpdRec> st_upd, st_rec;
 };
 
-// marginal covariances (solver_marginals.inc.h): per level, the ranges of its work entries in the selected inversion's table
-struct SelLevel { int gat_off = 0, n_gat = 0, diag_off = 0, n_diag = 0, tri_off = 0, n_tri = 0, x_off = 0, n_x = 0, sus_off = 0, n_sus = 0, sss_off = 0, n_sss = 0; };
+// The work-entry tables of the retained-factor consumers: one vector of entries per table, and per level and kernel the run of entries
+// its launch takes.  span_of(ent, fill): the run that fill() appends to ent.
+struct Span { int off = 0, n = 0; };
+template <class E, class Fill> static Span span_of(std::vector<E> &ent, Fill fill) {
+    Span sp{ (int)ent.size(), 0 };
+    fill();
+    sp.n = (int)ent.size() - sp.off;
+    return sp;
+}
+
+// marginal covariances (solver_marginals.inc.h): per level, the runs of its work entries in the selected inversion's table
+struct SelLevel { Span gat, diag, tri, x, sus, sss; };
 
 // The structure the retained factor lives in, derived once for all its readers (factor_view, solver_query.inc.h: builder and validity rule):
 // the fronts (scr: written by the selected inversion's table builder, read by its kernels alone), their depth below the root, the fronts of
@@ -75,6 +85,12 @@ struct FactorView {
     DBuf<int> d_i32; bool on_device = false;
     void release() { d_i32.release(); fr.clear(); depth.clear(); i32.clear(); lev.clear(); kind = 0; serial = -1; on_device = false; }
 };
+
+// A front of the view as the solve kernels take it (pathsolve.hip.h, treesolve.hip.h): its local vectors at buf, ncol columns wide, under
+// the record `parent`, its columns mapped to the parent's through the column map at cmap
+static PsFront ps_front(const SelFront &F, long long buf, int ncol, int parent, int cmap) {
+    return PsFront{ F.off, buf, F.s, F.u, F.R, ncol, parent, F.rel_begin, cmap, F.first };
+}
 
 // joint covariances of any pair and gating (solver_gating.inc.h): the scratch maps of one call, and the device buffers of the path solves
 struct PathState {
@@ -92,16 +108,16 @@ struct PathState {
 
 // solves with the retained factor (solver_treesolve.inc.h): the tables of the whole-tree passes, kept against the view's generation,
 // and the device / pinned buffers of one call
-struct TsLevel { int asm_off = 0, n_asm = 0, tr_off = 0, n_tr = 0, gm_off = 0, n_gm = 0, gat_off = 0, n_gat = 0, gt_off = 0, n_gt = 0; };
+struct TsLevel { Span assemble, trsm, gemm, gather, gemmt; };
 struct TreeState {
     long long gen = -1;                    // FactorView::gen the tables describe
     long long rows = 0;                    // sum over the fronts of s + u: the work buffer takes this many doubles per column
     std::vector<int> wrow; std::vector<TsLevel> lev;      // a front's first row in the work buffer; the levels, root first
-    DBuf<PsFront> d_fr; DBuf<TsFront> d_tf; DBuf<int2> d_ent; DBuf<int> d_cptr, d_npos, d_nodes; DBuf<TsKid> d_cent;
+    DBuf<PsFront> d_fr; DBuf<int2> d_ent; DBuf<int> d_cptr, d_npos, d_nodes; DBuf<TsKid> d_cent;
     DBuf<double> d_buf, d_B, d_st; HBuf<double> h_B, h_X;
     long long peak_bytes = 0;              // the largest work buffer a call has used
     void release() {
-        d_fr.release(); d_tf.release(); d_ent.release(); d_cptr.release(); d_npos.release(); d_nodes.release(); d_cent.release();
+        d_fr.release(); d_ent.release(); d_cptr.release(); d_npos.release(); d_nodes.release(); d_cent.release();
         d_buf.release(); d_B.release(); d_st.release(); h_B.release(); h_X.release();
         wrow.clear(); lev.clear(); gen = -1;
     }

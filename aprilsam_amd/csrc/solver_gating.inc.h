@@ -38,9 +38,7 @@ static void ps_chunk(Context &c, hipStream_t s, const std::vector<int> &nodes, c
     long long used = 0;
     for (int r = 0; r < nr; r++) {
         const SelFront &F = fr[touched[r]];
-        PsFront &R = rec[r];
-        R.off = F.off; R.buf = used; R.s = F.s; R.u = F.u; R.R = F.R; R.ncol = 3 * m[r];
-        R.parent = F.parent >= 0 ? S.rec[F.parent] : -1; R.rel_begin = F.rel_begin; R.cmap = cbeg[r]; R.pad = 0;
+        PsFront &R = rec[r] = ps_front(F, used, 3 * m[r], F.parent >= 0 ? S.rec[F.parent] : -1, cbeg[r]);
         if (F.parent >= 0 && R.parent < 0) fail(ERR_INTERNAL, "aprilsam_amd_marginals_joint_any: a path leaves the tree");
         cbeg[r + 1] = cbeg[r] + R.ncol;
         used += (long long)(F.s + F.u) * R.ncol;
@@ -71,21 +69,19 @@ static void ps_chunk(Context &c, hipStream_t s, const std::vector<int> &nodes, c
         pairs[i] = PsPair{ pbeg[ja], na, pbeg[jb], nb, nc, out0 + (int)i };
     }
     // work entries, level by level
-    struct Lev { int tr_off, n_tr, gm_off, n_gm; };
+    struct Lev { Span trsm, gemm; };
     std::vector<Lev> lev;
     std::vector<int4> ent;
     for (int r0 = 0; r0 < nr; ) {
         int r1 = r0;
         while (r1 < nr && V.depth[touched[r1]] == V.depth[touched[r0]]) r1++;
         Lev L;
-        L.tr_off = (int)ent.size();
-        for (int r = r0; r < r1; r++) for (int y = 0; y * SEL_T < rec[r].ncol; y++) ent.push_back(int4{ r, y, 0, 0 });
-        L.n_tr = (int)ent.size() - L.tr_off;
-        L.gm_off = (int)ent.size();
-        for (int r = r0; r < r1; r++)
-            if (rec[r].parent >= 0)
-                for (int y = 0; y * SEL_T < rec[r].ncol; y++) for (int i = 0; i * SEL_T < rec[r].u; i++) ent.push_back(int4{ r, i, y, 0 });
-        L.n_gm = (int)ent.size() - L.gm_off;
+        L.trsm = span_of(ent, [&] { for (int r = r0; r < r1; r++) for (int y = 0; y * SEL_T < rec[r].ncol; y++) ent.push_back(int4{ r, y, 0, 0 }); });
+        L.gemm = span_of(ent, [&] {
+            for (int r = r0; r < r1; r++)
+                if (rec[r].parent >= 0)
+                    for (int y = 0; y * SEL_T < rec[r].ncol; y++) for (int i = 0; i * SEL_T < rec[r].u; i++) ent.push_back(int4{ r, i, y, 0 });
+        });
         lev.push_back(L);
         r0 = r1;
     }
@@ -103,11 +99,9 @@ static void ps_chunk(Context &c, hipStream_t s, const std::vector<int> &nodes, c
     HIPCHECK(hipMemsetAsync(S.d_buf.p, 0, (size_t)used * 8, s));
     const PsFront *dfr = S.d_fr.p; const int4 *de = S.d_ent.p; const double *pool = c.d_pool.p; double *buf = S.d_buf.p;
     hipLaunchKernelGGL(k_path_init, dim3((unsigned)((at.size() + 255) / 256)), dim3(256), 0, s, (int)at.size(), (const long long *)S.d_at.p, buf);
-    auto waves = [](int n) { return dim3((unsigned)((n + 3) / 4)); };
     for (const Lev &L : lev) {
-        if (L.n_tr) hipLaunchKernelGGL(k_path_trsm, waves(L.n_tr), dim3(256), 0, s, dfr, de + L.tr_off, L.n_tr, pool, buf);
-        if (L.n_gm) hipLaunchKernelGGL(k_path_gemm, waves(L.n_gm), dim3(256), 0, s, dfr, de + L.gm_off, L.n_gm, pool, (const int *)c.d_i32.p,
-                                       (const int *)S.d_cmap.p, buf);
+        launch_waves(k_path_trsm, s, L.trsm, 1, dfr, de, pool, buf);
+        launch_waves(k_path_gemm, s, L.gemm, 1, dfr, de, pool, (const int *)c.d_i32.p, (const int *)S.d_cmap.p, buf);
     }
     hipLaunchKernelGGL(k_path_gram, dim3((unsigned)pairs.size()), dim3(256), 0, s, (const PsPair *)S.d_pair.p, (const PsPath *)S.d_path.p,
                        (const double *)buf, S.d_cov.p, S.h_out.p);

@@ -245,6 +245,15 @@ static void enqueue_families_before(GraphPack &gp, hipStream_t s, const double *
     enqueue_polar(gp, s);
 }
 
+// The one-wave-per-work-entry kernels of the retained-factor consumers (selinv.hip.h, pathsolve.hip.h, treesolve.hip.h): four waves per
+// workgroup over the entries of `sp`, times `column_tiles` in the grid's y (the tree solve's 16-column tiles; 1 elsewhere).  Every such
+// kernel starts with (fronts, entries, number of entries); `a` is what follows.  An empty span: no launch
+template <class K, class Fr, class E, class... Args>
+static void launch_waves(K kern, hipStream_t s, Span sp, unsigned column_tiles, const Fr *fr, const E *ent, const Args &...a) {
+    if (sp.n == 0) return;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((sp.n + 3) / 4), column_tiles), dim3(TPB), 0, s, fr, ent + sp.off, sp.n, a...);
+}
+
 // The kernels of polargate.hip.h, behind the path solves of a gating call: k_gate_polar runs one thread per candidate
 // (per_item = false: `work` candidates), k_associate_polar one workgroup per observation (per_item = true: `work` observations); `a` are the
 // kernel's arguments.  Nothing to gate: no launch

@@ -20,33 +20,23 @@ static void build_sel_tables(Context &c, hipStream_t s) {
         for (int t : fl) { fr[t].scr = scr; scr += (long long)sel_round16(fr[t].s) * (sel_round16(fr[t].s) + sel_round16(fr[t].u)); }
         scr_max = std::max(scr_max, scr);
         // (the tile loops below walk each front's tiles in a fixed order: the tables, not the hardware, decide who writes what)
-        L.gat_off = (int)ent.size();
-        for (int t : fl) if (fr[t].parent >= 0 && fr[t].u > 0) {
-            const long long nel = (long long)fr[t].u * fr[t].u;
-            for (long long ch = 0; ch * SEL_GATHER_PER_WG < nel; ch++) ent.push_back(int4{ t, (int)ch, 0, 0 });
-        }
-        L.n_gat = (int)ent.size() - L.gat_off;
-        L.diag_off = (int)ent.size();
-        for (int t : fl) for (int b = 0; b * SEL_T < fr[t].s; b++) ent.push_back(int4{ t, b, 0, 0 });
-        L.n_diag = (int)ent.size() - L.diag_off;
-        // (trinv: the longest chains -- column block 0 of the widest fronts -- first)
-        L.tri_off = (int)ent.size();
-        {
+        L.gat = span_of(ent, [&] {
+            for (int t : fl) if (fr[t].parent >= 0 && fr[t].u > 0) {
+                const long long nel = (long long)fr[t].u * fr[t].u;
+                for (long long ch = 0; ch * SEL_GATHER_PER_WG < nel; ch++) ent.push_back(int4{ t, (int)ch, 0, 0 });
+            }
+        });
+        L.diag = span_of(ent, [&] { for (int t : fl) for (int b = 0; b * SEL_T < fr[t].s; b++) ent.push_back(int4{ t, b, 0, 0 }); });
+        L.tri = span_of(ent, [&] {                          // (the longest chains -- column block 0 of the widest fronts -- first)
             std::vector<int4> tri;
             for (int t : fl) for (int b = 0; (b + 1) * SEL_T < fr[t].s; b++) tri.push_back(int4{ t, b, 0, 0 });
             std::stable_sort(tri.begin(), tri.end(), [&](const int4 &a, const int4 &b) { return fr[a.x].s - SEL_T * a.y > fr[b.x].s - SEL_T * b.y; });
             ent.insert(ent.end(), tri.begin(), tri.end());
-        }
-        L.n_tri = (int)ent.size() - L.tri_off;
-        L.x_off = (int)ent.size();
-        for (int t : fl) for (int j = 0; j * SEL_T < fr[t].s; j++) for (int i = 0; i * SEL_T < fr[t].u; i++) ent.push_back(int4{ t, i, j, 0 });
-        L.n_x = (int)ent.size() - L.x_off;
-        L.sus_off = (int)ent.size();
-        for (int t : fl) for (int j = 0; j * SEL_T < fr[t].s; j++) for (int i = 0; i * SEL_T < fr[t].u; i++) ent.push_back(int4{ t, i, j, 0 });
-        L.n_sus = (int)ent.size() - L.sus_off;
-        L.sss_off = (int)ent.size();
-        for (int t : fl) for (int j = 0; j * SEL_T < fr[t].s; j++) for (int i = j; i * SEL_T < fr[t].s; i++) ent.push_back(int4{ t, i, j, 0 });
-        L.n_sss = (int)ent.size() - L.sss_off;
+        });
+        auto us_tiles = [&] { for (int t : fl) for (int j = 0; j * SEL_T < fr[t].s; j++) for (int i = 0; i * SEL_T < fr[t].u; i++) ent.push_back(int4{ t, i, j, 0 }); };
+        L.x = span_of(ent, us_tiles);
+        L.sus = span_of(ent, us_tiles);
+        L.sss = span_of(ent, [&] { for (int t : fl) for (int j = 0; j * SEL_T < fr[t].s; j++) for (int i = j; i * SEL_T < fr[t].s; i++) ent.push_back(int4{ t, i, j, 0 }); });
     }
     if (ent.empty()) ent.push_back(int4{ 0, 0, 0, 0 });
     c.d_sel_fd.need(std::max<size_t>(1, fr.size())); c.d_sel_ent.need(ent.size());
@@ -63,14 +53,13 @@ static void enqueue_selinv(Context &c, hipStream_t s) {
     const SelFront *fr = c.d_sel_fd.p; const int4 *ent = c.d_sel_ent.p;
     const int *rel = c.d_i32.p;                             // (the block maps the factorisation read)
     double *sig = c.d_sigma.p, *scr = c.d_sel_scr.p; const double *pool = c.d_pool.p;
-    auto waves = [](int n) { return dim3((unsigned)((n + 3) / 4)); };
     for (const SelLevel &L : c.sel_levels) {
-        if (L.n_gat) hipLaunchKernelGGL(k_selinv_gather, dim3(L.n_gat), dim3(TPB), 0, s, fr, rel, ent + L.gat_off, sig);
-        if (L.n_diag) hipLaunchKernelGGL(k_selinv_diag, waves(L.n_diag), dim3(TPB), 0, s, fr, ent + L.diag_off, L.n_diag, pool, scr);
-        if (L.n_tri) hipLaunchKernelGGL(k_selinv_trinv, waves(L.n_tri), dim3(TPB), 0, s, fr, ent + L.tri_off, L.n_tri, pool, scr);
-        if (L.n_x) hipLaunchKernelGGL(k_selinv_x, waves(L.n_x), dim3(TPB), 0, s, fr, ent + L.x_off, L.n_x, pool, scr);
-        if (L.n_sus) hipLaunchKernelGGL(k_selinv_sus, waves(L.n_sus), dim3(TPB), 0, s, fr, ent + L.sus_off, L.n_sus, (const double *)scr, sig);
-        if (L.n_sss) hipLaunchKernelGGL(k_selinv_sss, waves(L.n_sss), dim3(TPB), 0, s, fr, ent + L.sss_off, L.n_sss, (const double *)scr, sig);
+        if (L.gat.n) hipLaunchKernelGGL(k_selinv_gather, dim3(L.gat.n), dim3(TPB), 0, s, fr, rel, ent + L.gat.off, sig);
+        launch_waves(k_selinv_diag, s, L.diag, 1, fr, ent, pool, scr);
+        launch_waves(k_selinv_trinv, s, L.tri, 1, fr, ent, pool, scr);
+        launch_waves(k_selinv_x, s, L.x, 1, fr, ent, pool, scr);
+        launch_waves(k_selinv_sus, s, L.sus, 1, fr, ent, (const double *)scr, sig);
+        launch_waves(k_selinv_sss, s, L.sss, 1, fr, ent, (const double *)scr, sig);
     }
     HIPCHECK(hipGetLastError());
 }

@@ -56,8 +56,6 @@ static const int *ts_tables(Context &c, hipStream_t s) {
                 cent[(size_t)fill[(size_t)T.wrow[F.parent] / 3 + rel[(size_t)F.rel_begin + a]]++] = TsKid{ T.wrow[t], F.s + F.u, F.s + 3 * a, 0 };
         }
     }
-    std::vector<TsFront> tf((size_t)std::max(nFr, 1));
-    for (int t = 0; t < nFr; t++) tf[t] = TsFront{ fr[t].first, T.wrow[t] / 3 };
     std::vector<int> npos((size_t)std::max(N, 1), 0);
     for (int i = 0; i < N; i++) {
         const int p = S.i32[i];
@@ -73,37 +71,23 @@ static const int *ts_tables(Context &c, hipStream_t s) {
     for (int l = 0; l < nLev; l++) {
         TsLevel &L = T.lev[l];
         const std::vector<int> &fl = S.lev[l];
-        L.asm_off = (int)ent.size();
-        for (int t : fl) for (int b = 0; b * TS_BAND < fr[t].s + fr[t].u; b++) ent.push_back(int2{ t, b });
-        L.n_asm = (int)ent.size() - L.asm_off;
-        L.tr_off = (int)ent.size();
-        {                                                   // (the longest chains first)
+        L.assemble = span_of(ent, [&] { for (int t : fl) for (int b = 0; b * TS_BAND < fr[t].s + fr[t].u; b++) ent.push_back(int2{ t, b }); });
+        L.trsm = span_of(ent, [&] {                         // (the longest chains first)
             std::vector<int> o(fl);
             std::stable_sort(o.begin(), o.end(), [&](int a, int b) { return fr[a].s > fr[b].s; });
             for (int t : o) ent.push_back(int2{ t, 0 });
-        }
-        L.n_tr = (int)ent.size() - L.tr_off;
-        L.gm_off = (int)ent.size();
-        for (int t : fl) for (int i = 0; i * SEL_T < fr[t].u; i++) ent.push_back(int2{ t, i });
-        L.n_gm = (int)ent.size() - L.gm_off;
-        L.gat_off = (int)ent.size();
-        for (int t : fl) if (fr[t].parent >= 0) for (int b = 0; b * TS_BAND < fr[t].u; b++) ent.push_back(int2{ t, b });
-        L.n_gat = (int)ent.size() - L.gat_off;
-        L.gt_off = (int)ent.size();
-        for (int t : fl) if (fr[t].u > 0) for (int i = 0; i * SEL_T < fr[t].s; i++) ent.push_back(int2{ t, i });
-        L.n_gt = (int)ent.size() - L.gt_off;
+        });
+        L.gemm = span_of(ent, [&] { for (int t : fl) for (int i = 0; i * SEL_T < fr[t].u; i++) ent.push_back(int2{ t, i }); });
+        L.gather = span_of(ent, [&] { for (int t : fl) if (fr[t].parent >= 0) for (int b = 0; b * TS_BAND < fr[t].u; b++) ent.push_back(int2{ t, b }); });
+        L.gemmt = span_of(ent, [&] { for (int t : fl) if (fr[t].u > 0) for (int i = 0; i * SEL_T < fr[t].s; i++) ent.push_back(int2{ t, i }); });
     }
     if (ent.empty()) ent.push_back(int2{ 0, 0 });
     std::vector<PsFront> pf((size_t)std::max(nFr, 1));
-    for (int t = 0; t < nFr; t++) {
-        const SelFront &F = fr[t];
-        pf[t] = PsFront{ F.off, T.wrow[t], F.s, F.u, F.R, 0, F.parent, F.rel_begin, 0, 0 };
-    }
-    T.d_fr.need(std::max<size_t>(1, (size_t)nFr)); T.d_tf.need(tf.size()); T.d_ent.need(ent.size()); T.d_cptr.need(cptr.size()); T.d_cent.need(cent.size());
+    for (int t = 0; t < nFr; t++) pf[t] = ps_front(fr[t], T.wrow[t], 0, fr[t].parent, 0);      // (buf: the first row; the column count is the kernels' argument)
+    T.d_fr.need(std::max<size_t>(1, (size_t)nFr)); T.d_ent.need(ent.size()); T.d_cptr.need(cptr.size()); T.d_cent.need(cent.size());
     T.d_npos.need(npos.size());
     const int *pos = view_pos(c, s);
     HIPCHECK(hipMemcpyAsync(T.d_fr.p, pf.data(), pf.size() * sizeof(PsFront), hipMemcpyHostToDevice, s));
-    HIPCHECK(hipMemcpyAsync(T.d_tf.p, tf.data(), tf.size() * sizeof(TsFront), hipMemcpyHostToDevice, s));
     HIPCHECK(hipMemcpyAsync(T.d_ent.p, ent.data(), ent.size() * sizeof(int2), hipMemcpyHostToDevice, s));
     HIPCHECK(hipMemcpyAsync(T.d_cptr.p, cptr.data(), cptr.size() * 4, hipMemcpyHostToDevice, s));
     HIPCHECK(hipMemcpyAsync(T.d_cent.p, cent.data(), cent.size() * sizeof(TsKid), hipMemcpyHostToDevice, s));
@@ -125,29 +109,30 @@ static int ts_chunk_cols(const TreeState &T, int ncol) {
 // left in the fronts' own rows of the work buffer (k_ts_store / k_cross_extract / k_relative_cov read it).
 static void ts_passes(Context &c, hipStream_t s, int mode, int ncol, const double *dB) {
     TreeState &T = c.ts;
-    const PsFront *fr = T.d_fr.p; const TsFront *tf = T.d_tf.p; const int2 *ent = T.d_ent.p;
+    const PsFront *fr = T.d_fr.p; const int2 *ent = T.d_ent.p;
     const double *pool = c.d_pool.p; double *buf = T.d_buf.p;
     const long long n3 = 3ll * c.view.N;
     const unsigned ct = (unsigned)((ncol + SEL_T - 1) / SEL_T);
-    auto waves = [&](int n) { return dim3((unsigned)((n + 3) / 4), ct); };
     const int nLev = (int)T.lev.size();
     const bool fwd = mode != APRILSAM_AMD_SOLVE_BACKWARD, bwd = mode != APRILSAM_AMD_SOLVE_FORWARD;
+    auto assemble = [&](const TsLevel &L, int kids) {
+        if (L.assemble.n) hipLaunchKernelGGL(k_ts_assemble, dim3(L.assemble.n), dim3(256), 0, s, fr, ent + L.assemble.off, (const int *)T.d_cptr.p, (const TsKid *)T.d_cent.p,
+                                             (const int *)T.d_npos.p, dB, n3, 1, kids, ncol, buf);
+    };
     if (fwd)
         for (int l = nLev - 1; l >= 0; l--) {
             const TsLevel &L = T.lev[l];
-            if (L.n_asm) hipLaunchKernelGGL(k_ts_assemble, dim3(L.n_asm), dim3(256), 0, s, fr, tf, ent + L.asm_off, (const int *)T.d_cptr.p, (const TsKid *)T.d_cent.p,
-                                            (const int *)T.d_npos.p, dB, n3, 1, 1, ncol, buf);
-            if (L.n_tr) hipLaunchKernelGGL(k_ts_trsm, waves(L.n_tr), dim3(256), 0, s, fr, ent + L.tr_off, L.n_tr, pool, ncol, buf);
-            if (L.n_gm) hipLaunchKernelGGL(k_ts_gemm, waves(L.n_gm), dim3(256), 0, s, fr, ent + L.gm_off, L.n_gm, pool, ncol, buf);
+            assemble(L, 1);
+            launch_waves(k_ts_trsm, s, L.trsm, ct, fr, ent, pool, ncol, buf);
+            launch_waves(k_ts_gemm, s, L.gemm, ct, fr, ent, pool, ncol, buf);
         }
     if (bwd)
         for (int l = 0; l < nLev; l++) {
             const TsLevel &L = T.lev[l];
-            if (!fwd && L.n_asm) hipLaunchKernelGGL(k_ts_assemble, dim3(L.n_asm), dim3(256), 0, s, fr, tf, ent + L.asm_off, (const int *)T.d_cptr.p,
-                                                    (const TsKid *)T.d_cent.p, (const int *)T.d_npos.p, dB, n3, 1, 0, ncol, buf);
-            if (L.n_gat) hipLaunchKernelGGL(k_ts_gather, dim3(L.n_gat), dim3(256), 0, s, fr, (const int *)c.d_i32.p, ent + L.gat_off, ncol, buf);
-            if (L.n_gt) hipLaunchKernelGGL(k_ts_gemmt, waves(L.n_gt), dim3(256), 0, s, fr, ent + L.gt_off, L.n_gt, pool, ncol, buf);
-            if (L.n_tr) hipLaunchKernelGGL(k_ts_trsmt, waves(L.n_tr), dim3(256), 0, s, fr, ent + L.tr_off, L.n_tr, pool, ncol, buf);
+            if (!fwd) assemble(L, 0);
+            if (L.gather.n) hipLaunchKernelGGL(k_ts_gather, dim3(L.gather.n), dim3(256), 0, s, fr, (const int *)c.d_i32.p, ent + L.gather.off, ncol, buf);
+            launch_waves(k_ts_gemmt, s, L.gemmt, ct, fr, ent, pool, ncol, buf);
+            launch_waves(k_ts_trsmt, s, L.trsm, ct, fr, ent, pool, ncol, buf);
         }
     HIPCHECK(hipGetLastError());
 }
@@ -185,7 +170,7 @@ static int solve_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int
         HIPCHECK(hipMemcpyAsync(T.d_B.p, T.h_B.p, 8 * n3 * nc, hipMemcpyHostToDevice, s));
         ts_passes(c, s, mode, nc, T.d_B.p);
         const long long nv = (long long)n3 * nc;
-        hipLaunchKernelGGL(k_ts_store, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, s, (const PsFront *)T.d_fr.p, (const TsFront *)T.d_tf.p,
+        hipLaunchKernelGGL(k_ts_store, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, s, (const PsFront *)T.d_fr.p,
                            pos, pos + N, (const double *)T.d_buf.p, N, nc, T.h_X.p);
         HIPCHECK(hipGetLastError());
         HIPCHECK(hipStreamSynchronize(s));
@@ -241,7 +226,7 @@ static int cross_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int
     TreeState &T = q.c().ts;
     hipStream_t s = q.stream();
     hipLaunchKernelGGL(k_cross_extract, dim3((unsigned)((9ll * n + 255) / 256)), dim3(256), 0, s, n, nodes ? (const int *)T.d_nodes.p : (const int *)nullptr,
-                       (const PsFront *)T.d_fr.p, (const TsFront *)T.d_tf.p, pos, pos + q.N(), (const double *)T.d_buf.p, T.h_X.p);
+                       (const PsFront *)T.d_fr.p, pos, pos + q.N(), (const double *)T.d_buf.p, T.h_X.p);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(s));
     memcpy(cov, T.h_X.p, (size_t)8 * 9 * n);
@@ -265,7 +250,7 @@ static int relative_impl(april_graph_t *g, april_graph_cholesky_param_t *param, 
     T.d_st.need(st.size());
     HIPCHECK(hipMemcpyAsync(T.d_st.p, st.data(), 8 * st.size(), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_relative_cov, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, nodes ? (const int *)T.d_nodes.p : (const int *)nullptr, anchor,
-                       (const double *)T.d_st.p, (const double *)T.d_st.p + 3, (const PsFront *)T.d_fr.p, (const TsFront *)T.d_tf.p, pos,
+                       (const double *)T.d_st.p, (const double *)T.d_st.p + 3, (const PsFront *)T.d_fr.p, pos,
                        pos + q.N(), (const double *)T.d_buf.p, (const double *)c.d_sigma.p, T.h_X.p);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(s));
