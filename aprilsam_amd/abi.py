@@ -153,6 +153,9 @@ FACTOR_GAUSSIAN_TYPE = 5
 GAUSSIAN_MAX_NODES = 11
 MARGINAL_MAX_NODES = 40        # aprilsam_amd_marginal_prior: removed nodes + blanket nodes
 
+# joint compatibility gating (include/aprilsam_amd.h: aprilsam_amd_gate_xyt_joint): candidates per hypothesis
+JOINT_MAX = 16
+
 # measured LP64 layout of the reference; checked by tests/test_abi.py
 EXPECTED_SIZES = {"ZArray": 24, "Graph": 32, "Factor": 104, "Node": 112, "CholeskyParam": 128}
 EXPECTED_OFFSETS = {

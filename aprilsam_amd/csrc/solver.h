@@ -105,6 +105,9 @@ int marginals(april_graph_t *g, april_graph_cholesky_param_t *param, int n, cons
 long long selinv_runs(const april_graph_cholesky_param_t *param);
 int marginals_joint_any(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, double *cov);      // solver_gating.inc.h
 int gate_xyt(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, const double *z, const double *W, double *d2, double *S);
+int marginals_set(april_graph_t *g, april_graph_cholesky_param_t *param, int k, const int *nodes, double *cov);
+int gate_xyt_joint(april_graph_t *g, april_graph_cholesky_param_t *param, int n_hyp, const int *hyp_ptr, const int *a, const int *b, const double *z,
+                   const double *W, double *d2_prefix, double *C);
 int gate_polar(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, const int *kind, const double *z, const double *W,
                double *d2, double *S);
 int associate_polar(april_graph_t *g, april_graph_cholesky_param_t *param, int observer, int m, const int *kind, const double *z, const double *W, int L,

@@ -41,6 +41,7 @@
 #include "audit.hip.h"
 #include "pathsolve.hip.h"
 #include "polargate.hip.h"
+#include "jointgate.hip.h"
 #include "treesolve.hip.h"
 #include "plan.h"
 #include "refmodel.h"
@@ -541,6 +542,13 @@ extern "C" int aprilsam_amd_marginals_joint_any(april_graph_t *graph, april_grap
 extern "C" int aprilsam_amd_gate_xyt(april_graph_t *graph, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, const double *z,
                                      const double *W, double *d2, double *S) {
     return asam::gate_xyt(graph, param, n, a, b, z, W, d2, S);
+}
+extern "C" int aprilsam_amd_marginals_set(april_graph_t *graph, april_graph_cholesky_param_t *param, int k, const int *nodes, double *cov) {
+    return asam::marginals_set(graph, param, k, nodes, cov);
+}
+extern "C" int aprilsam_amd_gate_xyt_joint(april_graph_t *graph, april_graph_cholesky_param_t *param, int n_hyp, const int *hyp_ptr, const int *a, const int *b,
+                                           const double *z, const double *W, double *d2_prefix, double *C) {
+    return asam::gate_xyt_joint(graph, param, n_hyp, hyp_ptr, a, b, z, W, d2_prefix, C);
 }
 extern "C" int aprilsam_amd_gate_polar(april_graph_t *graph, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, const int *kind,
                                        const double *z, const double *W, double *d2, double *S) {

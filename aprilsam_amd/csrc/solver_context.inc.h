@@ -99,9 +99,10 @@ struct PathState {
     DBuf<PsFront> d_fr; DBuf<int4> d_ent; DBuf<int> d_cmap; DBuf<long long> d_at; DBuf<PsPath> d_path; DBuf<PsPair> d_pair;
     DBuf<double> d_buf, d_cov, d_in; HBuf<double> h_out;
     DBuf<int> d_pidx;                      // k_gate_polar: candidate -> its pair's block in d_cov
+    DBuf<int> d_jtab; DBuf<long long> d_joff;      // k_gate_xyt_joint: hyp_ptr | tab_ptr | the index table; the matrices' offsets
     long long peak_doubles = 0;            // the largest work buffer a chunk has used
     void release() {
-        d_fr.release(); d_ent.release(); d_cmap.release(); d_at.release(); d_path.release(); d_pair.release(); d_buf.release(); d_cov.release(); d_in.release(); h_out.release(); d_pidx.release();
+        d_fr.release(); d_ent.release(); d_cmap.release(); d_at.release(); d_path.release(); d_pair.release(); d_buf.release(); d_cov.release(); d_in.release(); h_out.release(); d_pidx.release(); d_jtab.release(); d_joff.release();
         rec.clear(); node_j.clear(); gen = -1;
     }
 };

@@ -1,8 +1,10 @@
 // solver_gating.inc.h -- part of solver.hip.cpp (ONE translation unit); included from there, inside namespace asam.
 // Contents: aprilsam_amd_marginals_joint_any / aprilsam_amd_gate_xyt: joint covariances of any pose pairs from the retained factor
 // by triangular solves along assembly-tree paths (pathsolve.hip.h), and the Mahalanobis gating of candidate xyt measurements.
-// DESIGN.md section 13.  aprilsam_amd_gate_polar / aprilsam_amd_associate_polar: the same for range / bearing / range-bearing measurements,
-// and their nearest-neighbour association against landmarks (polargate.hip.h).  DESIGN.md section 21.
+// DESIGN.md section 13.  aprilsam_amd_marginals_set / aprilsam_amd_gate_xyt_joint: the dense joint covariance of a node set and the joint
+// compatibility gating of closure hypotheses (jointgate.hip.h).  DESIGN.md section 29.  aprilsam_amd_gate_polar / aprilsam_amd_associate_polar:
+// the gate for range / bearing / range-bearing measurements, and their nearest-neighbour association against landmarks (polargate.hip.h).
+// DESIGN.md section 21.
 // Admission, refusals, the guard and the structure the factor lives in: solver_query.inc.h (RetainedQuery, FactorView).
 // ------------------------------------------------------------------------------------------------------
 // doubles of work buffer node q's three columns take: 3 (s + u) summed over its path
@@ -197,6 +199,18 @@ static int joint_any_impl(april_graph_t *g, april_graph_cholesky_param_t *param,
     return 0;
 }
 
+// a candidate's information matrix (3 x 3, row-major): symmetric (mirror entries equal) and positive definite: a Cholesky factorisation
+static const char *const XYT_INFO_MSG = "an information matrix that is not symmetric positive definite";
+static bool xyt_info_spd(const double *w) {
+    bool ok = w[1] == w[3] && w[2] == w[6] && w[5] == w[7];
+    const double l00 = w[0] > 0 ? sqrt(w[0]) : 0;
+    ok = ok && l00 > 0;
+    const double l10 = ok ? w[3] / l00 : 0, l20 = ok ? w[6] / l00 : 0, p1 = w[4] - l10 * l10;
+    ok = ok && p1 > 0;
+    const double l11 = ok ? sqrt(p1) : 0, l21 = ok ? (w[7] - l20 * l10) / l11 : 0, p2 = w[8] - l20 * l20 - l21 * l21;
+    return ok && p2 > 0;
+}
+
 static int gate_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *qa, const int *qb, const double *z, const double *W,
                      double *d2, double *Sout) {
     const char *who = "aprilsam_amd_gate_xyt";
@@ -210,17 +224,8 @@ static int gate_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int 
         for (int k = 0; k < 3; k++) if (!std::isfinite(z[3 * i + k])) return q.refuse(ERR_BAD_GRAPH, "a non-finite measurement");
         for (int k = 0; k < 9; k++) if (!std::isfinite(W[9 * i + k])) return q.refuse(ERR_BAD_GRAPH, "a non-finite information matrix");
     }
-    for (int i = 0; i < n; i++) {                           // symmetric (mirror entries equal) and positive definite: a Cholesky factorisation
-        const double *w = W + 9 * i;
-        bool ok = w[1] == w[3] && w[2] == w[6] && w[5] == w[7];
-        const double l00 = w[0] > 0 ? sqrt(w[0]) : 0;
-        ok = ok && l00 > 0;
-        const double l10 = ok ? w[3] / l00 : 0, l20 = ok ? w[6] / l00 : 0, p1 = w[4] - l10 * l10;
-        ok = ok && p1 > 0;
-        const double l11 = ok ? sqrt(p1) : 0, l21 = ok ? (w[7] - l20 * l10) / l11 : 0, p2 = w[8] - l20 * l20 - l21 * l21;
-        ok = ok && p2 > 0;
-        if (!ok) return q.refuse(ERR_UNSUPPORTED, "an information matrix that is not symmetric positive definite");
-    }
+    for (int i = 0; i < n; i++)
+        if (!xyt_info_spd(W + 9 * i)) return q.refuse(ERR_UNSUPPORTED, "%s", XYT_INFO_MSG);
     if (n == 0) return 0;
     std::vector<double> in((size_t)18 * n);
     april_graph_node_t **ns = (april_graph_node_t **)g->nodes->data;
@@ -234,6 +239,161 @@ static int gate_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int 
     memcpy(d2, o, (size_t)8 * n);
     if (Sout) memcpy(Sout, o + n, (size_t)8 * 9 * n);
     return 0;
+}
+
+// ---- node sets and joint compatibility ---------------------------------------------------------------------------
+// The distinct unordered node pairs of one call, each solved once: slot s holds the 6 x 6 block of (ua[s], ub[s]) in the order it was first
+// asked for.  code(x, y) = 4 slot + quarter names the 3 x 3 block S(p, q) inside it (k_gate_xyt_joint's table entry) for the call's distinct
+// nodes p = un[x], q = un[y]: quarter 1 the pair as stored, 2 the pair the other way round, 0 / 3 a node's own block -- taken from the
+// first pair that named the node.  The codes of all ordered index pairs lie in a table of nu x nu entries while the call names at most
+// DENSE_MAX distinct nodes (a branch-and-bound level shares a few tens of nodes among its hypotheses: one array read per entry of the
+// kernel's index table), in a hash map beyond.
+static_assert(JG_MAX == APRILSAM_AMD_JOINT_MAX, "k_gate_xyt_joint's LDS is sized for the header's limit");
+struct PairBook {
+    static constexpr int DENSE_MAX = 1024;
+    std::vector<int> un, ua, ub;                             // the distinct nodes, ascending; slot -> its pair (node ids)
+    std::vector<int> dense;
+    std::unordered_map<long long, int> sparse;
+    // the nodes of the call: ids[0..n) and, if not null, more[0..n)
+    PairBook(int n, const int *ids, const int *more) : un(ids, ids + n) {
+        if (more) un.insert(un.end(), more, more + n);
+        std::sort(un.begin(), un.end());
+        un.erase(std::unique(un.begin(), un.end()), un.end());
+        if (un.size() <= (size_t)DENSE_MAX) dense.assign(un.size() * un.size(), -1);
+    }
+    int index(int node) const { return (int)(std::lower_bound(un.begin(), un.end(), node) - un.begin()); }
+    int code(int x, int y) const {
+        if (!dense.empty()) return dense[(size_t)x * un.size() + y];
+        auto it = sparse.find(((long long)x << 32) | (unsigned)y);
+        return it == sparse.end() ? -1 : it->second;
+    }
+    void set(int x, int y, int v) {
+        if (!dense.empty()) dense[(size_t)x * un.size() + y] = v;
+        else sparse[((long long)x << 32) | (unsigned)y] = v;
+    }
+    void add(int x, int y) {
+        if (code(x, y) >= 0) return;
+        if (ua.size() >= (size_t)(0x7fffffff / 36)) fail(ERR_OOM, "more distinct node pairs than one call can hold");
+        const int s4 = 4 * (int)ua.size();
+        ua.push_back(un[x]); ub.push_back(un[y]);
+        if (x != y) { set(x, y, s4 + 1); set(y, x, s4 + 2); }
+        if (code(x, x) < 0) set(x, x, s4);
+        if (code(y, y) < 0) set(y, y, s4 + 3);
+    }
+    int n() const { return (int)ua.size(); }
+};
+
+// dense joint covariance of the k listed nodes: every distinct node solved once, every distinct unordered pair through k_path_gram once
+static int marginals_set_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int k, const int *nodes, double *cov) {
+    const char *who = "aprilsam_amd_marginals_set";
+    if (!param || k < 0 || (k > 0 && (!nodes || !cov))) return refuse(ERR_BAD_GRAPH, who, "null argument or negative count");
+    RetainedQuery q(who, g, param);
+    if (int rc = q.admit()) return rc;
+    Context &c = q.c();
+    const int N = q.N();
+    for (int i = 0; i < k; i++) if (nodes[i] < 0 || nodes[i] >= N) return q.refuse(ERR_BAD_GRAPH, "%s", PS_RANGE_MSG);
+    if (k == 0) return 0;
+    PairBook B(k, nodes, nullptr);
+    const int nu = (int)B.un.size();
+    if (nu == 1) B.add(0, 0);
+    for (int x = 0; x < nu; x++) for (int y = x + 1; y < nu; y++) B.add(x, y);
+    ps_run(c, q.stream(), B.n(), B.ua.data(), B.ub.data(), nullptr);
+    std::vector<int> ix((size_t)k);
+    for (int i = 0; i < k; i++) ix[i] = B.index(nodes[i]);
+    const double *o = c.ps.h_out.p;
+    const size_t ld = (size_t)3 * k;
+    for (int i = 0; i < k; i++)
+        for (int j = 0; j < k; j++) {
+            const int code = B.code(ix[i], ix[j]), ro = (code & 2) ? 3 : 0, co = (code & 1) ? 3 : 0;
+            const double *blk = o + (size_t)36 * (code >> 2);
+            for (int x = 0; x < 3; x++) for (int y = 0; y < 3; y++) cov[(3 * i + x) * ld + 3 * j + y] = blk[6 * (ro + x) + co + y];
+        }
+    return 0;
+}
+
+// n_hyp hypotheses (CSR hyp_ptr into a / b / z / W): nodes, then unordered node pairs, deduplicated across the whole call; k_gate_xyt_joint
+// behind the blocks.  What the checks can judge without the graph comes before the device is asked for.
+static int gate_joint_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int n_hyp, const int *hyp_ptr, const int *qa, const int *qb, const double *z,
+                           const double *W, double *d2, double *Cout) {
+    const char *who = "aprilsam_amd_gate_xyt_joint";
+    if (!g || !param || !hyp_ptr || !qa || !qb || !z || !W || !d2 || n_hyp < 0) return refuse(ERR_BAD_GRAPH, who, "null argument or negative count");
+    if (hyp_ptr[0] != 0) return refuse(ERR_BAD_GRAPH, who, "hyp_ptr does not start at 0");
+    for (int h = 0; h < n_hyp; h++) {
+        const long long m = (long long)hyp_ptr[h + 1] - hyp_ptr[h];
+        if (m < 0) return refuse(ERR_BAD_GRAPH, who, "hyp_ptr decreases at hypothesis %d", h);
+        if (m < 1 || m > APRILSAM_AMD_JOINT_MAX)
+            return refuse(ERR_BAD_GRAPH, who, "hypothesis %d has %lld candidates (1 to %d are allowed)", h, m, APRILSAM_AMD_JOINT_MAX);
+    }
+    const int n = hyp_ptr[n_hyp];
+    for (int i = 0; i < n; i++) {
+        if (qa[i] == qb[i]) return refuse(ERR_BAD_GRAPH, who, "a candidate joins a node to itself");
+        for (int k = 0; k < 3; k++) if (!std::isfinite(z[3 * (size_t)i + k])) return refuse(ERR_BAD_GRAPH, who, "a non-finite measurement");
+        for (int k = 0; k < 9; k++) if (!std::isfinite(W[9 * (size_t)i + k])) return refuse(ERR_BAD_GRAPH, who, "a non-finite information matrix");
+    }
+    for (int i = 0; i < n; i++) if (!xyt_info_spd(W + 9 * (size_t)i)) return refuse(ERR_UNSUPPORTED, who, "%s", XYT_INFO_MSG);
+    RetainedQuery q(who, g, param);
+    if (int rc = q.admit()) return rc;
+    Context &c = q.c();
+    if (!ps_ids_ok(q, n, qa) || !ps_ids_ok(q, n, qb)) return q.refuse(ERR_BAD_GRAPH, "%s", PS_RANGE_MSG);
+    if (n_hyp == 0) return 0;
+    PairBook B(n, qa, qb);
+    std::vector<int> xa((size_t)n), xb((size_t)n);          // the candidates' nodes as indices into B.un
+    for (int i = 0; i < n; i++) { xa[i] = B.index(qa[i]); xb[i] = B.index(qb[i]); }
+    for (int i = 0; i < n; i++) B.add(xa[i], xb[i]);       // (first: every node's own block comes from a candidate's own pair)
+    for (int h = 0; h < n_hyp; h++)
+        for (int i = hyp_ptr[h]; i < hyp_ptr[h + 1]; i++)
+            for (int j = hyp_ptr[h]; j < i; j++)
+                for (int e = 0; e < 4; e++) {
+                    const int x = (e & 2) ? xb[i] : xa[i], y = (e & 1) ? xb[j] : xa[j];
+                    if (x != y) B.add(x, y);
+                }
+    // hyp_ptr | tab_ptr | the table: per hypothesis and lower block (i, j) the four entries S(a_i,a_j), S(a_i,b_j), S(b_i,a_j), S(b_i,b_j)
+    std::vector<int> tab((size_t)2 * (n_hyp + 1));
+    std::vector<long long> coff((size_t)n_hyp);
+    long long nC = 0, nT = 0;
+    for (int h = 0; h < n_hyp; h++) {
+        const long long m = hyp_ptr[h + 1] - hyp_ptr[h];
+        coff[h] = nC; nC += 9 * m * m;
+        tab[h] = hyp_ptr[h]; tab[(size_t)n_hyp + 1 + h] = (int)nT; nT += 2 * m * (m + 1);
+        if (nT > 0x7fffffff) fail(ERR_OOM, "the index table of %d hypotheses does not fit", n_hyp);
+    }
+    tab[n_hyp] = n; tab[(size_t)2 * n_hyp + 1] = (int)nT;
+    tab.reserve(tab.size() + (size_t)nT);
+    for (int h = 0; h < n_hyp; h++)
+        for (int i = hyp_ptr[h]; i < hyp_ptr[h + 1]; i++)
+            for (int j = hyp_ptr[h]; j <= i; j++) {
+                // i == j: the four quarters of the candidate's own pair's block, turned round if the pair is stored as (b, a)
+                const int own = B.code(xa[i], xb[i]), own0 = own & ~3, sw = (own & 3) == 1 ? 0 : 3;
+                for (int e = 0; e < 4; e++) tab.push_back(i == j ? own0 + (e ^ sw) : B.code((e & 2) ? xb[i] : xa[i], (e & 1) ? xb[j] : xa[j]));
+            }
+    std::vector<double> in((size_t)18 * n);
+    april_graph_node_t **ns = (april_graph_node_t **)g->nodes->data;
+    for (int i = 0; i < n; i++) {
+        double *v = in.data() + (size_t)18 * i;
+        for (int k = 0; k < 3; k++) { v[k] = ns[qa[i]]->state[k]; v[3 + k] = ns[qb[i]]->state[k]; v[6 + k] = z[3 * (size_t)i + k]; }
+        for (int k = 0; k < 9; k++) v[9 + k] = W[9 * (size_t)i + k];
+    }
+    PathState &S = c.ps;
+    const int np = B.n();
+    PsTail tail;
+    tail.extra = (size_t)n + n_hyp + (Cout ? (size_t)nC : 0);         // the prefixes, the hypotheses' flags, the matrices
+    tail.enqueue = [&](hipStream_t st) {
+        S.d_in.need(in.size()); S.d_jtab.need(tab.size()); S.d_joff.need(coff.size());
+        HIPCHECK(hipMemcpyAsync(S.d_in.p, in.data(), in.size() * 8, hipMemcpyHostToDevice, st));
+        HIPCHECK(hipMemcpyAsync(S.d_jtab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st));
+        HIPCHECK(hipMemcpyAsync(S.d_joff.p, coff.data(), coff.size() * 8, hipMemcpyHostToDevice, st));
+        double *o = S.h_out.p + (size_t)36 * np;
+        const int *t = S.d_jtab.p;
+        hipLaunchKernelGGL(k_gate_xyt_joint, dim3((unsigned)n_hyp), dim3(JG_T), 0, st, n_hyp, t, t + n_hyp + 1, t + 2 * (n_hyp + 1), (const long long *)S.d_joff.p,
+                           (const double *)S.d_in.p, np, (const double *)S.d_cov.p, o, o + n, Cout ? o + n + n_hyp : (double *)nullptr);
+    };
+    ps_run(c, q.stream(), np, B.ua.data(), B.ub.data(), nullptr, &tail);
+    const double *o = S.h_out.p + (size_t)36 * np;
+    memcpy(d2, o, (size_t)8 * n);
+    if (Cout) memcpy(Cout, o + n + n_hyp, (size_t)8 * nC);
+    int bad = 0;
+    for (int h = 0; h < n_hyp; h++) bad += o[n + h] != 0.0;
+    return bad;
 }
 
 // ---- polar gates ----------------------------------------------------------------------------------------------
@@ -345,6 +505,13 @@ int marginals_joint_any(april_graph_t *g, april_graph_cholesky_param_t *param, i
 }
 int gate_xyt(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, const double *z, const double *W, double *d2, double *S) {
     return query_guard([&] { return gate_impl(g, param, n, a, b, z, W, d2, S); });
+}
+int marginals_set(april_graph_t *g, april_graph_cholesky_param_t *param, int k, const int *nodes, double *cov) {
+    return query_guard([&] { return marginals_set_impl(g, param, k, nodes, cov); });
+}
+int gate_xyt_joint(april_graph_t *g, april_graph_cholesky_param_t *param, int n_hyp, const int *hyp_ptr, const int *a, const int *b, const double *z,
+                   const double *W, double *d2_prefix, double *C) {
+    return query_guard([&] { return gate_joint_impl(g, param, n_hyp, hyp_ptr, a, b, z, W, d2_prefix, C); });
 }
 int gate_polar(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, const int *kind, const double *z, const double *W,
                double *d2, double *S) {

@@ -154,6 +154,9 @@ class SolverLib:
                 d.aprilsam_amd_gate_xyt.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.c_int, _ip, _ip, _dp, _dp, _dp, _dp]
                 d.aprilsam_amd_debug_path_solve_bytes.argtypes = [C.POINTER(abi.CholeskyParam)]
                 d.aprilsam_amd_debug_path_solve_bytes.restype = C.c_longlong
+            if hasattr(d, "aprilsam_amd_gate_xyt_joint"):         # (defined in the HIP translation unit)
+                d.aprilsam_amd_marginals_set.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.c_int, _ip, _dp]
+                d.aprilsam_amd_gate_xyt_joint.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.c_int, _ip, _ip, _ip, _dp, _dp, _dp, _dp]
             if hasattr(d, "aprilsam_amd_solve"):                  # (defined in the HIP translation unit)
                 d.aprilsam_amd_solve.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.c_int, C.c_int, _dp, _dp]
                 for nm in ("aprilsam_amd_marginals_cross", "aprilsam_amd_relative_covariances"):
@@ -778,6 +781,36 @@ class Graph:
         if rc < 0:
             raise MarginalsError(rc, self.lib.last_error())
         return d2, S
+
+    def marginals_set(self, param, nodes):
+        """[3k, 3k] dense joint covariance of the k listed nodes, node i's unknowns at rows / columns 3i..3i+2 (include/aprilsam_amd.h:
+        aprilsam_amd_marginals_set).  Raises MarginalsError(rc) on a negative return."""
+        idx = np.ascontiguousarray(nodes, dtype=np.int32).ravel()
+        k = len(idx)
+        out = np.empty((3 * k, 3 * k))
+        rc = self.lib.dll.aprilsam_amd_marginals_set(self.ptr, param.ptr, k, _np_i(idx), _np_d(out))
+        if rc < 0:
+            raise MarginalsError(rc, self.lib.last_error())
+        return out
+
+    def gate_xyt_joint(self, param, hyps):
+        """Joint compatibility gating (include/aprilsam_amd.h: aprilsam_amd_gate_xyt_joint).  hyps: a list of hypotheses, each a tuple
+        (a [m], b [m], z [m, 3], W [m, 3, 3] or [m, 9]) of candidate xyt measurements.  Returns (bad, [d2_prefix [m] per hypothesis],
+        [C [3m, 3m] per hypothesis]); bad counts the hypotheses with a pivot that was not positive.  Raises MarginalsError(rc) on a
+        negative return."""
+        ms = [len(np.atleast_1d(h[0])) for h in hyps]
+        ptr = np.concatenate([[0], np.cumsum(ms)]).astype(np.int32)
+        n = int(ptr[-1])
+        cat = lambda k, dt, w: np.ascontiguousarray(np.concatenate([np.asarray(h[k], dt).reshape(-1, w) for h in hyps]) if hyps else np.zeros((0, w), dt))
+        a, b, z, W = cat(0, np.int32, 1).ravel(), cat(1, np.int32, 1).ravel(), cat(2, float, 3), cat(3, float, 9)
+        if not (len(a) == len(b) == len(z) == len(W) == n):
+            raise ValueError("a, b, z and W of a hypothesis must have the same length")
+        d2 = np.empty(n); Cm = np.empty(int(sum(9 * m * m for m in ms)))
+        rc = self.lib.dll.aprilsam_amd_gate_xyt_joint(self.ptr, param.ptr, len(hyps), _np_i(ptr), _np_i(a), _np_i(b), _np_d(z), _np_d(W), _np_d(d2), _np_d(Cm))
+        if rc < 0:
+            raise MarginalsError(rc, self.lib.last_error())
+        off = np.concatenate([[0], np.cumsum([9 * m * m for m in ms])]).astype(np.int64)
+        return rc, [d2[ptr[h]:ptr[h + 1]] for h in range(len(hyps))], [Cm[off[h]:off[h + 1]].reshape(3 * m, 3 * m) for h, m in enumerate(ms)]
 
     def gate_polar(self, param, a, b, kind, z, W):
         """Mahalanobis gating of candidate polar measurements (include/aprilsam_amd.h: aprilsam_amd_gate_polar): kind [n], z [n, 2], W [n, 4]

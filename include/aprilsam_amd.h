@@ -503,6 +503,41 @@ int aprilsam_amd_marginals_joint_any(april_graph_t *graph, april_graph_cholesky_
  * argument.  Nothing is written on a refusal. */
 int aprilsam_amd_gate_xyt(april_graph_t *graph, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, const double *z,
                           const double *W, double *d2, double *S);
+/* ---- node sets and joint compatibility of closure hypotheses ----------------------------------------------------
+ * aprilsam_amd_marginals_set: the dense joint covariance of the k listed nodes, cov (3k) x (3k) row-major, node i's unknowns at rows /
+ * columns 3i..3i+2, of the same system as aprilsam_amd_marginals_joint_any.  Any k >= 0 (k == 0 returns 0 and writes nothing); a node may
+ * be listed more than once, its blocks repeat.  Every distinct node is solved once, every distinct unordered pair goes through the path
+ * solves' block kernel once (work buffer chunked as for _joint_any): block (i, j) equals _joint_any's S_ab of the pair (nodes[i], nodes[j])
+ * bit for bit, the matrix is exactly symmetric, blocks across the components of a disconnected graph are exactly 0.0, the rows and columns
+ * of a fixed node are exact zeros.  Returns 0 or _joint_any's codes; -11 when a buffer does not fit under option mem_cap_mb.
+ *
+ * aprilsam_amd_gate_xyt_joint: the joint compatibility test (Neira and Tardos) of n_hyp hypotheses, each a list of 1 .. APRILSAM_AMD_JOINT_MAX
+ * candidate xyt measurements as aprilsam_amd_gate_xyt takes them; hyp_ptr (n_hyp + 1 entries, hyp_ptr[0] == 0, CSR) indexes a / b / z / W.
+ * Per hypothesis with candidates i = 0 .. m - 1, on the GPU behind the path solves:
+ *     r_i, J_ai, J_bi    exactly as aprilsam_amd_gate_xyt: residual (theta wrapped) and Jacobians at the nodes' CURRENT states
+ *     C = H Sigma_set H' + blockdiag(W_i^-1)     (3m x 3m; H holds J_ai, J_bi in the columns of a_i, b_i; Sigma_set: the joint covariance
+ *                        of the hypothesis's distinct nodes, at the l_points of the last solver call).  Block (i, j) =
+ *                        J_ai S(a_i,a_j) J_aj' + J_ai S(a_i,b_j) J_bj' + J_bi S(b_i,a_j) J_aj' + J_bi S(b_i,b_j) J_bj'
+ *     C = L L', y = L^-1 r;  d2_prefix[hyp_ptr[h] + j] = sum of y_t^2 over t < 3 (j + 1)
+ * Entry j is the joint distance of the hypothesis's first j + 1 candidates (compare with a chi^2 quantile of 3 (j + 1) degrees of freedom:
+ * 16.27, 22.46, 27.88, 32.91 at 0.999 for 3, 6, 9, 12), the last entry the whole hypothesis's, the difference of consecutive entries
+ * candidate j's distance conditioned on its predecessors: one call evaluates a whole branch of a branch-and-bound search, many hypotheses
+ * one level of it.  Candidates may share nodes or repeat a pair, as (a, b) or as (b, a), also within one hypothesis.  Nodes, then unordered
+ * node pairs, are deduplicated across ALL hypotheses of the call: a pair is solved once per call.  C, when not NULL, receives every
+ * hypothesis's matrix, row-major and exactly symmetric, packed one after another (hypothesis h starts at the sum of 9 m_g^2 over g < h).
+ * Two calls give the same bits; a hypothesis cut to its first j candidates and sent as a hypothesis of the same call reproduces prefix j
+ * bit for bit; a one-candidate hypothesis agrees with aprilsam_amd_gate_xyt to rounding.
+ * Returns 0, or the number of hypotheses in which a pivot of C was not positive (their d2_prefix entries are NaN from that candidate on;
+ * W^-1 being positive definite this does not happen in exact arithmetic), or the codes of aprilsam_amd_gate_xyt: -1 no retained factor or
+ * a resident run in progress; -12 sharded param, asymmetric W in the factorised graph, a candidate W that is not symmetric positive
+ * definite; -13 a null argument, n_hyp < 0, a hyp_ptr that does not start at 0 or decreases, a hypothesis with 0 or more than
+ * APRILSAM_AMD_JOINT_MAX candidates, a == b, a non-finite z or W, a node id out of range of the factorised system or of graph; -14 no HIP
+ * device; -11 a buffer that does not fit under option mem_cap_mb.  What needs neither graph nor device (everything but the node ids) is
+ * judged before a device is asked for.  n_hyp == 0 returns 0.  A refusal writes nothing and leaves plan, factor and Sigma in place. */
+#define APRILSAM_AMD_JOINT_MAX 16      /* candidates per hypothesis */
+int aprilsam_amd_marginals_set(april_graph_t *graph, april_graph_cholesky_param_t *param, int k, const int *nodes, double *cov);
+int aprilsam_amd_gate_xyt_joint(april_graph_t *graph, april_graph_cholesky_param_t *param, int n_hyp, const int *hyp_ptr, const int *a, const int *b,
+                                const double *z, const double *W, double *d2_prefix, double *C);
 /* debug: the largest path-solve work buffer this param has used, in bytes (-1: no context) */
 long long aprilsam_amd_debug_path_solve_bytes(const april_graph_cholesky_param_t *param);
 
