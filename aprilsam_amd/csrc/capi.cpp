@@ -18,6 +18,8 @@
 // the host sources against a stub file that does not know the call (tools/sanitize_host.sh with an older tests/support/solver_nodevice.cpp)
 // still links.
 namespace asam { __attribute__((weak)) int debug_front_forms(const april_graph_cholesky_param_t *, int *, int) { return -1; } }
+// ... and of "no incremental call yet" for aprilsam_amd_debug_inc_forms, for the same reason
+namespace asam { __attribute__((weak)) int debug_inc_forms(const april_graph_cholesky_param_t *, int *, int) { return -1; } }
 
 extern "C" {
 
@@ -89,6 +91,7 @@ int aprilsam_amd_kernel_profile(const april_graph_cholesky_param_t *param, doubl
 int aprilsam_amd_debug_stage(april_graph_t *graph, april_graph_cholesky_param_t *param, int what, double *out) { return asam::debug_stage(graph, param, what, out); }
 int aprilsam_amd_debug_front_times(const april_graph_cholesky_param_t *param, long long *out, int n_fronts) { return asam::debug_front_times(param, out, n_fronts); }
 int aprilsam_amd_debug_front_forms(const april_graph_cholesky_param_t *param, int *out, int cap) { return asam::debug_front_forms(param, out, cap); }
+int aprilsam_amd_debug_inc_forms(const april_graph_cholesky_param_t *param, int *out, int cap) { return asam::debug_inc_forms(param, out, cap); }
 // host logic, no GPU: the reference's elimination order (aprilsam.c:999-1249 restated) and block elimination
 // tree for a graph given as factor endpoint arrays; out_order / out_parent: n_nodes ints each
 int aprilsam_amd_reference_order(int n_nodes, int n_factors, const int *fa, const int *fb, int *out_order, int *out_parent) {

@@ -340,8 +340,10 @@ static void inc_impl(april_graph_t *g, april_graph_cholesky_param_t *param) {
     // fast path: frozen base plan + TAIL front, only the dirty root paths are regenerated and re-factorised
     const int N_before = c.inc_N;
     c.h_bad.p[0] = c.h_bad.p[1] = c.h_bad.p[2] = c.h_bad.p[3] = 0;      // (the riding state update only ever writes a SET failure record)
+    g_incfail_last = 0;
     bool reused = g_opt.inc_fast && gp.host_idx.empty() && inc_fast_step(c, gp, N, F, c.inc_F, c.inc_N, partial ? &visits : nullptr, -1.0, patch_states);
     if (!reused) {                // the step does not fit the frozen structure (or slack ran out): full re-plan
+        inc_forms_head(c.inc, IF_REPLAN, g_incfail_last, F - c.inc_F, TailStep{ -1, 0, 0, 0, 0, 0, 0 }, 0, 0, 0, 0, 0);      // (aprilsam_amd_debug_inc_forms: no rows)
         if (lazy_states) pack_states(gp, g, true, false);       // (every pose's state / l_point goes to the device below: look at all of them)
         gp.mirror_sync = false; gp.new_states = gp.h_state.p;
         upload_factors(gp);

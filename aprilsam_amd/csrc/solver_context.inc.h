@@ -58,7 +58,23 @@ struct IncState {
     bool upd_ok = true;                     // false after a step that failed half-way, until the next full plan
     bool base_has_big = false;              // the base plan has fronts on the multi-workgroup path
     std::vector<char> st_mid, st_mode; std::vector<int> st_owner, st_mask, st_wout, st_slot; std::vector<UpdRec> st_upd, st_rec;
+    // what the last april_graph_cholesky_inc did, as aprilsam_amd_debug_inc_forms hands it out (IF_HEAD ints, then IF_ROW per dirty front); empty: none yet
+    std::vector<int> forms;
 };
+// aprilsam_amd_debug_inc_forms: header and row widths, the path codes of header [3]
+constexpr int IF_HEAD = 14, IF_ROW = 10 + UPD_MAXC;
+enum { IF_REPLAN = 0, IF_TAIL_SOLVE = 1, IF_TAIL_LIST = 2, IF_TAIL_GENERAL = 3, IF_ONE = 4, IF_MULTI = 5, IF_LEVELS = 6 };
+static void inc_forms_head(IncState &I, int path, int fail, int n_fac, const TailStep &ts, int n_old, int threads, int one, int up_multi, int dn_multi) {
+    int h[IF_HEAD] = { 0, IF_HEAD, IF_ROW, path, fail, n_fac, ts.t >= 0 ? ts.a_idx : -1, ts.t >= 0 ? n_old : -1, ts.t >= 0 ? ts.nsb : -1, ts.t >= 0 && ts.solve ? ts.s_idx : -1,
+                       threads, one, up_multi, dn_multi };
+    I.forms.assign(h, h + IF_HEAD);
+}
+static void inc_forms_row(IncState &I, int t, int mode, int nsb, int nub, int old_nub, int inplace, int mid, const UpdRec *u) {
+    int r[IF_ROW] = { t, mode, nsb, nub, old_nub, u ? u->mask : 0, u ? u->n_own : 0, u ? u->n_ch : 0, inplace, mid };
+    for (int k = 0; k < UPD_MAXC; k++) r[10 + k] = u && k < u->n_ch ? u->ch_cnu[k] : -1;
+    I.forms.insert(I.forms.end(), r, r + IF_ROW);
+    I.forms[0]++;
+}
 
 // The work-entry tables of the retained-factor consumers: one vector of entries per table, and per level and kernel the run of entries
 // its launch takes.  span_of(ent, fill): the run that fill() appends to ent.
@@ -403,7 +419,8 @@ static int waves_of(int nt) { return nt >= 1024 ? 16 : (nt >= 512 ? 8 : 4); }
 // workgroup size of k_front_small on a level with n fronts: latency levels take the big workgroup (more lanes on one
 // front's critical path), throughput levels the smaller one (more workgroups per CU)
 static long long g_incfail[32] = { 0 };        // APRILSAM_AMD_INC_PROFILE: why inc_fast_step handed a step to a full re-plan (exit number in source order)
-static bool inc_fail(int why) { g_incfail[why & 31]++; return false; }
+static thread_local int g_incfail_last = 0;    // the exit the calling thread's last inc_fast_step left by (aprilsam_amd_debug_inc_forms; 0: it did not fail, or was not tried)
+static bool inc_fail(int why) { g_incfail[why & 31]++; g_incfail_last = why; return false; }
 static long long g_updstat[6] = { 0 };      // APRILSAM_AMD_INC_PROFILE: general-path steps with / without updated fronts, fronts updated / re-factorised in the former, re-factorised in the latter, steps through k_inc_one
 static double g_incsub[8] = { 0 }; static long long g_incsub_n = 0;      // APRILSAM_AMD_INC_PROFILE: host sub-phases of the general incremental path (ms, summed)
 static const bool g_incprof_stamps = [] { const char *e = getenv("APRILSAM_AMD_INC_PROFILE"); return e && *e == '2'; }();      // (see IncProf)

@@ -85,6 +85,8 @@ static bool inc_fast_step(Context &c, GraphPack &gp, int N, int F, int Fold, int
     }
     // ... and when the reference's walk stays on a short root path, the whole step is decided here, without the general
     // machinery below (whose cost grows with the number of fronts and levels): one k_inc_one launch
+    // workgroup sizes of the step's single-workgroup launches (option inc_one_threads; the launch that carries the prologue and tail_refactor ahead of launches of their own)
+    const int one_nt = g_opt.inc_one_threads >= 1024 ? 1024 : g_opt.inc_one_threads >= 512 ? 512 : 256, tail_nt = 1024;
     g_incsub[6] += tail_fast ? 1 : 0; g_incsub[7] += (tail_fast && needed && patch_states) ? 1 : 0;
     if (tail_fast && needed && g_opt.inc_one && g_opt.wave_backsolve && patch_states && F <= gp.F_cap) {
         const int T = tstep.t, first = I.t_first.back(), nT0 = (int)I.t_first.size(), nFr0 = nF0 + nT0;
@@ -130,6 +132,8 @@ static bool inc_fast_step(Context &c, GraphPack &gp, int N, int F, int Fold, int
                 new_swap[f - Fold] = (unsigned char)((fb[f] >= 0 && fa[f] < fb[f] ? 1 : 0) | ((c.wt_any && f < (int)c.wt.size() && c.wt[f]) ? 2 : 0));
             }
             FrontDesc &D = I.fd[T];
+            inc_forms_head(I, solve_here ? IF_TAIL_SOLVE : IF_TAIL_LIST, 0, F - Fold, tstep, tstep.n_old, one_nt, 1, 0, 0);
+            inc_forms_row(I, T, 0, n_new, nph, I.cur_nub[T], 1, 0, nullptr);
             D.nsb = n_new; D.nub = nph; I.cur_nub[T] = nph;
             I.recs_stale = T; I.tail_ok = T;
             c.st.reserved0 = 1; c.st.inc_fronts_updated = 0;
@@ -183,7 +187,6 @@ static bool inc_fast_step(Context &c, GraphPack &gp, int N, int F, int Fold, int
             const IncFlags nofl{ c.d_epoch.p, nullptr, nullptr, 0 };          // (one workgroup, no flags: the step counter advances all the same)
             rewind_epoch(c, s, 1);
             const int *dn = c.d_tab.p + I.tab_used; const int n_dn = solve_here ? 0 : (int)lst.size();
-            const int one_nt = g_opt.inc_one_threads >= 1024 ? 1024 : g_opt.inc_one_threads >= 512 ? 512 : 256;
             launch_inc_one_nt(one_nt, lds, s, pro, nofl, c.inl, c.dp, tstep, (const int *)nullptr, 0, dn, n_dn, c.d_pool.p, 0ll, c.d_x.p, upd1);
             gp.mirror_sync = true;
             gp.new_states = gp.h_out.p;
@@ -356,6 +359,7 @@ static bool inc_fast_step(Context &c, GraphPack &gp, int N, int F, int Fold, int
     long long wbuf_used = 0;
     struct Ent { int col, row, f, k, slot; };
     std::vector<Ent> ents;
+    if (!batch) inc_forms_head(I, IF_REPLAN, 0, F - Fold, tstep, tstep.n_old, 0, 0, 0, 0);      // (rows as the fronts are regenerated; the path once it is decided, section 5)
     auto nsb_of = [&](int t) { return is_tail(t) ? I.t_cnt[t - nF0] : P.f_nsb[t]; };
     auto nub0_of = [&](int t) { return is_tail(t) ? 0 : P.f_nub[t]; };
     for (int t = 0; t < nFr; t++) {
@@ -372,6 +376,7 @@ static bool inc_fast_step(Context &c, GraphPack &gp, int N, int F, int Fold, int
         c.st.max_front_rows = std::max<decltype(c.st.max_front_rows)>(c.st.max_front_rows, 3 * nbc);      // (stats: fronts grow under incremental steps)
         FrontDesc &D = I.fd[t];
         if (tail_fast && t == tstep.t) {               // only the descriptor changes: records, children and array stay
+            if (!batch) inc_forms_row(I, t, 0, nsb, nub, I.cur_nub[t], 1, 0, nullptr);
             D.nsb = nsb; D.nub = nub; I.cur_nub[t] = nub;
             for (int f = Fold; f < F; f++) new_swap[f - Fold] = (unsigned char)((fb[f] >= 0 && fa[f] < fb[f] ? 1 : 0) | ((c.wt_any && f < (int)c.wt.size() && c.wt[f]) ? 2 : 0));      // (own poses: local order = id order; see add_factor below)
             fd_dirty.push_back(t);
@@ -432,6 +437,7 @@ static bool inc_fast_step(Context &c, GraphPack &gp, int N, int F, int Fold, int
                 u.ch_cnu[u.n_ch] = nub0_of(ch) + (int)Ec.size(); u.ch_mask[u.n_ch] = fmask[ch]; u.n_ch++;
             }
             rec_of[t] = u;
+            inc_forms_row(I, t, 1, nsb, nub, old_nub, D.off == old_off, mid[t], &u);
             I.stale[t] = 1;
             D.parent = I.parent[t];
             fd_dirty.push_back(t);
@@ -439,6 +445,7 @@ static bool inc_fast_step(Context &c, GraphPack &gp, int N, int F, int Fold, int
             continue;
         }
         I.stale[t] = 0;
+        if (!batch) inc_forms_row(I, t, 0, nsb, nub, old_nub, D.off == old_off, mid[t], nullptr);
         // destination records: only fronts that own factors added since the batch need new ones
         if (!I.xfac[t].empty()) {
             ents.clear();
@@ -639,7 +646,6 @@ static bool inc_fast_step(Context &c, GraphPack &gp, int N, int F, int Fold, int
     // ... and a step that regenerates a front or three and walks a short root path runs as ONE launch of one workgroup
     // (k_inc_one: prologue, fronts, back substitution one after the other)
     bool one = iu && id && needed && g_opt.inc_one && iu_n <= g_opt.inc_one_up && id_n <= g_opt.inc_one_dn && id_maxns <= BSW_MAX_NS && g_opt.wave_backsolve;
-    const int one_nt = g_opt.inc_one_threads >= 1024 ? 1024 : g_opt.inc_one_threads >= 512 ? 512 : 256;
     size_t one_lds = std::max(id_lds, tail_fast ? tail_refactor_lds() : (size_t)0);
     if (one) {
         for (int l = 0; l < nLev; l++) for (int t : lev_dirty[l]) {         // the kernel's own full / panel decision, at its thread count
@@ -713,6 +719,12 @@ static bool inc_fast_step(Context &c, GraphPack &gp, int N, int F, int Fold, int
     // ---- 5. numeric: new factors linearised, dirty fronts level by level, back substitution, update ----------------------
     set_small_attr();
     if (iu && nFr > c.flag_stride) return inc_fail(13);
+    if (!batch) {
+        int lev_nt = 0;
+        for (int l = 0; l < nLev && !lev_nt; l++) if (!lev_dirty[l].empty()) lev_nt = dl[l].small_nt;
+        I.forms[3] = tail_fast ? IF_TAIL_GENERAL : one ? IF_ONE : iu ? IF_MULTI : IF_LEVELS;
+        I.forms[10] = one ? one_nt : tail_fast ? tail_nt : iu ? iu_nt : lev_nt; I.forms[11] = one; I.forms[12] = iu && !one; I.forms[13] = id && !one;
+    }
     rewind_epoch(c, s, 1);
     // the plan as this step's multi-level launches see it: the flags carry the step number (advanced by the step's first kernel) -- dpi: a
     // front waits for the children this step regenerates (marks, written by the prologue); dpm: a batch step on the extended plan, levels >= 1
@@ -755,7 +767,7 @@ static bool inc_fast_step(Context &c, GraphPack &gp, int N, int F, int Fold, int
         c.one_wait = 0;
         const IncFlags fl = (!one && iu) ? IncFlags{ c.d_epoch.p, c.d_marks.p, c.d_tab.p + iu_off, iu_n } : IncFlags{ c.d_epoch.p, nullptr, nullptr, 0 };
         if (tail_fast && !one) {                       // the refactorisation in the prologue's launch, the back substitution in launches of its own
-            launch_inc_one_nt(1024, tail_refactor_lds(), s, pro, fl, c.inl, c.dp, tstep, (const int *)nullptr, 0, (const int *)nullptr, 0, c.d_pool.p, iu_full, c.d_x.p, UpdArgs{});
+            launch_inc_one_nt(tail_nt, tail_refactor_lds(), s, pro, fl, c.inl, c.dp, tstep, (const int *)nullptr, 0, (const int *)nullptr, 0, c.d_pool.p, iu_full, c.d_x.p, UpdArgs{});
         } else if (one) {
             if (g_incprof_stamps) { c.h_kstamp.need(8 + PROF_SLOTS); memset(c.h_kstamp.p, 0, 8 * (8 + PROF_SLOTS)); pro.stamps = c.h_kstamp.p; }
             if (g_opt.inc_one_spin) {                  // completion through a word in pinned memory: the host spins instead of sleeping in hipStreamSynchronize

@@ -247,6 +247,16 @@ int debug_front_forms(const april_graph_cholesky_param_t *param, int *out, int c
     for (int i = 0; i < (int)o.size() && i < cap; i++) out[i] = o[i];
     return (int)o.size();
 }
+// What the param's most recent april_graph_cholesky_inc did: IncState::forms, filled by inc_fast_step (and by inc_step for a re-plan) at the
+// places where these facts are decided -- nothing is decided here.  Columns: include/aprilsam_amd.h.  -1: no incremental call yet.
+int debug_inc_forms(const april_graph_cholesky_param_t *param, int *out, int cap) {
+    SlotLock lk(param, nullptr);
+    auto it = g_ctx.find(param);
+    if (it == g_ctx.end() || it->second->inc.forms.empty()) return -1;
+    const std::vector<int> &o = it->second->inc.forms;
+    for (int i = 0; i < (int)o.size() && i < cap; i++) out[i] = o[i];
+    return (int)o.size();
+}
 // debug option pool_guard checking itself: declares ONE extra band that lies inside the first frontal array (which the last step
 // wrote) and runs the check, which must then report ERR_GUARD; the param's context is dropped by the failure path as for any error
 int debug_guard_selftest(const april_graph_cholesky_param_t *param) {

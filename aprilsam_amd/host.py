@@ -178,6 +178,8 @@ class SolverLib:
                 d.aprilsam_amd_debug_graph_captures.restype = C.c_longlong
             if hasattr(d, "aprilsam_amd_debug_front_forms"):
                 d.aprilsam_amd_debug_front_forms.argtypes = [C.POINTER(abi.CholeskyParam), _ip, C.c_int]
+            if hasattr(d, "aprilsam_amd_debug_inc_forms"):
+                d.aprilsam_amd_debug_inc_forms.argtypes = [C.POINTER(abi.CholeskyParam), _ip, C.c_int]
             if hasattr(d, "aprilsam_amd_initialize_chordal"):    # (defined in the HIP translation unit)
                 d.aprilsam_amd_chordal_opts_init.argtypes = [C.POINTER(abi.ChordalOpts)]
                 d.aprilsam_amd_chordal_opts_init.restype = None
@@ -376,6 +378,29 @@ class Param:
             levels.append(dict(n_big=int(buf[k]), grouped=bool(buf[k + 1]), blocks=[tuple(int(v) for v in buf[k + 3 + 4 * b:k + 7 + 4 * b]) for b in range(nob)]))
             k += 3 + 4 * nob
         return fronts, levels
+
+    INC_PATHS = ("re-plan", "tail+solve", "tail+list", "tail general", "one", "multi", "levels")
+
+    def inc_forms(self):
+        """(head, rows): what this param's most recent april_graph_cholesky_inc did (aprilsam_amd_debug_inc_forms; columns as
+        include/aprilsam_amd.h lists them).  head: dict(path (one of INC_PATHS), fail, n_factors, a_idx, n_old, n_new, s_idx, threads, one,
+        up_multi, dn_multi); rows: one dict per dirty front, in the order the step regenerated them (children first)"""
+        n = int(self.lib.dll.aprilsam_amd_debug_inc_forms(self.ptr, None, 0))
+        if n < 0:
+            raise RuntimeError("no incremental step on this param yet")
+        buf = np.zeros(n, np.int32)
+        assert int(self.lib.dll.aprilsam_amd_debug_inc_forms(self.ptr, _np_i(buf), n)) == n
+        nrow, hw, rw = (int(v) for v in buf[:3])
+        names = ("fail", "n_factors", "a_idx", "n_old", "n_new", "s_idx", "threads", "one", "up_multi", "dn_multi")
+        head = dict(path=self.INC_PATHS[int(buf[3])], **{k: int(v) for k, v in zip(names, buf[4:hw])})
+        cols = ("front", "mode", "nsb", "nub", "old_nub", "mask", "n_own", "n_ch", "inplace", "mid")
+        rows = []
+        for i in range(nrow):
+            r = buf[hw + rw * i:hw + rw * (i + 1)]
+            d = {k: int(v) for k, v in zip(cols, r)}
+            d["ch_cnu"] = [int(v) for v in r[len(cols):len(cols) + d["n_ch"]]] if d["mode"] else []
+            rows.append(d)
+        return head, rows
 
     def destroy(self):
         if self.ptr:

@@ -1129,6 +1129,22 @@ int aprilsam_amd_debug_front_times(const april_graph_cholesky_param_t *param, lo
  * Returns the number of ints the record takes (out is filled up to cap), or -1: no plan, or a plan extended by tail fronts. */
 int aprilsam_amd_debug_front_forms(const april_graph_cholesky_param_t *param, int *out, int cap);
 
+/* debug (tests/test_gpu_inc_shapes.py): what the param's most recent april_graph_cholesky_inc did, noted by the host code of the incremental
+ * path at the places where it decides these things -- read-only, nothing is decided again.  out (ints):
+ *   [0] rows (dirty fronts)   [1] ints of this header (14)   [2] ints per row (14)
+ *   [3] path: 0 full re-plan; 1 tail_refactor inside k_inc_one, back substitution in its window (solve_here); 2 the same with a list of
+ *       fronts to back-substitute; 3 tail_refactor on the general path; 4 general step as one k_inc_one; 5 multi-level launch; 6 per-level launches
+ *   [4] for a re-plan, the exit of inc_fast_step it left by (0: the fast path was not tried)   [5] new factors of the step
+ *   [6] [7] [8] [9] the tail step's a_idx, n_old, n_new, s_idx (-1: no tail_refactor; s_idx -1: no solve in the window)
+ *   [10] workgroup size of the step's (first) front launch   [11] 1 = the whole step was one k_inc_one launch
+ *   [12] 1 = fronts in a multi-level launch of their own   [13] 1 = back substitution in a multi-level launch of its own
+ *   per dirty front, children before parents: front id; mode 1 low-rank updated / 0 re-assembled (or its trailing columns refactorised);
+ *     own pose blocks nsb; update blocks nub after the step; nub before it; the step's factor slots the front sees (bit mask; updated fronts);
+ *     own new factors taken as slots; updated children; 1 = its array was rewritten in place; 1 = its structure gained a row that is not
+ *     its last (mid); then the update blocks of each updated child (4 ints, -1 = none)
+ * Returns the number of ints the record takes (out is filled up to cap), or -1: no incremental call on this param yet. */
+int aprilsam_amd_debug_inc_forms(const april_graph_cholesky_param_t *param, int *out, int cap);
+
 const char *aprilsam_amd_version(void);
 
 #ifdef __cplusplus

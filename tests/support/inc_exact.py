@@ -42,6 +42,22 @@ def _bind_model(dll):
     dll.aprilsam_amd_refmodel_destroy.argtypes = [C.c_void_p]
 
 
+def incremental_system(lp, fa, fb, z, W, q, n_batch, tikhanov):
+    """The exact linear system of an incremental step, as the arguments Oracle.solve_system(lp, lp, fa, fb, zz, W, lam) takes:
+    every xyt factor at its poses' l_point, every prior at q[i] -- the state of its node in the call that added it -- which gives the same rows
+    as a prior at the l_point with z' = z - q + l_point; Tikhonov only on the poses present at the last batch step.  q: [F, 3], rows of binary
+    factors unused.  -> (zz, lam)"""
+    N = len(lp)
+    zz = np.array(z, float)
+    pr = np.nonzero(np.asarray(fb) < 0)[0]
+    if len(pr):
+        qq = np.asarray(q, float)[pr]; at = lp[np.asarray(fa)[pr]]
+        moved = np.any(qq != at, axis=1)
+        d = zz[pr] - qq; d[:, 2] = mod2pi(d[:, 2])
+        zz[pr[moved]] = (d + at)[moved]
+    return zz, np.where(np.arange(N) < n_batch, tikhanov, 0.0)
+
+
 class IncExact:
     """lib stand-in: the graphs it makes check every solver call (module docstring).  stride: an incremental step that is not a
     fall-back, re-planned or low-rank-updated step is solved exactly only when its index (count of incremental calls so far on
@@ -168,14 +184,7 @@ class _CheckedGraph:
             r["old_old_cross"] += s["inc_old_old_cross"] > 0
         check = replanned or updated or k % chk.stride == 0
         if check:
-            zz = z.copy()
-            pr = np.nonzero(fb < 0)[0]
-            if len(pr):                                   # a prior evaluated at q: the same rows as one at lp with z' = z - q + lp
-                q = np.array([self.q[i] for i in pr]); at = lp[fa[pr]]
-                moved = np.any(q != at, axis=1)
-                d = z[pr] - q; d[:, 2] = mod2pi(d[:, 2])
-                zz[pr[moved]] = (d + at)[moved]
-            lam = np.where(np.arange(N) < self.n_batch, p.c.tikhanov, 0.0)
+            zz, lam = incremental_system(lp, fa, fb, z, W, np.array(self.q, float).reshape(-1, 3), self.n_batch, p.c.tikhanov)
             x = np.ascontiguousarray(chk.oracle.solve_system(lp, lp, fa, fb, zz, W, lam))
         else:
             x = np.ascontiguousarray(d1, float)

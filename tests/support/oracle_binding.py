@@ -32,6 +32,7 @@ class Oracle:
         d.orc_chi2.restype = C.c_double
         d.orc_chi2.argtypes = [C.c_int, _dp, C.c_int, _ip, _ip, _dp, _dp]
         d.orc_solve_system.argtypes = [C.c_int, _dp, _dp, C.c_int, _ip, _ip, _dp, _dp, _dp, _dp, _ip, _dp]
+        d.orc_solve_system_ordered.argtypes = [C.c_int, _dp, _dp, C.c_int, _ip, _ip, _dp, _dp, _dp, _dp, _ip, _ip, _dp]
         d.orc_batch_step.argtypes = [C.c_int, _dp, C.c_int, _ip, _ip, _dp, _dp, C.c_double, _dp, _dp]
         d.orc_batch_step_ordered.argtypes = [C.c_int, _dp, C.c_int, _ip, _ip, _dp, _dp, C.c_double, _ip, _dp, _dp]
         d.orc_normal_equations_dense.argtypes = [C.c_int, _dp, _dp, C.c_int, _ip, _ip, _dp, _dp, C.c_double, _dp, _dp]
@@ -72,11 +73,17 @@ class Oracle:
             raise ArithmeticError("oracle: matrix not positive definite")
         return s, dx, stats
 
-    def solve_system(self, lp, st_unary, fa, fb, z, W, lambda_node):
+    def solve_system(self, lp, st_unary, fa, fb, z, W, lambda_node, order=None):
+        """order: elimination order (position -> node); None = the oracle's own"""
         lp, fa, fb, z, W = self._prep(lp, fa, fb, z, W)
         su = np.ascontiguousarray(st_unary, float); lam = np.ascontiguousarray(lambda_node, float)
         dx = np.zeros_like(lp)
-        rc = self.dll.orc_solve_system(len(lp), _d(lp), _d(su), len(fa), _i(fa), _i(fb), _d(z), _d(W), _d(lam), _d(dx), None, None)
+        if order is not None:
+            order = np.ascontiguousarray(order, np.int32)
+            assert len(order) == len(lp)
+            rc = self.dll.orc_solve_system_ordered(len(lp), _d(lp), _d(su), len(fa), _i(fa), _i(fb), _d(z), _d(W), _d(lam), _d(dx), _i(order), None, None)
+        else:
+            rc = self.dll.orc_solve_system(len(lp), _d(lp), _d(su), len(fa), _i(fa), _i(fb), _d(z), _d(W), _d(lam), _d(dx), None, None)
         if rc != 0:
             raise ArithmeticError("oracle: matrix not positive definite")
         return dx

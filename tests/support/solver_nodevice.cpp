@@ -34,6 +34,7 @@ double resident_chi2(april_graph_t *) { no_device("resident_chi2"); return NAN; 
 int resident_end(april_graph_t *, april_graph_cholesky_param_t *) { return no_device("resident_end"); }
 int level_profile(const april_graph_cholesky_param_t *, double *, int) { return -1; }
 int debug_front_forms(const april_graph_cholesky_param_t *, int *, int) { return -1; }
+int debug_inc_forms(const april_graph_cholesky_param_t *, int *, int) { return -1; }
 int kernel_profile(const april_graph_cholesky_param_t *, double *, long long *, double *, double *, const char **) { return -1; }
 void drop_context(const april_graph_cholesky_param_t *) {}
 void drop_graph_pack(const april_graph_t *) {}
