@@ -471,7 +471,12 @@ static int shard_gather_states_impl(april_graph_t *g, april_graph_cholesky_param
     param->nreordering = N; param->factor_num = gp.Fg;
     return 0;
 }
-// chi^2 at the resident states: every rank sums the factors its fronts own, the transport adds the partial sums
+// chi^2 at the resident states: every rank sums the factors its fronts own, the transport adds the partial sums.  A transport that has
+// failed (now, or in an earlier call of this run) cannot add them: the result is NaN, not this rank's partial sum, and the error is recorded
+static double shard_chi2_failed(const Transport &T) {
+    set_last_error(-6, std::string("aprilsam_amd_shard_chi2: the transport has failed (") + T.error + "): the partial sums cannot be added");
+    return std::nan("");
+}
 static double shard_chi2_impl(april_graph_t *g, april_graph_cholesky_param_t *param);
 double shard_chi2(april_graph_t *g, april_graph_cholesky_param_t *param) {
     double out = std::nan("");
@@ -485,6 +490,7 @@ static double shard_chi2_impl(april_graph_t *g, april_graph_cholesky_param_t *pa
     GraphPack &gp = pack_for(g);
     const Plan &P = ic->second->plan; ShardState &S = *it->second;
     hipStream_t s = gp.stream;
+    if (S.tr && S.tr->failed) return shard_chi2_failed(*S.tr);
     enqueue_objective(gp, s, Convention::CHI2, gp.d_state.p, gp.d_chi2f.p);      // (every family is refused at shard_begin: the plain launch alone)
     std::vector<double> h(gp.F);
     HIPCHECK(hipMemcpyAsync(h.data(), gp.d_chi2f.p, (size_t)8 * gp.F, hipMemcpyDeviceToHost, s));
@@ -497,6 +503,7 @@ static double shard_chi2_impl(april_graph_t *g, april_graph_cholesky_param_t *pa
         S.tr->allreduce_sum(gp.d_scalar.p, 1, s);
         HIPCHECK(hipMemcpyAsync(gp.h_scalar.p, gp.d_scalar.p, 8, hipMemcpyDeviceToHost, s));
         HIPCHECK(hipStreamSynchronize(s));
+        if (S.tr->failed) return shard_chi2_failed(*S.tr);
         acc = gp.h_scalar.p[0];
     }
     return acc;

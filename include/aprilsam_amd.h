@@ -1003,7 +1003,10 @@ long long aprilsam_amd_debug_graph_captures(const april_graph_cholesky_param_t *
  *                                                                     fronts (broadcast).  With RCCL everything is enqueued
  *                                                                     on the solver's HIP stream: no host synchronisation
  *                                                                     between a level's kernels and its transfers.
- *     aprilsam_amd_shard_chi2(graph, param);                          chi^2 of the whole graph (partial sums added)
+ *     aprilsam_amd_shard_chi2(graph, param);                          chi^2 of the whole graph (partial sums added); NaN when
+ *                                                                     the call fails or the transport has failed, in this call
+ *                                                                     or in an earlier one of the run (never this rank's partial
+ *                                                                     sum); aprilsam_amd_last_error then holds -6 and the message
  *     aprilsam_amd_shard_gather_states(graph, param);                 every rank ends up with ALL states / l_points / dx,
  *                                                                     in HBM and in the node objects
  *     aprilsam_amd_shard_end(param);

@@ -53,15 +53,11 @@ def test_two_rank_replicas_gloo(built):
     assert v0 == v1 == pytest.approx(2 * 100 / 0.75)          # whole-job iterations / s
 
 
-@pytest.mark.parametrize("world", [1, 2, 3, 4, 8])
-def test_shard_map_is_a_consistent_partition(lib, world):
-    from tests.support.mf_emulator import PlanView
-    st, fa, fb, z, W = lib.lattice_arrays(100)
-    P = PlanView(lib, len(st), fa, fb, xy=st[:, :2], leaf_nodes=16, shard_worlds=(world,))
+def _assert_partition(P, world):
+    """owners, transfers and broadcasts of one world form a consistent partition of the plan's tree; -> (xfer, top fronts, owner)"""
     xfer, bcast, owner = P.shard[world]
     nF = P.nF
     assert len(owner) == nF and owner.min() >= 0 and owner.max() < world
-    assert set(owner.tolist()) == set(range(world))                          # every rank owns something
     # transfers = exactly the tree edges that cross ranks, child -> owner of the parent, levels ascending
     cross = [(t, int(owner[t]), int(owner[P.front_parent[t]])) for t in range(nF) if P.front_parent[t] >= 0 and owner[P.front_parent[t]] != owner[t]]
     assert sorted((int(r[1]), int(r[2]), int(r[3])) for r in xfer) == sorted(cross)
@@ -72,6 +68,19 @@ def test_shard_map_is_a_consistent_partition(lib, world):
         par = int(P.front_parent[t])
         if par >= 0 and par not in top:
             assert owner[t] == owner[par]
+    if world == 1:
+        assert len(xfer) == 0 and len(bcast) == 0
+    return xfer, top, owner
+
+
+@pytest.mark.parametrize("world", [1, 2, 3, 4, 8])
+def test_shard_map_is_a_consistent_partition(lib, world):
+    from tests.support.mf_emulator import PlanView
+    st, fa, fb, z, W = lib.lattice_arrays(100)
+    P = PlanView(lib, len(st), fa, fb, xy=st[:, :2], leaf_nodes=16, shard_worlds=(world,))
+    xfer, top, owner = _assert_partition(P, world)
+    nF = P.nF
+    assert set(owner.tolist()) == set(range(world))                          # every rank owns something (true of this lattice, not of every graph: below)
     if world > 1:
         assert len(xfer) >= world - 1 and len(top) >= world - 1
         # balance of the parallel phase: the subtrees below the top fronts (the top fronts themselves run level after
@@ -80,8 +89,27 @@ def test_shard_map_is_a_consistent_partition(lib, world):
         local = np.array([t not in top for t in range(nF)])
         w = np.bincount(owner[local], weights=(ns * m * m)[local], minlength=world)
         assert w.min() > 0 and w.max() < 2.1 * w.mean(), w     # (binary tree over 3 ranks: 50 / 25 / 25 at best)
-    else:
-        assert len(xfer) == 0 and len(bcast) == 0
+
+
+@pytest.mark.parametrize("world", [1, 2, 3, 4, 5, 8])
+@pytest.mark.parametrize("name", ["6,5 x65", "30,25,20 fan 2", "three_components"])
+def test_shard_map_of_designed_trees_is_a_consistent_partition(lib, name, world):
+    """the same partition and transfer assertions on trees where ranks stay idle, one root has 32 remote children, or there are three roots
+    (tests/support/shard_designs.py): not "every rank owns something"; instead every root belongs to rank 0, every top front is broadcast from
+    its owner with its own first position and width, and the packed count of a transfer is the lower trapezoid of the update block"""
+    from tests.support import shard_designs as D
+    from tests.support.mf_emulator import PlanView
+    arr = D.arrays(lib, name)
+    P = PlanView(lib, len(arr[0]), arr[1], arr[2], xy=arr[0][:, :2], shard_worlds=(world,))
+    xfer, top, owner = _assert_partition(P, world)
+    assert all(owner[t] == 0 for t in range(P.nF) if P.front_parent[t] < 0)
+    for lev, front, own, first, nsb in P.shard[world][1]:
+        assert (lev, own, first, nsb) == (P.front_level[front], owner[front], P.front_first[front], P.front_nsb[front])
+    for lev, front, src, dst, off, cnt in xfer:
+        u = 3 * int(P.front_nub[front])                # columns of the update block; column j holds rows (j rounded down to its 3 x 3 block) .. u, the last being the right-hand side
+        assert cnt == sum(u + 1 - 3 * (j // 3) for j in range(u)), (front, cnt)
+    if world > 1 and P.nF > 1:
+        assert len(xfer) >= 1 and len(top) >= 1
 
 
 def _shard_worker(rank, world, port, out):

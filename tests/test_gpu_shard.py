@@ -4,7 +4,9 @@ over gloo here because RCCL cannot place two ranks on one device).  Checked: chi
 golden (K = 24, 316) or the recorded single-GPU trace (K = 1000), the gathered STATES against a single-GPU run of the
 same iterations (<= 1e-9), identical gathered states on every rank, and that a rank only
 allocates the fronts it owns.  On the 8-GPU node the same calls run with the RCCL transport (world = 1 exercises it
-here)."""
+here).  These are the only tests on the gloo and RCCL wires; what the lattices never reach (idle ranks, primary-child ghosts,
+several roots, 3 and 5 ranks, the failure contracts, ...) is in tests/test_gpu_shard_designs.py, with the ranks as threads of
+one process."""
 import os
 import sys
 
