@@ -155,6 +155,8 @@ MARGINAL_MAX_NODES = 40        # aprilsam_amd_marginal_prior: removed nodes + bl
 
 # joint compatibility gating (include/aprilsam_amd.h: aprilsam_amd_gate_xyt_joint): candidates per hypothesis
 JOINT_MAX = 16
+# information measures (include/aprilsam_amd.h: aprilsam_amd_logdet_sets): nodes per set
+SET_MAX = 16
 
 # measured LP64 layout of the reference; checked by tests/test_abi.py
 EXPECTED_SIZES = {"ZArray": 24, "Graph": 32, "Factor": 104, "Node": 112, "CholeskyParam": 128}

@@ -114,6 +114,10 @@ int gate_polar(april_graph_t *g, april_graph_cholesky_param_t *param, int n, con
 int associate_polar(april_graph_t *g, april_graph_cholesky_param_t *param, int observer, int m, const int *kind, const double *z, const double *W, int L,
                     const int *landmarks, double gate1, double gate2, double *d2, int *best, double *d2_best, double *d2_second);
 long long path_solve_bytes(const april_graph_cholesky_param_t *param);
+int logdet(april_graph_t *g, april_graph_cholesky_param_t *param, double *out);                                                      // solver_info.inc.h
+int logdet_sets(april_graph_t *g, april_graph_cholesky_param_t *param, int n_sets, const int *set_ptr, const int *nodes, double *logdet_prefix);
+int info_gain_xyt(april_graph_t *g, april_graph_cholesky_param_t *param, int n_hyp, const int *hyp_ptr, const int *a, const int *b, const double *W,
+                  double *gain_prefix);
 int tree_solve(april_graph_t *g, april_graph_cholesky_param_t *param, int mode, int nrhs, const double *B, double *X);                // solver_treesolve.inc.h
 int marginals_cross(april_graph_t *g, april_graph_cholesky_param_t *param, int anchor, int n, const int *nodes, double *cov);
 int relative_covariances(april_graph_t *g, april_graph_cholesky_param_t *param, int anchor, int n, const int *nodes, double *cov);

@@ -42,6 +42,7 @@
 #include "pathsolve.hip.h"
 #include "polargate.hip.h"
 #include "jointgate.hip.h"
+#include "infomeasure.hip.h"
 #include "treesolve.hip.h"
 #include "plan.h"
 #include "refmodel.h"
@@ -259,6 +260,7 @@ struct PatchList {
 #include "solver_query.inc.h"
 #include "solver_marginals.inc.h"
 #include "solver_gating.inc.h"
+#include "solver_info.inc.h"
 #include "solver_audit.inc.h"
 #include "solver_marginal_prior.inc.h"
 #include "solver_treesolve.inc.h"
@@ -549,6 +551,15 @@ extern "C" int aprilsam_amd_marginals_set(april_graph_t *graph, april_graph_chol
 extern "C" int aprilsam_amd_gate_xyt_joint(april_graph_t *graph, april_graph_cholesky_param_t *param, int n_hyp, const int *hyp_ptr, const int *a, const int *b,
                                            const double *z, const double *W, double *d2_prefix, double *C) {
     return asam::gate_xyt_joint(graph, param, n_hyp, hyp_ptr, a, b, z, W, d2_prefix, C);
+}
+extern "C" int aprilsam_amd_logdet(april_graph_t *graph, april_graph_cholesky_param_t *param, double *logdet) { return asam::logdet(graph, param, logdet); }
+extern "C" int aprilsam_amd_logdet_sets(april_graph_t *graph, april_graph_cholesky_param_t *param, int n_sets, const int *set_ptr, const int *nodes,
+                                        double *logdet_prefix) {
+    return asam::logdet_sets(graph, param, n_sets, set_ptr, nodes, logdet_prefix);
+}
+extern "C" int aprilsam_amd_info_gain_xyt(april_graph_t *graph, april_graph_cholesky_param_t *param, int n_hyp, const int *hyp_ptr, const int *a, const int *b,
+                                          const double *W, double *gain_prefix) {
+    return asam::info_gain_xyt(graph, param, n_hyp, hyp_ptr, a, b, W, gain_prefix);
 }
 extern "C" int aprilsam_amd_gate_polar(april_graph_t *graph, april_graph_cholesky_param_t *param, int n, const int *a, const int *b, const int *kind,
                                        const double *z, const double *W, double *d2, double *S) {

@@ -116,9 +116,12 @@ struct PathState {
     DBuf<double> d_buf, d_cov, d_in; HBuf<double> h_out;
     DBuf<int> d_pidx;                      // k_gate_polar: candidate -> its pair's block in d_cov
     DBuf<int> d_jtab; DBuf<long long> d_joff;      // k_gate_xyt_joint: hyp_ptr | tab_ptr | the index table; the matrices' offsets
+    DBuf<LdEnt> d_ldent; DBuf<double> d_ldpart; DBuf<int> d_ldbad; HBuf<double> h_ld;      // k_logdet_partial / k_logdet_sum: the entries, the partials, the counts; the result
+    long long ld_gen = -1; int ld_n = 0;   // FactorView::gen d_ldent describes, and its entries
     long long peak_doubles = 0;            // the largest work buffer a chunk has used
     void release() {
         d_fr.release(); d_ent.release(); d_cmap.release(); d_at.release(); d_path.release(); d_pair.release(); d_buf.release(); d_cov.release(); d_in.release(); h_out.release(); d_pidx.release(); d_jtab.release(); d_joff.release();
+        d_ldent.release(); d_ldpart.release(); d_ldbad.release(); h_ld.release(); ld_gen = -1; ld_n = 0;
         rec.clear(); node_j.clear(); gen = -1;
     }
 };

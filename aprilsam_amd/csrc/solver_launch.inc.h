@@ -262,6 +262,18 @@ template <class K, class... Args> static void launch_polar_gate(hipStream_t s, K
     hipLaunchKernelGGL(kern, dim3((unsigned)(per_item ? work : (work + PG_T - 1) / PG_T)), dim3(PG_T), 0, s, a...);
 }
 
+// The kernels of infomeasure.hip.h.  k_logdet_partial (one wave per entry, four per workgroup; k_logdet_sum, one
+// workgroup, follows it on the stream and is enqueued with it: `a` = the pool, the partials, the counts, then the sum's output) and
+// k_logdet_blocks (one wave per set / hypothesis, behind the path solves; `a` = what follows the count).  No work: no launch
+template <class K, class... Args> static void launch_info(hipStream_t s, K kern, int work, const Args &...a) {
+    if (work <= 0) return;
+    hipLaunchKernelGGL(kern, dim3((unsigned)work), dim3(JG_T), 0, s, work, a...);
+}
+static void launch_info(hipStream_t s, int n_ent, const LdEnt *ent, const double *pool, double *part, int *nbad, double *out) {
+    if (n_ent > 0) hipLaunchKernelGGL(k_logdet_partial, dim3((unsigned)((n_ent + 3) / 4)), dim3(TPB), 0, s, ent, n_ent, pool, part, nbad);
+    hipLaunchKernelGGL(k_logdet_sum, dim3(1), dim3(LD_SUM_T), 0, s, n_ent, (const double *)part, (const int *)nbad, out);
+}
+
 // The kernel of fixed.hip.h that runs one thread per record of the pack's fixed table and one per fixed node: the
 // slots of d_H named by the records become zero, d_lambda at the fixed nodes' positions 1.0.  None for a pack without fixed nodes.  It
 // follows whatever wrote the slots and d_lambda for the step and precedes the first assembly kernel, inside every captured graph

@@ -157,6 +157,10 @@ class SolverLib:
             if hasattr(d, "aprilsam_amd_gate_xyt_joint"):         # (defined in the HIP translation unit)
                 d.aprilsam_amd_marginals_set.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.c_int, _ip, _dp]
                 d.aprilsam_amd_gate_xyt_joint.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.c_int, _ip, _ip, _ip, _dp, _dp, _dp, _dp]
+            if hasattr(d, "aprilsam_amd_logdet"):                 # (defined in the HIP translation unit)
+                d.aprilsam_amd_logdet.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), _dp]
+                d.aprilsam_amd_logdet_sets.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.c_int, _ip, _ip, _dp]
+                d.aprilsam_amd_info_gain_xyt.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.c_int, _ip, _ip, _ip, _dp, _dp]
             if hasattr(d, "aprilsam_amd_solve"):                  # (defined in the HIP translation unit)
                 d.aprilsam_amd_solve.argtypes = [C.POINTER(abi.Graph), C.POINTER(abi.CholeskyParam), C.c_int, C.c_int, _dp, _dp]
                 for nm in ("aprilsam_amd_marginals_cross", "aprilsam_amd_relative_covariances"):
@@ -836,6 +840,45 @@ class Graph:
             raise MarginalsError(rc, self.lib.last_error())
         off = np.concatenate([[0], np.cumsum([9 * m * m for m in ms])]).astype(np.int64)
         return rc, [d2[ptr[h]:ptr[h + 1]] for h in range(len(hyps))], [Cm[off[h]:off[h + 1]].reshape(3 * m, 3 * m) for h, m in enumerate(ms)]
+
+    def logdet(self, param):
+        """ln det of the factorised system, in nats (include/aprilsam_amd.h: aprilsam_amd_logdet).  Raises MarginalsError(rc) on a negative
+        return."""
+        out = C.c_double(0.0)
+        rc = self.lib.dll.aprilsam_amd_logdet(self.ptr, param.ptr, C.byref(out))
+        if rc < 0:
+            raise MarginalsError(rc, self.lib.last_error())
+        return out.value
+
+    def logdet_sets(self, param, sets):
+        """ln det of the joint marginal covariance of every prefix of every node set (include/aprilsam_amd.h: aprilsam_amd_logdet_sets).
+        sets: a list of node lists.  Returns (bad, [prefix [k] per set]); bad counts the sets with a pivot that was not positive.  Raises
+        MarginalsError(rc) on a negative return."""
+        ks = [len(np.atleast_1d(s)) for s in sets]
+        ptr = np.concatenate([[0], np.cumsum(ks)]).astype(np.int32)
+        nodes = np.ascontiguousarray(np.concatenate([np.asarray(s, np.int32).ravel() for s in sets]) if sets else np.zeros(0, np.int32))
+        out = np.empty(int(ptr[-1]))
+        rc = self.lib.dll.aprilsam_amd_logdet_sets(self.ptr, param.ptr, len(sets), _np_i(ptr), _np_i(nodes), _np_d(out))
+        if rc < 0:
+            raise MarginalsError(rc, self.lib.last_error())
+        return rc, [out[ptr[h]:ptr[h + 1]] for h in range(len(sets))]
+
+    def info_gain_xyt(self, param, hyps):
+        """Expected information gain of adding candidate xyt measurements (include/aprilsam_amd.h: aprilsam_amd_info_gain_xyt).  hyps: a list
+        of hypotheses, each a tuple (a [m], b [m], W [m, 3, 3] or [m, 9]); a gate_xyt_joint tuple (a, b, z, W) is taken too, its z unused.
+        Returns (bad, [gain_prefix [m] per hypothesis]).  Raises MarginalsError(rc) on a negative return."""
+        ms = [len(np.atleast_1d(h[0])) for h in hyps]
+        ptr = np.concatenate([[0], np.cumsum(ms)]).astype(np.int32)
+        n = int(ptr[-1])
+        cat = lambda k, dt, w: np.ascontiguousarray(np.concatenate([np.asarray(h[k], dt).reshape(-1, w) for h in hyps]) if hyps else np.zeros((0, w), dt))
+        a, b, W = cat(0, np.int32, 1).ravel(), cat(1, np.int32, 1).ravel(), cat(-1, float, 9)
+        if not (len(a) == len(b) == len(W) == n):
+            raise ValueError("a, b and W of a hypothesis must have the same length")
+        out = np.empty(n)
+        rc = self.lib.dll.aprilsam_amd_info_gain_xyt(self.ptr, param.ptr, len(hyps), _np_i(ptr), _np_i(a), _np_i(b), _np_d(W), _np_d(out))
+        if rc < 0:
+            raise MarginalsError(rc, self.lib.last_error())
+        return rc, [out[ptr[h]:ptr[h + 1]] for h in range(len(hyps))]
 
     def gate_polar(self, param, a, b, kind, z, W):
         """Mahalanobis gating of candidate polar measurements (include/aprilsam_amd.h: aprilsam_amd_gate_polar): kind [n], z [n, 2], W [n, 4]

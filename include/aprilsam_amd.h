@@ -541,6 +541,51 @@ int aprilsam_amd_gate_xyt_joint(april_graph_t *graph, april_graph_cholesky_param
 /* debug: the largest path-solve work buffer this param has used, in bytes (-1: no context) */
 long long aprilsam_amd_debug_path_solve_bytes(const april_graph_cholesky_param_t *param);
 
+/* ---- information measures: log-determinants, set entropies, information gain ---------------------------------------
+ * Three consumers of the retained factor.  All values are NATURAL logarithms (nats).  Common to the three: -1 no retained factor or a
+ * resident run in progress (also after aprilsam_amd_optimize_lm / _gnc / aprilsam_amd_initialize_chordal, which drop the factor); -12
+ * sharded param or asymmetric W in the factorised graph; -14 no HIP device; -11 a buffer that does not fit under option mem_cap_mb; -13 a
+ * null argument.  A refusal writes nothing, sets aprilsam_amd_last_error and leaves plan, factor and Sigma in place; no selected inversion
+ * runs and no Sigma pool is allocated.  Two calls give the same bits.
+ *
+ * aprilsam_amd_logdet: *logdet = ln det A of the system aprilsam_amd_solve documents, A = sum J^T W J + diag(lambda) = P' L L' P of the last
+ * successful solver call on `param` (whichever way the step went: batch, tail fronts, low-rank updates, re-plan, batch fall-back; robust,
+ * max-mixture, polar and Gaussian factors as they were factorised), computed as 2 sum ln L_jj over the factor's diagonal on the GPU.  A
+ * fixed node's diagonal block of A is exactly the identity and contributes exactly 0: the result is the log-determinant of the REDUCED
+ * system of the free nodes.  -ln det A is ln det of the whole joint covariance; the Laplace evidence of the linearised problem is
+ * -chi2 / 2 - ln det A / 2 up to a constant.  The sum's order depends on the factor's structure alone: options that only move offsets or
+ * reorder work lists give the same bits.  -15 if a diagonal entry is not positive and finite (an admitted factor has none).
+ *
+ * aprilsam_amd_logdet_sets: n_sets node sets, set_ptr (n_sets + 1 entries, set_ptr[0] == 0, CSR) indexing nodes; each set holds 1 ..
+ * APRILSAM_AMD_SET_MAX DISTINCT nodes.  logdet_prefix[set_ptr[h] + j] = ln det Sigma of the joint marginal covariance of the set's first
+ * j + 1 nodes -- the Sigma of aprilsam_amd_marginals_set -- by a Cholesky factorisation in LDS behind the path solves.  The last entry is
+ * the whole set's value, the difference of consecutive entries the log-determinant of node j conditional on its predecessors.  With k
+ * nodes in a set A (3 unknowns each):
+ *     differential entropy   h(A)    = (3 k ln(2 pi e) + ln det Sigma_A) / 2
+ *     mutual information     I(A; B) = (ln det Sigma_A + ln det Sigma_B - ln det Sigma_{A u B}) / 2
+ * Nodes, then unordered pairs, are deduplicated across ALL sets of the call and solved once.  A set cut to its first j nodes, in this or
+ * another call, reproduces prefix j bit for bit.  Returns 0, or the number of sets in which a pivot was not positive: their entries are
+ * NaN from that node on.  A set that holds a fixed node is such a set (its rows of Sigma are exact zeros).  -13 also for n_sets < 0, a
+ * set_ptr that does not start at 0 or decreases, an empty set or one of more than APRILSAM_AMD_SET_MAX nodes, a node repeated within a set
+ * (all judged before a device is asked for), a node id out of range of the factorised system or of graph.  n_sets == 0 returns 0.
+ *
+ * aprilsam_amd_info_gain_xyt: the expected information gain of ADDING candidate xyt measurements between a[i] and b[i] with information
+ * W[9i..]; the hypotheses have aprilsam_amd_gate_xyt_joint's shape (1 .. APRILSAM_AMD_JOINT_MAX candidates each, CSR hyp_ptr; candidates may
+ * share nodes or repeat a pair).  gain_prefix[hyp_ptr[h] + j] = ln det (I + blockdiag(W_i) H Sigma H') / 2 over the hypothesis's first j + 1
+ * candidates = (ln det C_prefix + sum_{i <= j} ln det W_i) / 2 with C = H Sigma_set H' + blockdiag(W_i^-1) exactly as _gate_xyt_joint
+ * builds it: the Jacobians at the nodes' CURRENT states, Sigma at the l_points of the last solver call.  No z is taken: the Jacobians of an
+ * xyt factor do not depend on the measurement, so the gain is known before the measurement exists.  Where states and l_points coincide,
+ * 2 gain = ln det (A + H' W H) - ln det A: what aprilsam_amd_logdet would grow by if the factors were really added.  Every prefix is >= 0
+ * and the prefixes do not decrease, up to rounding.  Argument rules, refusals and the return value (the number of hypotheses with a pivot
+ * that was not positive, NaN from that candidate on) are _gate_xyt_joint's, without z: -12 also a W that is not symmetric positive
+ * definite; -13 also a == b, a non-finite W, a bad hyp_ptr, a node id out of range.  n_hyp == 0 returns 0. */
+#define APRILSAM_AMD_SET_MAX 16        /* nodes per set */
+int aprilsam_amd_logdet(april_graph_t *graph, april_graph_cholesky_param_t *param, double *logdet);
+int aprilsam_amd_logdet_sets(april_graph_t *graph, april_graph_cholesky_param_t *param, int n_sets, const int *set_ptr, const int *nodes,
+                             double *logdet_prefix);
+int aprilsam_amd_info_gain_xyt(april_graph_t *graph, april_graph_cholesky_param_t *param, int n_hyp, const int *hyp_ptr, const int *a, const int *b,
+                               const double *W, double *gain_prefix);
+
 /* ---- solves with the retained factor -----------------------------------------------------------------------
  * The system is the one aprilsam_amd_marginals describes: A = sum J^T W J + diag(lambda) of the last successful solver call on `param`
  * (lambda where that step put it, everything at the l_points, robust and max factors as they were factorised).  Write A = P' L L' P with
