@@ -166,6 +166,16 @@ __device__ __forceinline__ void xyt_joint_cov(const double *J0, const double *J1
         }
 }
 
+// wi = W^-1 (3 x 3, row-major) by the adjugate, nine quotients by det W, which is returned: what every gate of xyt candidates adds to
+// its innovation covariance, and the gain takes the logarithm of
+__device__ __forceinline__ double xyt_info_inverse(const double *W, double *wi) {
+    const double det = W[0] * (W[4] * W[8] - W[5] * W[7]) - W[1] * (W[3] * W[8] - W[5] * W[6]) + W[2] * (W[3] * W[7] - W[4] * W[6]);
+    wi[0] = (W[4] * W[8] - W[5] * W[7]) / det; wi[1] = (W[2] * W[7] - W[1] * W[8]) / det; wi[2] = (W[1] * W[5] - W[2] * W[4]) / det;
+    wi[3] = (W[5] * W[6] - W[3] * W[8]) / det; wi[4] = (W[0] * W[8] - W[2] * W[6]) / det; wi[5] = (W[2] * W[3] - W[0] * W[5]) / det;
+    wi[6] = (W[3] * W[7] - W[4] * W[6]) / det; wi[7] = (W[1] * W[6] - W[0] * W[7]) / det; wi[8] = (W[0] * W[4] - W[1] * W[3]) / det;
+    return det;
+}
+
 // One thread per candidate (a, b, z, W): in = { state a (3), state b (3), z (3), W (9, row-major) }, cov its joint block.
 //   r, J_a, J_b    the xyt factor's residual (theta wrapped) and Jacobians at the states (factor_residual)
 //   S = [J_a J_b] cov [J_a J_b]' + W^-1,   d2 = r' S^-1 r   (Cholesky of S)
@@ -176,11 +186,8 @@ __global__ void __launch_bounds__(256) k_gate_xyt(int n, const double *__restric
     const double *q = in + 18ll * i, *C = cov + 36ll * i;
     double J0[9], J1[9], r[3];
     factor_residual(true, q, q + 3, q + 6, J0, J1, r);
-    const double *W = q + 9;                              // W^-1 by the adjugate (W was checked positive definite on the host)
-    const double det = W[0] * (W[4] * W[8] - W[5] * W[7]) - W[1] * (W[3] * W[8] - W[5] * W[6]) + W[2] * (W[3] * W[7] - W[4] * W[6]);
-    const double Wi[9] = { (W[4] * W[8] - W[5] * W[7]) / det, (W[2] * W[7] - W[1] * W[8]) / det, (W[1] * W[5] - W[2] * W[4]) / det,
-                           (W[5] * W[6] - W[3] * W[8]) / det, (W[0] * W[8] - W[2] * W[6]) / det, (W[2] * W[3] - W[0] * W[5]) / det,
-                           (W[3] * W[7] - W[4] * W[6]) / det, (W[1] * W[6] - W[0] * W[7]) / det, (W[0] * W[4] - W[1] * W[3]) / det };
+    double Wi[9];
+    xyt_info_inverse(q + 9, Wi);                          // (W was checked positive definite on the host)
     double S[9];
     xyt_joint_cov(J0, J1, C, S);
 #pragma unroll

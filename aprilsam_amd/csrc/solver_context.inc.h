@@ -115,7 +115,7 @@ struct PathState {
     DBuf<PsFront> d_fr; DBuf<int4> d_ent; DBuf<int> d_cmap; DBuf<long long> d_at; DBuf<PsPath> d_path; DBuf<PsPair> d_pair;
     DBuf<double> d_buf, d_cov, d_in; HBuf<double> h_out;
     DBuf<int> d_pidx;                      // k_gate_polar: candidate -> its pair's block in d_cov
-    DBuf<int> d_jtab; DBuf<long long> d_joff;      // k_gate_xyt_joint: hyp_ptr | tab_ptr | the index table; the matrices' offsets
+    DBuf<int> d_jtab; DBuf<long long> d_joff;      // k_block_chol: hyp_ptr | tab_ptr | the index table; the matrices' offsets
     DBuf<LdEnt> d_ldent; DBuf<double> d_ldpart; DBuf<int> d_ldbad; HBuf<double> h_ld;      // k_logdet_partial / k_logdet_sum: the entries, the partials, the counts; the result
     long long ld_gen = -1; int ld_n = 0;   // FactorView::gen d_ldent describes, and its entries
     long long peak_doubles = 0;            // the largest work buffer a chunk has used

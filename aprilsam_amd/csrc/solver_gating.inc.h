@@ -117,18 +117,17 @@ static long long ps_budget() {
     return g_opt.mem_cap_mb > 0 ? std::min(dflt, ((long long)g_opt.mem_cap_mb << 20) / 8) : dflt;
 }
 
-// what a caller of ps_run runs behind the blocks in place of k_gate_xyt (the polar gates): `extra` doubles of S.h_out
-// behind the 36 n of the blocks, and what enqueues its copies and its kernel on the stream, which is synchronised after it
+// what a caller of ps_run runs behind the blocks (the gates, the information measures): `extra` doubles of S.h_out behind the 36 n of the
+// blocks, and what enqueues its copies and its kernel on the stream, which is synchronised after it
 struct PsTail { size_t extra = 0; std::function<void(hipStream_t)> enqueue; };
 
-// joint blocks of the n pairs (qa, qb) into S.d_cov / S.h_out (36 per pair); gate != null: then the gate of candidate i, in = 18
-// doubles each (k_gate_xyt), its d2 and S behind the blocks in S.h_out; tail != null (and gate_in null): the caller's kernel instead.
-static void ps_run(Context &c, hipStream_t s, int n, const int *qa, const int *qb, const double *gate_in, const PsTail *tail = nullptr) {
+// joint blocks of the n pairs (qa, qb) into S.d_cov / S.h_out (36 per pair): the path solves, the mask of the fixed nodes, then the tail
+static void ps_run(Context &c, hipStream_t s, int n, const int *qa, const int *qb, const PsTail *tail = nullptr) {
     const FactorView &V = factor_view(c);
     PathState &S = c.ps;
     if (S.gen != V.gen) { S.rec.assign(V.fr.size(), -1); S.node_j.assign((size_t)V.N, -1); S.gen = V.gen; }
     S.d_cov.need((size_t)36 * n);
-    S.h_out.need((size_t)(gate_in ? 46 : 36) * n + (tail ? tail->extra : 0));
+    S.h_out.need((size_t)36 * n + (tail ? tail->extra : 0));
     const long long budget = ps_budget();
     std::vector<int> nodes; std::vector<int2> pj;
     long long used = 0;
@@ -161,14 +160,6 @@ static void ps_run(Context &c, hipStream_t s, int n, const int *qa, const int *q
         HIPCHECK(hipGetLastError());
         HIPCHECK(hipStreamSynchronize(s));
     }
-    if (gate_in) {
-        S.d_in.need((size_t)18 * n);
-        HIPCHECK(hipMemcpyAsync(S.d_in.p, gate_in, (size_t)8 * 18 * n, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_gate_xyt, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, (const double *)S.d_in.p, (const double *)S.d_cov.p,
-                           S.h_out.p + (size_t)36 * n);
-        HIPCHECK(hipGetLastError());
-        HIPCHECK(hipStreamSynchronize(s));
-    }
     if (tail) {
         tail->enqueue(s);
         HIPCHECK(hipGetLastError());
@@ -194,7 +185,7 @@ static int joint_any_impl(april_graph_t *g, april_graph_cholesky_param_t *param,
     for (int i = 0; i < n; i++)
         if (qa[i] < 0 || qa[i] >= N || qb[i] < 0 || qb[i] >= N) return q.refuse(ERR_BAD_GRAPH, "%s", PS_RANGE_MSG);
     if (n == 0) return 0;
-    ps_run(c, q.stream(), n, qa, qb, nullptr);
+    ps_run(c, q.stream(), n, qa, qb);
     memcpy(cov, c.ps.h_out.p, (size_t)8 * 36 * n);
     return 0;
 }
@@ -211,6 +202,32 @@ static bool xyt_info_spd(const double *w) {
     return ok && p2 > 0;
 }
 
+// One candidate xyt measurement between a and b (z null: without one), before its information matrix is factorised: null, or what
+// ERR_BAD_GRAPH is refused for.  Every candidate of a call passes this before xyt_infos_spd judges the matrices (ERR_UNSUPPORTED, XYT_INFO_MSG)
+static const char *xyt_candidate_fault(int a, int b, const double *z, const double *W) {
+    if (a == b) return "a candidate joins a node to itself";
+    for (int k = 0; z && k < 3; k++) if (!std::isfinite(z[k])) return "a non-finite measurement";
+    for (int k = 0; k < 9; k++) if (!std::isfinite(W[k])) return "a non-finite information matrix";
+    return nullptr;
+}
+static bool xyt_infos_spd(int n, const double *W) {
+    for (int i = 0; i < n; i++) if (!xyt_info_spd(W + 9 * (size_t)i)) return false;
+    return true;
+}
+
+// the candidates as the kernels take them, 18 doubles each: the states of a and b, z (or three zeros), W
+static std::vector<double> xyt_candidates_pack(const april_graph_t *g, int n, const int *qa, const int *qb, const double *z, const double *W) {
+    std::vector<double> in((size_t)18 * n, 0.0);
+    april_graph_node_t **ns = (april_graph_node_t **)g->nodes->data;
+    for (int i = 0; i < n; i++) {
+        double *v = in.data() + (size_t)18 * i;
+        for (int k = 0; k < 3; k++) { v[k] = ns[qa[i]]->state[k]; v[3 + k] = ns[qb[i]]->state[k]; if (z) v[6 + k] = z[3 * (size_t)i + k]; }
+        for (int k = 0; k < 9; k++) v[9 + k] = W[9 * (size_t)i + k];
+    }
+    return in;
+}
+
+// candidate i against the joint block of its own pair (a[i], b[i]), one path solve per candidate: k_gate_xyt behind the blocks
 static int gate_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int n, const int *qa, const int *qb, const double *z, const double *W,
                      double *d2, double *Sout) {
     const char *who = "aprilsam_amd_gate_xyt";
@@ -220,22 +237,22 @@ static int gate_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int 
     Context &c = q.c();
     for (int i = 0; i < n; i++) {
         if (!ps_ids_ok(q, 1, qa + i) || !ps_ids_ok(q, 1, qb + i)) return q.refuse(ERR_BAD_GRAPH, "%s", PS_RANGE_MSG);
-        if (qa[i] == qb[i]) return q.refuse(ERR_BAD_GRAPH, "a candidate joins a node to itself");
-        for (int k = 0; k < 3; k++) if (!std::isfinite(z[3 * i + k])) return q.refuse(ERR_BAD_GRAPH, "a non-finite measurement");
-        for (int k = 0; k < 9; k++) if (!std::isfinite(W[9 * i + k])) return q.refuse(ERR_BAD_GRAPH, "a non-finite information matrix");
+        if (const char *why = xyt_candidate_fault(qa[i], qb[i], z + 3 * (size_t)i, W + 9 * (size_t)i)) return q.refuse(ERR_BAD_GRAPH, "%s", why);
     }
-    for (int i = 0; i < n; i++)
-        if (!xyt_info_spd(W + 9 * i)) return q.refuse(ERR_UNSUPPORTED, "%s", XYT_INFO_MSG);
+    if (!xyt_infos_spd(n, W)) return q.refuse(ERR_UNSUPPORTED, "%s", XYT_INFO_MSG);
     if (n == 0) return 0;
-    std::vector<double> in((size_t)18 * n);
-    april_graph_node_t **ns = (april_graph_node_t **)g->nodes->data;
-    for (int i = 0; i < n; i++) {
-        double *q = in.data() + (size_t)18 * i;
-        for (int k = 0; k < 3; k++) { q[k] = ns[qa[i]]->state[k]; q[3 + k] = ns[qb[i]]->state[k]; q[6 + k] = z[3 * i + k]; }
-        for (int k = 0; k < 9; k++) q[9 + k] = W[9 * i + k];
-    }
-    ps_run(c, q.stream(), n, qa, qb, in.data());
-    const double *o = c.ps.h_out.p + (size_t)36 * n;
+    const std::vector<double> in = xyt_candidates_pack(g, n, qa, qb, z, W);
+    PathState &S = c.ps;
+    PsTail tail;
+    tail.extra = (size_t)10 * n;                            // d2, then S
+    tail.enqueue = [&](hipStream_t st) {
+        S.d_in.need(in.size());
+        HIPCHECK(hipMemcpyAsync(S.d_in.p, in.data(), in.size() * 8, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_gate_xyt, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, (const double *)S.d_in.p, (const double *)S.d_cov.p,
+                           S.h_out.p + (size_t)36 * n);
+    };
+    ps_run(c, q.stream(), n, qa, qb, &tail);
+    const double *o = S.h_out.p + (size_t)36 * n;
     memcpy(d2, o, (size_t)8 * n);
     if (Sout) memcpy(Sout, o + n, (size_t)8 * 9 * n);
     return 0;
@@ -243,12 +260,12 @@ static int gate_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int 
 
 // ---- node sets and joint compatibility ---------------------------------------------------------------------------
 // The distinct unordered node pairs of one call, each solved once: slot s holds the 6 x 6 block of (ua[s], ub[s]) in the order it was first
-// asked for.  code(x, y) = 4 slot + quarter names the 3 x 3 block S(p, q) inside it (k_gate_xyt_joint's table entry) for the call's distinct
+// asked for.  code(x, y) = 4 slot + quarter names the 3 x 3 block S(p, q) inside it (the table entry of jointgate.hip.h's frame) for the call's distinct
 // nodes p = un[x], q = un[y]: quarter 1 the pair as stored, 2 the pair the other way round, 0 / 3 a node's own block -- taken from the
 // first pair that named the node.  The codes of all ordered index pairs lie in a table of nu x nu entries while the call names at most
 // DENSE_MAX distinct nodes (a branch-and-bound level shares a few tens of nodes among its hypotheses: one array read per entry of the
 // kernel's index table), in a hash map beyond.
-static_assert(JG_MAX == APRILSAM_AMD_JOINT_MAX, "k_gate_xyt_joint's LDS is sized for the header's limit");
+static_assert(JG_MAX == APRILSAM_AMD_JOINT_MAX, "the frame's LDS is sized for the header's limit");
 struct PairBook {
     static constexpr int DENSE_MAX = 1024;
     std::vector<int> un, ua, ub;                             // the distinct nodes, ascending; slot -> its pair (node ids)
@@ -297,7 +314,7 @@ static int marginals_set_impl(april_graph_t *g, april_graph_cholesky_param_t *pa
     const int nu = (int)B.un.size();
     if (nu == 1) B.add(0, 0);
     for (int x = 0; x < nu; x++) for (int y = x + 1; y < nu; y++) B.add(x, y);
-    ps_run(c, q.stream(), B.n(), B.ua.data(), B.ub.data(), nullptr);
+    ps_run(c, q.stream(), B.n(), B.ua.data(), B.ub.data());
     std::vector<int> ix((size_t)k);
     for (int i = 0; i < k; i++) ix[i] = B.index(nodes[i]);
     const double *o = c.ps.h_out.p;
@@ -311,89 +328,116 @@ static int marginals_set_impl(april_graph_t *g, april_graph_cholesky_param_t *pa
     return 0;
 }
 
-// n_hyp hypotheses (CSR hyp_ptr into a / b / z / W): nodes, then unordered node pairs, deduplicated across the whole call; k_gate_xyt_joint
-// behind the blocks.  What the checks can judge without the graph comes before the device is asked for.
-static int gate_joint_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int n_hyp, const int *hyp_ptr, const int *qa, const int *qb, const double *z,
-                           const double *W, double *d2, double *Cout) {
-    const char *who = "aprilsam_amd_gate_xyt_joint";
-    if (!g || !param || !hyp_ptr || !qa || !qb || !z || !W || !d2 || n_hyp < 0) return refuse(ERR_BAD_GRAPH, who, "null argument or negative count");
-    if (hyp_ptr[0] != 0) return refuse(ERR_BAD_GRAPH, who, "hyp_ptr does not start at 0");
-    for (int h = 0; h < n_hyp; h++) {
-        const long long m = (long long)hyp_ptr[h + 1] - hyp_ptr[h];
-        if (m < 0) return refuse(ERR_BAD_GRAPH, who, "hyp_ptr decreases at hypothesis %d", h);
-        if (m < 1 || m > APRILSAM_AMD_JOINT_MAX)
-            return refuse(ERR_BAD_GRAPH, who, "hypothesis %d has %lld candidates (1 to %d are allowed)", h, m, APRILSAM_AMD_JOINT_MAX);
+// CSR lists of 1 .. cap entries: 0 for well-formed offsets, else ERR_BAD_GRAPH refused for `who`, naming the offsets (`what`), the first
+// list at fault and its length
+static int csr_refusal(const char *who, const char *what, int n, const int *ptr, int cap) {
+    if (ptr[0] != 0) return refuse(ERR_BAD_GRAPH, who, "%s does not start at 0", what);
+    for (int h = 0; h < n; h++) {
+        const long long m = (long long)ptr[h + 1] - ptr[h];
+        if (m < 0) return refuse(ERR_BAD_GRAPH, who, "%s decreases at list %d", what, h);
+        if (m < 1 || m > cap) return refuse(ERR_BAD_GRAPH, who, "%s: list %d has %lld entries (1 to %d are allowed)", what, h, m, cap);
     }
-    const int n = hyp_ptr[n_hyp];
-    for (int i = 0; i < n; i++) {
-        if (qa[i] == qb[i]) return refuse(ERR_BAD_GRAPH, who, "a candidate joins a node to itself");
-        for (int k = 0; k < 3; k++) if (!std::isfinite(z[3 * (size_t)i + k])) return refuse(ERR_BAD_GRAPH, who, "a non-finite measurement");
-        for (int k = 0; k < 9; k++) if (!std::isfinite(W[9 * (size_t)i + k])) return refuse(ERR_BAD_GRAPH, who, "a non-finite information matrix");
+    return 0;
+}
+
+// The book of a call over hypotheses of candidates (qa[i], qb[i]), CSR hyp_ptr: the candidates' own pairs first (every node's own block comes
+// from a candidate's own pair), then the four cross pairs of every two candidates of a hypothesis
+struct HypBook : PairBook {
+    std::vector<int> xa, xb;                                 // the candidates' nodes as indices into un
+    HypBook(int n_hyp, const int *hyp_ptr, const int *qa, const int *qb) : PairBook(hyp_ptr[n_hyp], qa, qb) {
+        const int n = hyp_ptr[n_hyp];
+        xa.resize((size_t)n); xb.resize((size_t)n);
+        for (int i = 0; i < n; i++) { xa[i] = index(qa[i]); xb[i] = index(qb[i]); }
+        for (int i = 0; i < n; i++) add(xa[i], xb[i]);
+        for (int h = 0; h < n_hyp; h++)
+            for (int i = hyp_ptr[h]; i < hyp_ptr[h + 1]; i++)
+                for (int j = hyp_ptr[h]; j < i; j++)
+                    for (int e = 0; e < 4; e++) {
+                        const int x = (e & 2) ? xb[i] : xa[i], y = (e & 1) ? xb[j] : xa[j];
+                        if (x != y) add(x, y);
+                    }
     }
-    for (int i = 0; i < n; i++) if (!xyt_info_spd(W + 9 * (size_t)i)) return refuse(ERR_UNSUPPORTED, who, "%s", XYT_INFO_MSG);
-    RetainedQuery q(who, g, param);
-    if (int rc = q.admit()) return rc;
+    // the four entries of lower block (i, j): S(a_i,a_j), S(a_i,b_j), S(b_i,a_j), S(b_i,b_j); i == j: the four quarters of the candidate's own
+    // pair's block, turned round if the pair is stored as (b, a)
+    void entries(int i, int j, int *out) const {
+        if (i == j) {
+            const int own = code(xa[i], xb[i]), own0 = own & ~3, sw = (own & 3) == 1 ? 0 : 3;
+            for (int e = 0; e < 4; e++) out[e] = own0 + (e ^ sw);
+        } else
+            for (int e = 0; e < 4; e++) out[e] = code((e & 2) ? xb[i] : xa[i], (e & 1) ? xb[j] : xa[j]);
+    }
+};
+
+// The pairs of B solved, then jointgate.hip.h's frame with rider R over the n_hyp lists behind them.  Its table: hyp_ptr | tab_ptr | R::PER
+// entries per lower block, written by `entries(i, j, out)` for the positions i >= j of one list in the call's arrays; in: the candidates' 18 doubles,
+// or empty; C (or null): receives the lists' matrices, 9 m^2 doubles each, one behind the other.  `out` receives the n prefixes.  Returns
+// the number of lists with a pivot that was not positive
+template <class R, class Entries>
+static int block_lists_behind_paths(RetainedQuery &q, PairBook &B, int n_hyp, const int *hyp_ptr, const std::vector<double> &in, double *out, double *C, Entries entries) {
     Context &c = q.c();
-    if (!ps_ids_ok(q, n, qa) || !ps_ids_ok(q, n, qb)) return q.refuse(ERR_BAD_GRAPH, "%s", PS_RANGE_MSG);
-    if (n_hyp == 0) return 0;
-    PairBook B(n, qa, qb);
-    std::vector<int> xa((size_t)n), xb((size_t)n);          // the candidates' nodes as indices into B.un
-    for (int i = 0; i < n; i++) { xa[i] = B.index(qa[i]); xb[i] = B.index(qb[i]); }
-    for (int i = 0; i < n; i++) B.add(xa[i], xb[i]);       // (first: every node's own block comes from a candidate's own pair)
-    for (int h = 0; h < n_hyp; h++)
-        for (int i = hyp_ptr[h]; i < hyp_ptr[h + 1]; i++)
-            for (int j = hyp_ptr[h]; j < i; j++)
-                for (int e = 0; e < 4; e++) {
-                    const int x = (e & 2) ? xb[i] : xa[i], y = (e & 1) ? xb[j] : xa[j];
-                    if (x != y) B.add(x, y);
-                }
-    // hyp_ptr | tab_ptr | the table: per hypothesis and lower block (i, j) the four entries S(a_i,a_j), S(a_i,b_j), S(b_i,a_j), S(b_i,b_j)
+    PathState &S = c.ps;
+    const int n = hyp_ptr[n_hyp], np = B.n();
     std::vector<int> tab((size_t)2 * (n_hyp + 1));
     std::vector<long long> coff((size_t)n_hyp);
     long long nC = 0, nT = 0;
     for (int h = 0; h < n_hyp; h++) {
         const long long m = hyp_ptr[h + 1] - hyp_ptr[h];
         coff[h] = nC; nC += 9 * m * m;
-        tab[h] = hyp_ptr[h]; tab[(size_t)n_hyp + 1 + h] = (int)nT; nT += 2 * m * (m + 1);
-        if (nT > 0x7fffffff) fail(ERR_OOM, "the index table of %d hypotheses does not fit", n_hyp);
+        tab[h] = hyp_ptr[h]; tab[(size_t)n_hyp + 1 + h] = (int)nT; nT += R::PER * m * (m + 1) / 2;
+        if (nT > 0x7fffffff) fail(ERR_OOM, "the index table of %d lists does not fit", n_hyp);
     }
     tab[n_hyp] = n; tab[(size_t)2 * n_hyp + 1] = (int)nT;
-    tab.reserve(tab.size() + (size_t)nT);
+    size_t at = tab.size();
+    tab.resize(at + (size_t)nT);
     for (int h = 0; h < n_hyp; h++)
         for (int i = hyp_ptr[h]; i < hyp_ptr[h + 1]; i++)
-            for (int j = hyp_ptr[h]; j <= i; j++) {
-                // i == j: the four quarters of the candidate's own pair's block, turned round if the pair is stored as (b, a)
-                const int own = B.code(xa[i], xb[i]), own0 = own & ~3, sw = (own & 3) == 1 ? 0 : 3;
-                for (int e = 0; e < 4; e++) tab.push_back(i == j ? own0 + (e ^ sw) : B.code((e & 2) ? xb[i] : xa[i], (e & 1) ? xb[j] : xa[j]));
-            }
-    std::vector<double> in((size_t)18 * n);
-    april_graph_node_t **ns = (april_graph_node_t **)g->nodes->data;
-    for (int i = 0; i < n; i++) {
-        double *v = in.data() + (size_t)18 * i;
-        for (int k = 0; k < 3; k++) { v[k] = ns[qa[i]]->state[k]; v[3 + k] = ns[qb[i]]->state[k]; v[6 + k] = z[3 * (size_t)i + k]; }
-        for (int k = 0; k < 9; k++) v[9 + k] = W[9 * (size_t)i + k];
-    }
-    PathState &S = c.ps;
-    const int np = B.n();
+            for (int j = hyp_ptr[h]; j <= i; j++, at += R::PER) entries(i, j, tab.data() + at);
     PsTail tail;
-    tail.extra = (size_t)n + n_hyp + (Cout ? (size_t)nC : 0);         // the prefixes, the hypotheses' flags, the matrices
+    tail.extra = (size_t)n + n_hyp + (C ? (size_t)nC : 0);   // the prefixes, the lists' flags, the matrices
     tail.enqueue = [&](hipStream_t st) {
-        S.d_in.need(in.size()); S.d_jtab.need(tab.size()); S.d_joff.need(coff.size());
-        HIPCHECK(hipMemcpyAsync(S.d_in.p, in.data(), in.size() * 8, hipMemcpyHostToDevice, st));
+        S.d_jtab.need(tab.size());
         HIPCHECK(hipMemcpyAsync(S.d_jtab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st));
-        HIPCHECK(hipMemcpyAsync(S.d_joff.p, coff.data(), coff.size() * 8, hipMemcpyHostToDevice, st));
+        if (!in.empty()) {
+            S.d_in.need(in.size());
+            HIPCHECK(hipMemcpyAsync(S.d_in.p, in.data(), in.size() * 8, hipMemcpyHostToDevice, st));
+        }
+        if (C) {
+            S.d_joff.need(coff.size());
+            HIPCHECK(hipMemcpyAsync(S.d_joff.p, coff.data(), coff.size() * 8, hipMemcpyHostToDevice, st));
+        }
         double *o = S.h_out.p + (size_t)36 * np;
         const int *t = S.d_jtab.p;
-        hipLaunchKernelGGL(k_gate_xyt_joint, dim3((unsigned)n_hyp), dim3(JG_T), 0, st, n_hyp, t, t + n_hyp + 1, t + 2 * (n_hyp + 1), (const long long *)S.d_joff.p,
-                           (const double *)S.d_in.p, np, (const double *)S.d_cov.p, o, o + n, Cout ? o + n + n_hyp : (double *)nullptr);
+        launch_block_chol<R>(st, n_hyp, t, t + n_hyp + 1, t + 2 * (n_hyp + 1), np, (const double *)S.d_cov.p, o, o + n,
+                             in.empty() ? (const double *)nullptr : (const double *)S.d_in.p, C ? (const long long *)S.d_joff.p : (const long long *)nullptr,
+                             C ? o + n + n_hyp : (double *)nullptr);
     };
-    ps_run(c, q.stream(), np, B.ua.data(), B.ub.data(), nullptr, &tail);
+    ps_run(c, q.stream(), np, B.ua.data(), B.ub.data(), &tail);
     const double *o = S.h_out.p + (size_t)36 * np;
-    memcpy(d2, o, (size_t)8 * n);
-    if (Cout) memcpy(Cout, o + n + n_hyp, (size_t)8 * nC);
+    memcpy(out, o, (size_t)8 * n);
+    if (C) memcpy(C, o + n + n_hyp, (size_t)8 * nC);
     int bad = 0;
     for (int h = 0; h < n_hyp; h++) bad += o[n + h] != 0.0;
     return bad;
+}
+
+// n_hyp hypotheses (CSR hyp_ptr into a / b / z / W): nodes, then unordered node pairs, deduplicated across the whole call; the frame with
+// JointGate behind the blocks.  What the checks can judge without the graph comes before the device is asked for.
+static int gate_joint_impl(april_graph_t *g, april_graph_cholesky_param_t *param, int n_hyp, const int *hyp_ptr, const int *qa, const int *qb, const double *z,
+                           const double *W, double *d2, double *Cout) {
+    const char *who = "aprilsam_amd_gate_xyt_joint";
+    if (!g || !param || !hyp_ptr || !qa || !qb || !z || !W || !d2 || n_hyp < 0) return refuse(ERR_BAD_GRAPH, who, "null argument or negative count");
+    if (int rc = csr_refusal(who, "hyp_ptr", n_hyp, hyp_ptr, APRILSAM_AMD_JOINT_MAX)) return rc;
+    const int n = hyp_ptr[n_hyp];
+    for (int i = 0; i < n; i++)
+        if (const char *why = xyt_candidate_fault(qa[i], qb[i], z + 3 * (size_t)i, W + 9 * (size_t)i)) return refuse(ERR_BAD_GRAPH, who, "%s", why);
+    if (!xyt_infos_spd(n, W)) return refuse(ERR_UNSUPPORTED, who, "%s", XYT_INFO_MSG);
+    RetainedQuery q(who, g, param);
+    if (int rc = q.admit()) return rc;
+    if (!ps_ids_ok(q, n, qa) || !ps_ids_ok(q, n, qb)) return q.refuse(ERR_BAD_GRAPH, "%s", PS_RANGE_MSG);
+    if (n_hyp == 0) return 0;
+    HypBook B(n_hyp, hyp_ptr, qa, qb);
+    return block_lists_behind_paths<JointGate>(q, B, n_hyp, hyp_ptr, xyt_candidates_pack(g, n, qa, qb, z, W), d2, Cout,
+                                               [&](int i, int j, int *out) { B.entries(i, j, out); });
 }
 
 // ---- polar gates ----------------------------------------------------------------------------------------------
@@ -437,7 +481,7 @@ static int gate_polar_impl(april_graph_t *g, april_graph_cholesky_param_t *param
         HIPCHECK(hipMemcpyAsync(S.d_pidx.p, pidx.data(), (size_t)4 * n, hipMemcpyHostToDevice, st));
         launch_polar_gate(st, k_gate_polar, n, false, n, (const double *)S.d_in.p, (const int *)S.d_pidx.p, (const double *)S.d_cov.p, S.h_out.p + (size_t)36 * np);
     };
-    ps_run(c, q.stream(), np, ua.data(), ub.data(), nullptr, &tail);
+    ps_run(c, q.stream(), np, ua.data(), ub.data(), &tail);
     const double *o = S.h_out.p + (size_t)36 * np;
     memcpy(d2, o, (size_t)8 * n);
     if (Sout) memcpy(Sout, o + n, (size_t)8 * 4 * n);
@@ -489,7 +533,7 @@ static int associate_polar_impl(april_graph_t *g, april_graph_cholesky_param_t *
         launch_polar_gate(sq, k_associate_polar, m, true, L, (const double *)S.d_in.p, (const double *)S.d_in.p + (size_t)PG_OBS * m, (const double *)S.d_cov.p,
                           gate1, gate2, d2 ? o : (double *)nullptr, (int2 *)(o + nmat + (size_t)2 * m), o + nmat, o + nmat + m);
     };
-    ps_run(c, q.stream(), L, qa.data(), landmarks, nullptr, &tail);
+    ps_run(c, q.stream(), L, qa.data(), landmarks, &tail);
     const double *o = S.h_out.p + (size_t)36 * L;
     if (d2) memcpy(d2, o, 8 * nmat);
     memcpy(d2_best, o + nmat, (size_t)8 * m);

@@ -262,13 +262,15 @@ template <class K, class... Args> static void launch_polar_gate(hipStream_t s, K
     hipLaunchKernelGGL(kern, dim3((unsigned)(per_item ? work : (work + PG_T - 1) / PG_T)), dim3(PG_T), 0, s, a...);
 }
 
-// The kernels of infomeasure.hip.h.  k_logdet_partial (one wave per entry, four per workgroup; k_logdet_sum, one
-// workgroup, follows it on the stream and is enqueued with it: `a` = the pool, the partials, the counts, then the sum's output) and
-// k_logdet_blocks (one wave per set / hypothesis, behind the path solves; `a` = what follows the count).  No work: no launch
-template <class K, class... Args> static void launch_info(hipStream_t s, K kern, int work, const Args &...a) {
-    if (work <= 0) return;
-    hipLaunchKernelGGL(kern, dim3((unsigned)work), dim3(JG_T), 0, s, work, a...);
+// The frame of jointgate.hip.h with rider R (JointGate; infomeasure.hip.h's SetLogdet, InfoGain), behind the path solves of a call: one wave
+// per list; `a` = what follows the count.  No lists: no launch
+template <class R, class... Args> static void launch_block_chol(hipStream_t s, int n_lists, const Args &...a) {
+    if (n_lists <= 0) return;
+    hipLaunchKernelGGL(k_block_chol<R>, dim3((unsigned)n_lists), dim3(JG_T), 0, s, n_lists, a...);
 }
+
+// The kernels of infomeasure.hip.h that read the factor itself: k_logdet_partial (one wave per entry, four per
+// workgroup) and k_logdet_sum (one workgroup), which follows it on the stream and is enqueued with it
 static void launch_info(hipStream_t s, int n_ent, const LdEnt *ent, const double *pool, double *part, int *nbad, double *out) {
     if (n_ent > 0) hipLaunchKernelGGL(k_logdet_partial, dim3((unsigned)((n_ent + 3) / 4)), dim3(TPB), 0, s, ent, n_ent, pool, part, nbad);
     hipLaunchKernelGGL(k_logdet_sum, dim3(1), dim3(LD_SUM_T), 0, s, n_ent, (const double *)part, (const int *)nbad, out);

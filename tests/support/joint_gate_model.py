@@ -1,4 +1,4 @@
-"""numpy model of aprilsam_amd_marginals_set and aprilsam_amd_gate_xyt_joint (k_gate_xyt_joint, aprilsam_amd/csrc/jointgate.hip.h).  TEST-ONLY.
+"""numpy model of aprilsam_amd_marginals_set and aprilsam_amd_gate_xyt_joint (k_block_chol<JointGate>, aprilsam_amd/csrc/jointgate.hip.h).  TEST-ONLY.
 
 For a hypothesis of m candidate xyt measurements (a_i, b_i, z_i, W_i), with Sigma the dense inverse of the factorised system
 (tests/support/selinv_model.py: system_blocks, dense_system):
